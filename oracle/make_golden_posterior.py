@@ -1,9 +1,12 @@
 """TEST INFRASTRUCTURE ONLY -- posterior / MCMC fixtures produced by the REFERENCE'S OWN CODE.
 
-    python oracle/make_golden.py posterior   ->  tests/golden/mcmc_chains.npz, bolfi_posterior.npz, maxvar.npz
+    python oracle/make_golden.py posterior   ->  tests/golden/mcmc_chains.npz, nuts_abs15.npz, bolfi_posterior.npz,
+                                                 maxvar.npz
 
 * mcmc_chains: elfi.methods.mcmc.nuts / metropolis (mcmc.py:114-429), the real functions, on an analytic
   bounded target (a correlated Gaussian with a quartic term, -inf outside a box), four chains each.
+* nuts_abs15: the real elfi.methods.mcmc.nuts on a second target, -sum |x|^1.5 inside a box of half-width 5 (a
+  gradient that is not smooth at 0), two three-dimensional chains of 80 draws with the default adaptation.
 * bolfi_posterior: the real elfi.methods.posteriors.BolfiPosterior (posteriors.py:20-212) over the real
   GPyRegression class carrying the oracle's posterior quantities (the stand-in `_gp` of make_golden_gp.py),
   with the real ModelPrior of a two-parameter ElfiModel with uniform priors: logpdf / gradient_logpdf at
@@ -40,6 +43,14 @@ def mcmc_grad(x):
     return g
 
 
+def abs15_target(x):
+    return float(-np.sum(np.abs(x) ** 1.5) if np.all(np.abs(x) < 5) else -np.inf)
+
+
+def abs15_grad(x):
+    return -1.5 * np.sign(x) * np.abs(x) ** 0.5 if np.all(np.abs(x) < 5) else np.zeros_like(x)
+
+
 def main(elfi, golden_dir):
     from elfi.methods import mcmc
     from elfi.methods.bo.gpy_regression import GPyRegression
@@ -58,6 +69,11 @@ def main(elfi, golden_dir):
     np.savez_compressed(os.path.join(golden_dir, 'mcmc_chains.npz'), inits=inits, seeds=seeds, sigma=sig, nuts=nuts,
                         nuts_fixed=nuts_fixed, metropolis=metro, lo=LO, hi=HI, A=A)
     print('mcmc_chains: nuts', nuts.shape, 'metropolis', metro.shape)
+    inits = np.array([[0.3, -0.2, 1.0], [2.0, 2.0, -3.0]])
+    seeds = np.array([5, 6])
+    nuts = np.array([mcmc.nuts(80, inits[c], abs15_target, abs15_grad, seed=int(seeds[c])) for c in range(2)])
+    np.savez_compressed(os.path.join(golden_dir, 'nuts_abs15.npz'), inits=inits, seeds=seeds, nuts=nuts)
+    print('nuts_abs15: nuts', nuts.shape)
 
     out = {}
     n, d, seed = 200, 2, 31
