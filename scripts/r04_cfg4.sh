@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/r4cfg4}
 mkdir -p $OUT
 export TMPDIR=/tmp
 R=$PWD
-CMD="bench.py --workload adaptive --steps 10 --warmup 3 --no-cpu-baseline --no-bolfi"
+CMD="bench.py --full --workload adaptive --steps 10 --warmup 3 --no-cpu-baseline --no-bolfi"
 timeout 300 python $CMD > $OUT/bench_adaptive.json 2> $OUT/bench_adaptive.err
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d $R/$OUT/trace -o bench -- python $R/$CMD > $R/$OUT/trace.log 2>&1

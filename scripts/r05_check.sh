@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 TESTS=${@:-tests/test_distance_gpu.py tests/test_selection_gpu.py tests/test_gp_gpu.py tests/test_gp_hyper_gpu.py}
 timeout 1500 python -m pytest $TESTS -x -q -m gpu > $OUT/pytest.log 2>&1
 tail -15 $OUT/pytest.log
-( time timeout 600 python bench.py --no-cpu-baseline --cfg3 off --e2e off ) > $OUT/bench_short.json 2> $OUT/bench_short.err
+( time timeout 600 python bench.py --full --no-cpu-baseline --cfg3 off --e2e off ) > $OUT/bench_short.json 2> $OUT/bench_short.err
 tail -3 $OUT/bench_short.err
 python - <<PY
 import json

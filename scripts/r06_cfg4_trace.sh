@@ -9,9 +9,9 @@ export TMPDIR=/tmp
 R=$PWD
 for tag in full shard; do
   if [ $tag = full ]; then A="--scaling strong --total 10000000"; else A="--scaling weak --n 1250000"; fi
-  python bench.py --workload adaptive $A --m 64 --steps 30 --warmup 5 --no-cpu-baseline > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
+  python bench.py --full --workload adaptive $A --m 64 --steps 30 --warmup 5 --no-cpu-baseline > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
   cd /tmp
-  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $R/$OUT/trace_$tag -o bench -- python $R/bench.py --workload adaptive $A --m 64 --steps 30 --warmup 5 --no-cpu-baseline > $R/$OUT/prof_$tag.json 2> $R/$OUT/prof_$tag.err
+  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $R/$OUT/trace_$tag -o bench -- python $R/bench.py --full --workload adaptive $A --m 64 --steps 30 --warmup 5 --no-cpu-baseline > $R/$OUT/prof_$tag.json 2> $R/$OUT/prof_$tag.err
   cd $R
   f=$(find $OUT/trace_$tag -name "*kernel_trace.csv" | head -1)
   python scripts/step_timeline.py $f reject_init_kernel 20 2 > $OUT/timeline_$tag.txt

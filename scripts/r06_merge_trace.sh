@@ -6,9 +6,9 @@ OUT=${1:-gpurun_out/r6merge}
 mkdir -p $OUT
 export TMPDIR=/tmp
 R=$PWD
-python bench.py --steps 50 --warmup 5 --no-bolfi --no-cfg4 --e2e off --cfg3 off --no-cpu-baseline > $OUT/bench_dist.json 2> $OUT/bench_dist.err
+python bench.py --full --steps 50 --warmup 5 --no-bolfi --no-cfg4 --e2e off --cfg3 off --no-cpu-baseline > $OUT/bench_dist.json 2> $OUT/bench_dist.err
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/trace -o bench -- python $R/bench.py --steps 50 --warmup 5 --no-bolfi --no-cfg4 --e2e off --cfg3 off --no-cpu-baseline > $R/$OUT/prof_dist.json 2> $R/$OUT/prof_dist.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/trace -o bench -- python $R/bench.py --full --steps 50 --warmup 5 --no-bolfi --no-cfg4 --e2e off --cfg3 off --no-cpu-baseline > $R/$OUT/prof_dist.json 2> $R/$OUT/prof_dist.err
 cd $R
 for f in $(find $OUT/trace -name "*.db"); do python scripts/rocprof_summary.py $f "bench.py distance only" > $OUT/trace_summary.md; done
 rm -rf $OUT/trace

@@ -44,7 +44,7 @@ calls, tot, avg = m.groups()
 kms = c["roofline"]["kernel_ms"]
 open(P + "/r06_distance_pmc.md", "w").write('''# rocprofv3 PMC passes for the distance kernel, round 6 (separate runs, one counter each)
 
-Command (each): `rocprofv3 --kernel-trace --pmc <COUNTER> --output-format csv -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-bolfi --no-cfg4 --e2e off`
+Command (each): `rocprofv3 --kernel-trace --pmc <COUNTER> --output-format csv -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-bolfi --no-cfg4 --e2e off`
 (`scripts/r06_record.sh`).  Kernel: `elfihip::dist_rows_dma_kernel<0, false, 32, 64, 2>` (LDS-DMA row stream, the sampler's
 selection fused in through `RejectFilter`; unchanged since round 5) on 10^6 x 32 f64 rows, 28 dispatches per pass.
 

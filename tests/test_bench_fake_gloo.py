@@ -1,5 +1,5 @@
-"""bench.py's N > 1 control flow, executed: `python bench.py --gpus 2 --fake-device` (CPU tensors, gloo, the stand-in library
-of bench_fake.py) must run the whole script -- self-launch under torch.distributed.run on 127.0.0.1, both scaling legs
+"""bench.py's N > 1 control flow, executed: `python bench.py --gpus 2 --fake-device --full` (CPU tensors, gloo, the stand-in
+library of bench_fake.py) must run the whole script -- self-launch under torch.distributed.run on 127.0.0.1, both scaling legs
 (weak configs[1] with the per-step gather of the packed sampler states; strong configs[3] with the all-gather + fixed-order
 merge of the column statistics), every post-run assertion of rank 0 -- and print ONE well-formed JSON line that says it is a
 dry run.  No 8-GPU node has been available to the builder: this is what makes the first real multi-GPU run boring."""
@@ -14,7 +14,7 @@ REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
             "vs_baseline", "dtype", "data", "config", "roofline")
 
 
-def _run(gpus, extra=()):
+def _line(gpus, extra=()):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
@@ -28,7 +28,12 @@ def _run(gpus, extra=()):
     # the driver keeps the last 8 KB of stdout: the line it parses must fit with room to spare (round 5's 20.6 KB line
     # left BENCH_r05.json.parsed = null)
     assert len(lines[0]) < 6144, len(lines[0])
-    compact = json.loads(lines[0])
+    return p, json.loads(lines[0])
+
+
+def _run(gpus, extra=()):
+    """The --full run: every leg, the post-run checks, the detail record on stderr."""
+    p, compact = _line(gpus, ["--full"] + list(extra))
     assert json.loads(json.dumps(compact)) == compact
     detail = [ln for ln in p.stderr.splitlines() if ln.startswith("bench detail: ")]
     assert len(detail) == 1
@@ -68,3 +73,18 @@ def test_one_rank_and_the_adaptive_workload():
     assert r["config"]["samples_per_gpu"] == 200000
     r3 = _run(3, ["--workload", "adaptive", "--scaling", "strong", "--total", "100001"])
     assert r3["n_gpus"] == 3 and r3["env"]["world_size_seen"] == 3      # a total the ranks do not divide
+
+
+def test_a_plain_run_is_the_headline_alone():
+    """Without --full: the contract's keys of the headline workload, no roofline, no other leg, no detail record."""
+    for gpus, extra in ((2, []), (1, ["--workload", "adaptive", "--scaling", "strong"])):
+        p, line = _line(gpus, extra)
+        for k in REQUIRED:
+            assert (k in line) == (k != "roofline"), k
+        assert not any(k in line for k in ("cfg4_strong", "cpu_baseline", "bolfi", "env", "more", "detail"))
+        assert not any(ln.startswith("bench detail: ") for ln in p.stderr.splitlines())
+        assert line["n_gpus"] == gpus == line["config"]["world_size_seen"] and line["steps"] == 5 and line["warmup"] == 2
+        assert line["data"].startswith("fake") and "NOT measurements" in line["config"]["dry_run"]
+        assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["metric"] == "ABC distances/sec"
+        units = gpus * line["config"]["samples_per_gpu"] if line["scaling"] == "weak" else 200000
+        assert abs(line["value"] - units * 5 / (line["ms_per_step"] * 5e-3)) < 1e-6 * line["value"]
