@@ -158,13 +158,24 @@ __global__ __launch_bounds__(256) void dist_rows_pipe_kernel(RowArgs A) {
 // still sums row r left to right, so the results stay bit-identical to cdist.  Non-temporal loads: the rows are read once.
 // Measured on 10^6 x 32 (scripts/native/glds_probe.hip, profiles/r05_glds_probe.md): 41.8-42.1 us = 6.3 TB/s (40.7 on the
 // best box), against 46.5-47.2 us for the register-staged pipeline in the same binary.
-template <int METRIC, bool W, int MM, int ROWS, int D>
+// MERGE: workgroup 0 folds the sampler state's sealed candidate list A.M into the state (reject_merge_wave, in the ring's
+// LDS) and streams nothing; the other gridDim.x - 1 workgroups stream the slots.  The stream reads the threshold once, with
+// an atomic load: the k-th distance before this merge and the one after it are both upper bounds of the state's k-th
+// distance, so either keeps the filter exact.  Nothing waits across workgroups.
+template <int METRIC, bool W, int MM, int ROWS, int D, bool MERGE>
 __global__ __launch_bounds__(64) void dist_rows_dma_kernel(RowArgs A) {
   extern __shared__ __align__(16) double lds[];
   constexpr int SLOT = ROWS * MM;                // doubles
   constexpr int H = MM / 2;
   constexpr int PIECES = ROWS * H / 64;
   static_assert(ROWS <= 64 && (ROWS * H) % 64 == 0, "a slot is a whole number of 1 KiB DMA pieces, one row per lane");
+  static_assert(D * SLOT * 8 >= REJ_FUSED_LDS, "the merge role works in the slot ring");
+  if constexpr (MERGE) {
+    if (blockIdx.x == 0) {
+      reject_merge_wave(A.M, lds);
+      return;
+    }
+  }
   const int lane = threadIdx.x;
   double* ring = lds;
   double* ys = lds + (size_t)D * SLOT;
@@ -175,8 +186,14 @@ __global__ __launch_bounds__(64) void dist_rows_dma_kernel(RowArgs A) {
     if constexpr (W) as[lane] = A.aux[lane];
   }
   const int64_t nslots = (A.n + ROWS - 1) / ROWS;
-  const int64_t stride = gridDim.x;
-  const double thr = A.F.thr ? *A.F.thr : 0.0;   // fused selection: the sampler state's current k-th best distance
+  const int64_t stride = MERGE ? gridDim.x - 1 : gridDim.x;
+  double thr = 0.0;   // fused selection: the sampler state's current k-th best distance
+  if (A.F.thr) {
+    if constexpr (MERGE)
+      thr = __hip_atomic_load(A.F.thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (workgroup 0 may be rewriting it)
+    else
+      thr = *A.F.thr;
+  }
   unsigned off[PIECES];   // byte offset of this lane's granule of piece i from the slot's first row (the launcher checks
 #pragma unroll            // that 64 rows of pitch ldx stay below 2^31 bytes)
   for (int i = 0; i < PIECES; ++i) {
@@ -185,7 +202,7 @@ __global__ __launch_bounds__(64) void dist_rows_dma_kernel(RowArgs A) {
     off[i] = (unsigned)(((int64_t)row * A.ldx + 2 * (g ^ dma_swizzle_key<MM>(row))) * 8);
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // nothing of the prologue is outstanding: the counted
-  int64_t t = blockIdx.x;                                        // waits below see the DMA pieces and the stores only
+  int64_t t = MERGE ? blockIdx.x - 1 : blockIdx.x;               // waits below see the DMA pieces and the stores only
 #pragma unroll
   for (int k = 0; k < D - 1; ++k) {
     const int64_t tk = t + k * stride;
@@ -757,7 +774,7 @@ static int pipe_unroll(int m, bool light) {
 }
 
 template <int METRIC, bool W>
-static int launch_rows(elfihip_ctx* ctx, RowArgs A, bool* filtered) {
+static int launch_rows(elfihip_ctx* ctx, RowArgs A, bool* filtered, bool* merged) {
   if (A.m > kMaxTileM) {
     int64_t rows_per_block = 4;
     int64_t g = (A.n + rows_per_block - 1) / rows_per_block;
@@ -790,16 +807,29 @@ static int launch_rows(elfihip_ctx* ctx, RowArgs A, bool* filtered) {
     const int rows = A.m == 64 ? 32 : 64;
     const int D = A.m == 16 ? 4 : 2;
     const size_t ldsd = ((size_t)D * rows * A.m + 2 * (size_t)A.m) * sizeof(double);
+    // a sealed candidate list of the sampler state: workgroup 0 of the same grid merges it (the other 4 x CUs - 1 stream:
+    // 15 625 slots of 10^6 x 32 still take 16 trips at most)
+    const bool merge = A.M.k > 0 && A.F.thr != nullptr;
     int64_t gd = (int64_t)ctx->cu_count * 4;
     const int64_t nslots = (A.n + rows - 1) / rows;
-    if (gd > nslots) gd = nslots;
+    if (gd > nslots + (merge ? 1 : 0)) gd = nslots + (merge ? 1 : 0);
     if (gd < 1) gd = 1;
-    if (A.m == 16)
-      hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 16, 64, 4>), dim3((unsigned)gd), dim3(64), ldsd, ctx->stream, A);
-    else if (A.m == 32)
-      hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 32, 64, 2>), dim3((unsigned)gd), dim3(64), ldsd, ctx->stream, A);
-    else
-      hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 64, 32, 2>), dim3((unsigned)gd), dim3(64), ldsd, ctx->stream, A);
+    const dim3 grid((unsigned)gd), block(64);
+    if (merge) {
+      if (A.m == 16)
+        hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 16, 64, 4, true>), grid, block, ldsd, ctx->stream, A);
+      else if (A.m == 32)
+        hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 32, 64, 2, true>), grid, block, ldsd, ctx->stream, A);
+      else
+        hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 64, 32, 2, true>), grid, block, ldsd, ctx->stream, A);
+      if (merged) *merged = true;
+    } else if (A.m == 16) {
+      hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 16, 64, 4, false>), grid, block, ldsd, ctx->stream, A);
+    } else if (A.m == 32) {
+      hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 32, 64, 2, false>), grid, block, ldsd, ctx->stream, A);
+    } else {
+      hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 64, 32, 2, false>), grid, block, ldsd, ctx->stream, A);
+    }
     if (filtered) *filtered = A.F.thr != nullptr;   // this form offers its candidates itself, too
     return launch_status(ctx, "dist_rows_dma_kernel");
   }
@@ -897,6 +927,7 @@ static RowArgs make_row_args(const double* dX, int64_t n, int m, int64_t ldx, co
   A.R = 0;
   A.nt = 0;
   A.F = RejectFilter{nullptr, nullptr, nullptr, nullptr, 0u, 0ll};
+  A.M = RejectMergeJob{};
   A.vec2 = (m % 2 == 0) && (ldx % 2 == 0) && aligned16(dX);
   A.div_h = make_fastdiv((uint32_t)(A.vec2 ? m / 2 : m));
   return A;
@@ -1072,10 +1103,13 @@ __global__ __launch_bounds__(256, KC == 4 ? 3 : 4) void dist_rows_mahalanobis_sp
 }
 
 // F / filtered: fused selection (reject.hip).  *filtered tells the caller whether the kernel that ran offered the
-// candidates itself; otherwise the caller filters dout in a separate pass.
+// candidates itself; otherwise the caller filters dout in a separate pass.  M / merged: a sealed candidate list to merge
+// beside the pass (with F only); *merged tells whether the launch took it (the DMA row form), otherwise the caller merges it.
 int dist_rows_dev_impl(elfihip_ctx* ctx, int metric, const double* dX, int64_t n, int m, int64_t ldx, const double* dy,
-                       const double* daux, double p, double* dout, const RejectFilter* F, bool* filtered) {
+                       const double* daux, double p, double* dout, const RejectFilter* F, bool* filtered,
+                       const RejectMergeJob* M, bool* merged) {
   if (filtered) *filtered = false;
+  if (merged) *merged = false;
   ELFIHIP_REQUIRE(ctx, n >= 0 && m >= 1, "bad shape n=%lld m=%d", (long long)n, m);
   ELFIHIP_REQUIRE(ctx, ldx >= m, "ldx (%lld) < m (%d)", (long long)ldx, m);
   ELFIHIP_REQUIRE(ctx, n == 0 || (dX && dy && dout), "NULL data pointer");
@@ -1085,6 +1119,7 @@ int dist_rows_dev_impl(elfihip_ctx* ctx, int metric, const double* dX, int64_t n
   RowArgs A = make_row_args(dX, n, m, ldx, dy, daux, p, dout);
   A.nt = ctx->dist_form != 1;   // rows are read once: non-temporal loads (the register-staged forms: 16-byte nt loads)
   if (F) A.F = *F;
+  if (F && M && M->k > 0 && M->k <= REJ_FUSED_MAX_K) A.M = *M;
   const bool w = daux != nullptr;
   if (cm == ELFIHIP_MAHALANOBIS) {
     ELFIHIP_REQUIRE(ctx, m <= kMaxTileM, "mahalanobis supports m <= %d", kMaxTileM);
@@ -1134,7 +1169,7 @@ int dist_rows_dev_impl(elfihip_ctx* ctx, int metric, const double* dX, int64_t n
   }
 #define ELFIHIP_DISPATCH_ROWS(M)                                                  \
   case M:                                                                         \
-    return w ? launch_rows<M, true>(ctx, A, filtered) : launch_rows<M, false>(ctx, A, filtered);
+    return w ? launch_rows<M, true>(ctx, A, filtered, merged) : launch_rows<M, false>(ctx, A, filtered, merged);
   switch (cm) {
     ELFIHIP_DISPATCH_ROWS(ELFIHIP_EUCLIDEAN)
     ELFIHIP_DISPATCH_ROWS(ELFIHIP_SQEUCLIDEAN)
@@ -1142,7 +1177,7 @@ int dist_rows_dev_impl(elfihip_ctx* ctx, int metric, const double* dX, int64_t n
     ELFIHIP_DISPATCH_ROWS(ELFIHIP_CHEBYSHEV)
     ELFIHIP_DISPATCH_ROWS(ELFIHIP_MINKOWSKI)
     case ELFIHIP_SEUCLIDEAN:
-      return launch_rows<ELFIHIP_SEUCLIDEAN, true>(ctx, A, filtered);
+      return launch_rows<ELFIHIP_SEUCLIDEAN, true>(ctx, A, filtered, merged);
   }
 #undef ELFIHIP_DISPATCH_ROWS
   return fail(ctx, ELFIHIP_ERR_ARG, "unhandled metric %d", cm);

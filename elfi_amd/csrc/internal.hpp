@@ -9,9 +9,11 @@ struct elfihip_reject;
 namespace elfihip {
 
 // distance.hip: device-pointer distance passes, optionally with the fused selection filter (see RejectFilter).
-// *filtered reports whether the kernel that ran offered the candidates itself.
+// *filtered reports whether the kernel that ran offered the candidates itself; *merged whether it also merged the sealed
+// candidate list M (RejectMergeJob) into the sampler state.
 int dist_rows_dev_impl(elfihip_ctx* ctx, int metric, const double* dX, int64_t n, int m, int64_t ldx, const double* dy,
-                       const double* daux, double p, double* dout, const RejectFilter* F, bool* filtered);
+                       const double* daux, double p, double* dout, const RejectFilter* F, bool* filtered,
+                       const RejectMergeJob* M = nullptr, bool* merged = nullptr);
 int dist_multiw_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t n, int m, int64_t ldx, const double* dy,
                          const double* dW, int K, double* dout, const RejectFilter* F, bool* filtered);
 

@@ -13,6 +13,14 @@
 //     one-workgroup launch between two 48 us distance passes is a third of their time, and running it on a second
 //     stream costs a 10 us event hand-over per batch on this stack (both measured); result / reset / state_dev /
 //     flush merge what is pending first;
+//   * states with k <= REJ_FUSED_MAX_K hold TWO lists.  Pushed through the DMA row kernel, such a state does not merge
+//     at a merge point: it SEALS the open list and opens the other (empty) one, and the next push's distance launch takes
+//     the merge as a job -- workgroup 0 merges the sealed list in one wave (reject_merge_wave, tile_stream.hpp) while
+//     the other workgroups stream (dist_rows_dma_kernel<..., MERGE>).  Such states seal every p / 3 pushes, so that a
+//     sealed list stays within the 512-entry sort the wave finishes inside the pass.  Whatever cannot hand a sealed list
+//     to such a launch (flush, result, state_dev, meta, growing the lists, the selection and acceptance paths, the other
+//     push forms, adaptive_push_impl) merges it first with the standalone kernel.  Measured at 10^6 x 32, k = 1000:
+//     the fused launches take ~1 us more than the plain pass, against 16 us per standalone merge;
 //   * only while the state is still filling up (the first batch) the batch goes through the radix selection of topk.hip.
 // Only the k best rows ever leave the GPU; row numbers are global (row_base + row in the batch), so the host fetches the
 // parameters / summaries of the accepted rows from its own batch store (as ELFI's OutputPool keeps them).
@@ -41,17 +49,21 @@ struct elfihip_reject {
   double* best_val = nullptr;      // (k) ascending
   long long* best_row = nullptr;   // (k)
   double* thr = nullptr;           // device scalar: best_val[k-1]
-  double* cand_val = nullptr;      // (cap) candidates offered since the last merge
+  double* cand_val = nullptr;      // (cap) the OPEN list: candidates offered since it was last merged or sealed
   long long* cand_row = nullptr;   // (cap)
   unsigned int* count = nullptr;   // how many
+  double* sealed_val = nullptr;    // k <= REJ_FUSED_MAX_K: the second list (cap) -- sealed, waiting for its merge, or idle
+  long long* sealed_row = nullptr;
+  unsigned int* sealed_count = nullptr;
+  bool sealed = false;             // the second list holds candidates that are not merged yet
   unsigned int* status = nullptr;  // bit 0: more candidates were offered than the list holds
-  unsigned int cap = 0;
-  int unmerged = 0;                // pushes since the last merge
+  unsigned int cap = 0;            // entries per list
+  int unmerged = 0;                // pushes into the open list
   int64_t armed_pushes = 0;        // pushes since the state became full (sets the merge interval)
   void* export_dst = nullptr;      // optional: every merge also leaves the packed state (k values, k rows) here
-  elfihip::DevBuf cand_mem;        // the candidate list (cap pairs), grown to 8 x the largest batch
+  elfihip::DevBuf cand_mem;        // the candidate lists (cap pairs each), grown to 8 x the largest batch
   int64_t rows_seen = 0;           // rows offered so far
-  int64_t pending_rows = 0;        // rows of the filtered pushes since the last merge: bounds the list's length
+  int64_t pending_rows = 0;        // rows of the filtered pushes into the open list: bounds the list's length
   // acceptance threshold (samplers.py:219-225)
   bool has_accept = false;
   double accept = 0.0;
@@ -315,7 +327,7 @@ __global__ __launch_bounds__(256) void reject_mask_kernel(const double* d, int64
 }
 
 __global__ void reject_init_kernel(double* best_val, long long* best_row, double* thr, unsigned int* count,
-                                   unsigned int* status, unsigned long long* acc_count, int k) {
+                                   unsigned int* count2, unsigned int* status, unsigned long long* acc_count, int k) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   const double inf = __longlong_as_double(0x7ff0000000000000ll);
   if (e < k) {
@@ -325,6 +337,7 @@ __global__ void reject_init_kernel(double* best_val, long long* best_row, double
   if (e == 0) {
     *thr = inf;
     *count = 0u;
+    if (count2) *count2 = 0u;
     *status = 0u;
     *acc_count = 0ull;
   }
@@ -351,8 +364,37 @@ static RejArgs merge_args(elfihip_reject* h, int ncand, long long row_offset) {
 
 static int host_merge(elfihip_reject* h, unsigned int ncand, long long row_offset);
 
-// merge whatever the list holds (asynchronous on the context's stream; host-merge states synchronise)
+// the sealed list by the standalone merge, where no fused launch takes it (see reject_push)
+static int merge_sealed(elfihip_reject* h) {
+  if (!h->sealed) return ELFIHIP_OK;
+  h->sealed = false;
+  RejArgs S = merge_args(h, -1, 0);
+  S.cand_val = h->sealed_val;
+  S.cand_row = h->sealed_row;
+  S.count = h->sealed_count;
+  hipLaunchKernelGGL(reject_merge_kernel, dim3(1), dim3(1024), REJ_MERGE_LDS, h->ctx->stream, S);
+  return launch_status(h->ctx, "reject_merge_kernel");
+}
+
+// the sealed list's merge as a job for the next DMA row launch (export: the buffer current at that launch)
+static RejectMergeJob sealed_job(elfihip_reject* h) {
+  RejectMergeJob J;
+  J.best_val = h->best_val;
+  J.best_row = h->best_row;
+  J.thr = h->thr;
+  J.cand_val = h->sealed_val;
+  J.cand_row = h->sealed_row;
+  J.count = h->sealed_count;
+  J.status = h->status;
+  J.cap = h->cap;
+  J.k = (int)h->k;
+  J.export_val = reinterpret_cast<double*>(h->export_dst);
+  return J;
+}
+
+// merge whatever the lists hold (asynchronous on the context's stream; host-merge states synchronise)
 static int reject_flush(elfihip_reject* h) {
+  ELFIHIP_TRY(merge_sealed(h));
   if (h->unmerged == 0) return ELFIHIP_OK;
   h->unmerged = 0;
   h->pending_rows = 0;
@@ -363,10 +405,11 @@ static int reject_flush(elfihip_reject* h) {
 
 static int reject_reset_impl(elfihip_reject* h) {
   hipLaunchKernelGGL(reject_init_kernel, dim3((unsigned)((std::min<int64_t>(h->k, REJ_MAX_K) + 255) / 256)), dim3(256), 0,
-                     h->ctx->stream, h->best_val, h->best_row, h->thr, h->count, h->status, h->acc_count,
+                     h->ctx->stream, h->best_val, h->best_row, h->thr, h->count, h->sealed_count, h->status, h->acc_count,
                      (int)std::min<int64_t>(h->k, REJ_MAX_K));
   h->filled = 0;
   h->unmerged = 0;
+  h->sealed = false;
   h->armed_pushes = 0;
   h->rows_seen = 0;
   h->pending_rows = 0;
@@ -377,8 +420,24 @@ static int reject_reset_impl(elfihip_reject* h) {
   return launch_status(h->ctx, "reject_init_kernel");
 }
 
-// The list holds 8 x the largest batch (>= 65 536 entries): with a merge every 8th push at the latest it cannot
-// overflow.  Growing it merges what is pending, waits, and reallocates.
+// Candidate lists: one, or two for states the fused merge can take (k <= REJ_FUSED_MAX_K: one list is open for the pushes
+// while the other is sealed and merged beside the next distance pass).
+static int rej_nlists(const elfihip_reject* h) { return h->k <= REJ_FUSED_MAX_K ? 2 : 1; }
+
+static void rej_lay_out_lists(elfihip_reject* h) {
+  const size_t have = h->cand_mem.cap / (16 * (size_t)rej_nlists(h));
+  h->cap = (unsigned int)std::min<size_t>(have, 0x7fffffffu);
+  h->cand_val = h->cand_mem.as<double>();
+  h->cand_row = reinterpret_cast<long long*>(h->cand_val + h->cap);
+  if (rej_nlists(h) == 2) {
+    h->sealed_val = reinterpret_cast<double*>(h->cand_row + h->cap);
+    h->sealed_row = reinterpret_cast<long long*>(h->sealed_val + h->cap);
+  }
+}
+
+// A list holds 8 x the largest batch (>= 65 536 entries) and receives at most REJ_MERGE_EVERY pushes before it is merged
+// or sealed -- a sealed list receives nothing until its merge has emptied it -- so neither list can overflow.  (Two lists:
+// 2 x 128 MB at 10^6-row batches.)  Growing them merges what is pending, waits, and reallocates.
 static int ensure_cap(elfihip_reject* h, int64_t n) {
   const int64_t want = std::max<int64_t>(REJ_CAP, REJ_MERGE_EVERY * n);
   if (want <= (int64_t)h->cap) return ELFIHIP_OK;
@@ -386,12 +445,9 @@ static int ensure_cap(elfihip_reject* h, int64_t n) {
   ELFIHIP_REQUIRE(ctx, want < (int64_t)1 << 31, "batch of %lld rows is too large for the sampler state", (long long)n);
   ELFIHIP_TRY(reject_flush(h));
   ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  hipError_t e = h->cand_mem.reserve((size_t)want * 16);
+  hipError_t e = h->cand_mem.reserve((size_t)want * 16 * rej_nlists(h));
   if (e != hipSuccess) return fail(ctx, ELFIHIP_ERR_NOMEM, "candidate list allocation failed: %s", hipGetErrorString(e));
-  const size_t have = h->cand_mem.cap / 16;
-  h->cap = (unsigned int)std::min<size_t>(have, 0x7fffffffu);
-  h->cand_val = h->cand_mem.as<double>();
-  h->cand_row = reinterpret_cast<long long*>(h->cand_val + h->cap);
+  rej_lay_out_lists(h);
   return ELFIHIP_OK;
 }
 
@@ -477,12 +533,13 @@ static int host_upload(elfihip_reject* h) {
   return ELFIHIP_OK;
 }
 
-// Fold a batch into the state.  run(F, &filtered) launches the distance pass with the filter F (or without: F == nullptr)
-// on the context's stream; dsel / stride address the batch's ranking distances (the last of `ncols` nested columns) for
-// the passes that need them.
+// Fold a batch into the state.  run(F, M, &filtered, &merged) launches the distance pass with the filter F (or without:
+// F == nullptr) on the context's stream, and with it, if it can, the merge M of the sealed list; dsel / stride address the
+// batch's ranking distances (the last of `ncols` nested columns) for the passes that need them.  fusable: the pass is one
+// that can take a merge job (the row distances), so the state seals its open list at a merge point instead of merging it.
 template <class Run>
 static int reject_push(elfihip_reject* h, int64_t n, const double* dsel, int64_t stride, int ncols, long long row_base,
-                       Run run) {
+                       bool fusable, Run run) {
   elfihip_ctx* ctx = h->ctx;
   hipStream_t st = ctx->stream;
   ELFIHIP_TRY(ensure_cap(h, n));
@@ -495,7 +552,7 @@ static int reject_push(elfihip_reject* h, int64_t n, const double* dsel, int64_t
     // acceptance condition, state still filling up (or very many rows would qualify): mask, count, select (above)
     ELFIHIP_TRY(reject_flush(h));
     bool dummy = false;
-    ELFIHIP_TRY(run(nullptr, &dummy));
+    ELFIHIP_TRY(run(nullptr, nullptr, &dummy, &dummy));
     ELFIHIP_CHECK_HIP(ctx, h->mask_mem.reserve(((size_t)n + 2) * sizeof(double)));
     unsigned long long* bcount = h->mask_mem.as<unsigned long long>();
     double* masked = h->mask_mem.as<double>() + 2;
@@ -520,7 +577,7 @@ static int reject_push(elfihip_reject* h, int64_t n, const double* dsel, int64_t
     // selection writes its result there.
     ELFIHIP_TRY(reject_flush(h));
     bool dummy = false;
-    ELFIHIP_TRY(run(nullptr, &dummy));
+    ELFIHIP_TRY(run(nullptr, nullptr, &dummy, &dummy));
     const int64_t kb = n < h->k ? n : h->k;
     if (kb > 0) {
       ELFIHIP_TRY(topk_dev_impl(ctx, dsel, n, stride, kb, h->cand_val, reinterpret_cast<int64_t*>(h->cand_row), true));
@@ -540,15 +597,21 @@ static int reject_push(elfihip_reject* h, int64_t n, const double* dsel, int64_t
   F.count = h->count;
   F.cap = h->cap;
   F.row_base = row_base;
-  bool filtered = false;
-  // an acceptance threshold needs every column of a row: the separate candidate pass applies it
-  ELFIHIP_TRY(run(h->has_accept ? nullptr : &F, &filtered));
+  bool filtered = false, merged = false;
+  // an acceptance threshold needs every column of a row: the separate candidate pass applies it.  A sealed list goes with
+  // the pass as its merge job; a pass that cannot take it leaves it to the standalone merge below.
+  const RejectMergeJob J = h->sealed ? sealed_job(h) : RejectMergeJob{};
+  ELFIHIP_TRY(run(h->has_accept ? nullptr : &F, h->sealed ? &J : nullptr, &filtered, &merged));
   if ((!filtered || h->has_accept) && n > 0) {
     int g = (int)((n + 255) / 256);
     if (g > ctx->cu_count * 8) g = ctx->cu_count * 8;
     hipLaunchKernelGGL(reject_filter_kernel, dim3(g), dim3(256), 0, st, dsel, n, stride, ncols, F, h->has_accept ? 1 : 0,
                        h->acc_dev, h->acc_count);
   }
+  if (merged)
+    h->sealed = false;
+  else
+    ELFIHIP_TRY(merge_sealed(h));
   h->pending_rows += n;
   // rows that ENTERED the state: every offered row without an acceptance condition; with one, the accepted rows -- the
   // count elfihip_reject_meta reads back (until then the state keeps merging after every push, which is always correct)
@@ -557,11 +620,25 @@ static int reject_push(elfihip_reject* h, int64_t n, const double* dsel, int64_t
   // distribution), so merging every p / 2 pushes -- at most every REJ_MERGE_EVERY-th -- keeps a merge at about k / 2
   // candidates: early on, while the threshold still falls quickly, after every push.  Host-merge states and states
   // that are still filling merge after every push.
+  // A state that seals its lists (the merge rides on the next row pass) seals every p / 3 pushes instead: about k / 3
+  // candidates, which one wave sorts and merges inside the pass (measured at 10^6 x 32, k = 1000: lists of <= 512 cost
+  // the pass 1-2 us; lists just above 512 -- the 1024-entry sort -- 25 us more than the pass).
+  const bool seals = fusable && rej_nlists(h) == 2 && !h->has_accept;
   ++h->armed_pushes;
-  int64_t interval = h->armed_pushes / 2;
+  int64_t interval = h->armed_pushes / (seals ? 3 : 2);
   interval = interval < 1 ? 1 : (interval > REJ_MERGE_EVERY ? REJ_MERGE_EVERY : interval);
   if (h->host_mode || !full) interval = 1;
-  if (++h->unmerged >= interval) return reject_flush(h);
+  if (++h->unmerged >= interval) {
+    if (!seals) return reject_flush(h);
+    // seal the open list (its merge goes with the next push's pass) and open the other one, which is empty: its own merge
+    // ran before this push's pass was queued, or in it
+    std::swap(h->cand_val, h->sealed_val);
+    std::swap(h->cand_row, h->sealed_row);
+    std::swap(h->count, h->sealed_count);
+    h->sealed = true;
+    h->unmerged = 0;
+    h->pending_rows = 0;
+  }
   return launch_status(ctx, "distance pass with selection");
 }
 
@@ -570,9 +647,10 @@ elfihip_ctx* reject_ctx(elfihip_reject* h) { return h->ctx; }
 int reject_push_rows_impl(elfihip_reject* h, int metric, const double* dX, int64_t n, int m, int64_t ldx,
                           const double* dy, const double* daux, double p, double* dout, int64_t row_base) {
   elfihip_ctx* ctx = h->ctx;
-  return reject_push(h, n, dout, 1, 1, (long long)row_base, [&](const RejectFilter* F, bool* filtered) {
-    return dist_rows_dev_impl(ctx, metric, dX, n, m, ldx, dy, daux, p, dout, F, filtered);
-  });
+  return reject_push(h, n, dout, 1, 1, (long long)row_base, true,
+                     [&](const RejectFilter* F, const RejectMergeJob* M, bool* filtered, bool* merged) {
+                       return dist_rows_dev_impl(ctx, metric, dX, n, m, ldx, dy, daux, p, dout, F, filtered, M, merged);
+                     });
 }
 
 // ---- one AdaptiveDistance batch: distances + column statistics + selection in one read (adaptive.hip) -------------
@@ -653,6 +731,7 @@ int adaptive_push_impl(elfihip_ctx* ctx, elfihip_reject* h, const double* dX, in
   }
   ELFIHIP_REQUIRE(ctx, h->acc_ncols == 0 || h->acc_ncols == K, "%d acceptance thresholds but K = %d nested distances",
                   h->acc_ncols, K);
+  ELFIHIP_TRY(merge_sealed(h));   // (a list sealed by a row push: this pass takes no merge job)
   ELFIHIP_TRY(ensure_cap(h, n));
   const bool full = h->host_mode ? (int64_t)h->hval.size() >= h->k : h->filled >= h->k;
   const bool acc_select = h->has_accept && !h->host_mode && n >= REJ_ACC_SELECT_MIN &&
@@ -662,7 +741,8 @@ int adaptive_push_impl(elfihip_ctx* ctx, elfihip_reject* h, const double* dX, in
     double* o = dout;
     if (!o) ELFIHIP_TRY(scratch_out(n, &o));
     ELFIHIP_TRY(pass(0, n, nullptr, false, o));
-    ELFIHIP_TRY(reject_push(h, n, o + (K - 1), K, K, (long long)row_base, [&](const RejectFilter*, bool* filtered) {
+    ELFIHIP_TRY(reject_push(h, n, o + (K - 1), K, K, (long long)row_base, false,
+                            [&](const RejectFilter*, const RejectMergeJob*, bool* filtered, bool*) {
       *filtered = false;
       return ELFIHIP_OK;
     }));
@@ -740,7 +820,7 @@ int adaptive_push_impl(elfihip_ctx* ctx, elfihip_reject* h, const double* dX, in
       // the prefix did not represent the batch: selection over all n distances (recomputed when the caller kept none)
       if (early)   // the state as reject_reset leaves it (only a timed-out selection with a list of plausible length has been merged)
         hipLaunchKernelGGL(reject_init_kernel, dim3((unsigned)((std::min<int64_t>(h->k, REJ_MAX_K) + 255) / 256)), dim3(256), 0, st,
-                           h->best_val, h->best_row, h->thr, h->count, h->status, h->acc_count,
+                           h->best_val, h->best_row, h->thr, h->count, h->sealed_count, h->status, h->acc_count,
                            (int)std::min<int64_t>(h->k, REJ_MAX_K));
       hipLaunchKernelGGL(reject_unseed_kernel, dim3(1), dim3(1), 0, st, h->thr, h->count, h->best_val,
                          (int)std::min<int64_t>(h->k, REJ_MAX_K));
@@ -827,7 +907,7 @@ int elfihip_reject_create(elfihip_ctx* ctx, int64_t k, elfihip_reject** out) {
   h->host_mode = k > REJ_MAX_K;
   const size_t bytes = (size_t)k * 16 + 64;
   hipError_t e = h->mem.reserve(bytes);
-  if (e == hipSuccess) e = h->cand_mem.reserve((size_t)REJ_CAP * 16);
+  if (e == hipSuccess) e = h->cand_mem.reserve((size_t)REJ_CAP * 16 * rej_nlists(h));
   if (e == hipSuccess) e = h->acc_mem.reserve(REJ_ACC_COLS * sizeof(double));
   if (e != hipSuccess) {
     h->mem.release();
@@ -844,9 +924,8 @@ int elfihip_reject_create(elfihip_ctx* ctx, int64_t k, elfihip_reject** out) {
   h->count = reinterpret_cast<unsigned int*>(p + 8);
   h->status = reinterpret_cast<unsigned int*>(p + 12);
   h->acc_count = reinterpret_cast<unsigned long long*>(p + 16);
-  h->cap = (unsigned int)std::min<size_t>(h->cand_mem.cap / 16, 0x7fffffffu);
-  h->cand_val = h->cand_mem.as<double>();
-  h->cand_row = reinterpret_cast<long long*>(h->cand_val + h->cap);
+  if (rej_nlists(h) == 2) h->sealed_count = reinterpret_cast<unsigned int*>(p + 24);
+  rej_lay_out_lists(h);
   h->acc_dev = h->acc_mem.as<double>();
   int rc = reject_reset_impl(h);
   if (rc != ELFIHIP_OK) {
@@ -885,8 +964,8 @@ int elfihip_reject_push_multiw_dev(elfihip_reject* h, const double* dX, int64_t 
   ELFIHIP_REQUIRE(ctx, n >= 0 && K >= 1 && (n == 0 || dout), "the batch's distances need a destination (dout)");
   DeviceGuard g(ctx->device);
   // nested distances are ranked by their LAST column (samplers.py:233)
-  return reject_push(h, n, dout ? dout + (K - 1) : nullptr, K, K, (long long)row_base,
-                     [&](const RejectFilter* F, bool* filtered) {
+  return reject_push(h, n, dout ? dout + (K - 1) : nullptr, K, K, (long long)row_base, false,
+                     [&](const RejectFilter* F, const RejectMergeJob*, bool* filtered, bool*) {
                        return dist_multiw_dev_impl(ctx, dX, n, m, ldx, dy, dW, K, dout, F, filtered);
                      });
 }
@@ -896,7 +975,8 @@ int elfihip_reject_push_dev(elfihip_reject* h, const double* dD, int64_t n, int6
   elfihip_ctx* ctx = h->ctx;
   ELFIHIP_REQUIRE(ctx, n >= 0 && stride >= 1 && (n == 0 || dD), "bad arguments");
   DeviceGuard g(ctx->device);
-  return reject_push(h, n, dD, stride, 1, (long long)row_base, [&](const RejectFilter*, bool* filtered) {
+  return reject_push(h, n, dD, stride, 1, (long long)row_base, false,
+                     [&](const RejectFilter*, const RejectMergeJob*, bool* filtered, bool*) {
     *filtered = false;   // the distances exist already: candidates come from the separate pass
     return ELFIHIP_OK;
   });
@@ -916,7 +996,8 @@ int elfihip_reject_push_kept(elfihip_reject* h, uint64_t epoch, int64_t row_base
   if (n == 0) return ELFIHIP_OK;
   DeviceGuard g(ctx->device);
   const double* dD = ctx->keep.as<double>();
-  ELFIHIP_TRY(reject_push(h, n, dD + (K - 1), K, K, (long long)row_base, [&](const RejectFilter*, bool* filtered) {
+  ELFIHIP_TRY(reject_push(h, n, dD + (K - 1), K, K, (long long)row_base, false,
+                          [&](const RejectFilter*, const RejectMergeJob*, bool* filtered, bool*) {
     *filtered = false;
     return ELFIHIP_OK;
   }));
@@ -1020,7 +1101,8 @@ int elfihip_reject_push(elfihip_reject* h, const double* D, int64_t n, int ncols
   ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(bytes));
   double* dD = ctx->in.as<double>();
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dD, D, bytes, hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(reject_push(h, n, dD + (ncols - 1), ncols, ncols, (long long)row_base, [&](const RejectFilter*, bool* filtered) {
+  ELFIHIP_TRY(reject_push(h, n, dD + (ncols - 1), ncols, ncols, (long long)row_base, false,
+                          [&](const RejectFilter*, const RejectMergeJob*, bool* filtered, bool*) {
     *filtered = false;
     return ELFIHIP_OK;
   }));

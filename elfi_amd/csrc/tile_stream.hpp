@@ -56,6 +56,25 @@ __device__ __forceinline__ void reject_offer(const RejectFilter& F, bool hit, do
   }
 }
 
+// A sealed candidate list of the sampler state (reject.hip) that a DMA row launch merges beside its stream: one workgroup of
+// the grid folds it into the state while the others stream the rows (dist_rows_dma_kernel<..., MERGE = true>).  k == 0: none.
+struct RejectMergeJob {
+  double* best_val;            // (k) ascending by (distance, row)
+  long long* best_row;
+  double* thr;                 // <- the new k-th distance
+  const double* cand_val;      // the sealed list
+  const long long* cand_row;
+  unsigned int* count;         // its length (reset to 0 by the merge)
+  unsigned int* status;        // bit 0: the list overflowed
+  unsigned int cap;
+  int k;                       // <= REJ_FUSED_MAX_K
+  double* export_val;          // packed copy of the new state (k values, k rows), or NULL
+};
+
+constexpr int REJ_FUSED_MAX_K = 1024;    // state entries the fused merge holds in LDS
+constexpr int REJ_FUSED_CHUNK = 1024;    // candidates per round of the fused merge
+constexpr int REJ_FUSED_LDS = (REJ_FUSED_MAX_K + REJ_FUSED_CHUNK) * 16;   // 32 KiB: fits every DMA ring
+
 struct RowArgs {
   const double* X;
   int64_t n;
@@ -71,6 +90,7 @@ struct RowArgs {
   int nt;         // pipelined kernels: non-temporal loads
   FastDiv div_h;  // by m/2 (vec2) or m
   RejectFilter F; // fused selection (thr == nullptr: off)
+  RejectMergeJob M; // DMA row kernels: the fused merge role (M.k == 0: off)
 };
 
 // Stream one tile of `rows` rows starting at row0 into LDS (pitch mp).
@@ -266,6 +286,161 @@ __device__ __forceinline__ void wave_store_rows(double* stage, double* dst, cons
   if ((total & 1) && lane == 0) dst[total - 1] = stage[total - 1];
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();   // the stage is free again
+}
+
+// ---- the sampler state's merge as ONE wave (the fused role of dist_rows_dma_kernel) ------------------------------------------
+// state <- the k smallest of state U sealed list, in the total order (distance, row); a NaN never enters.  The wave owns
+// REJ_FUSED_LDS bytes of LDS (the slot ring of its launch): the state (k <= 1024 entries) and one chunk of 1024 candidates,
+// 16 bytes per (distance, row) entry.  Per chunk: the candidates are sorted by a bitonic network in LDS (each lane loads all
+// of its pairs of a step before it writes any: the pairs of a step are disjoint), then a merge-path split -- lane l produces
+// places [l Q, l Q + Q) of the merged sequence, Q = ceil(k / 64), from one binary search on its diagonal and Q sequential
+// steps -- and the first k places are written back.  No other workgroup is waited for.
+struct __attribute__((aligned(16))) RejEnt {
+  double v;
+  long long r;
+};
+__device__ __forceinline__ bool rej_before(const RejEnt& a, const RejEnt& b) {
+  return a.v < b.v || (a.v == b.v && a.r < b.r);
+}
+
+__device__ __forceinline__ void reject_merge_wave(const RejectMergeJob& J, void* smem) {
+  RejEnt* st = reinterpret_cast<RejEnt*>(smem);   // [REJ_FUSED_MAX_K]
+  RejEnt* ch = st + REJ_FUSED_MAX_K;               // [REJ_FUSED_CHUNK]
+  const int lane = threadIdx.x, k = J.k;
+  const double inf = __longlong_as_double(0x7ff0000000000000ll);
+  const long long maxrow = 0x7fffffffffffffffll;
+  unsigned int c = *J.count;
+  if (c > J.cap) {
+    if (lane == 0) atomicOr(J.status, 1u);   // the list is incomplete: reported by result
+    c = J.cap;
+  }
+  // Global loads: unconditional (clamped indices) and all issued before the first use -- the wave runs beside a stream
+  // that saturates HBM, and loads behind a branch each, waited for one by one, took 70-100 us per merge.
+  constexpr int PER = REJ_FUSED_CHUNK / 64;
+  static_assert(REJ_FUSED_MAX_K / 64 == PER, "one register set for the state's and the chunks' loads");
+  double lv[PER];
+  long long lr[PER];
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int e = min(lane + 64 * u, k - 1);
+    lv[u] = J.best_val[e];
+    lr[u] = J.best_row[e];
+  }
+#pragma unroll
+  for (int u = 0; u < PER; ++u)
+    if (lane + 64 * u < k) st[lane + 64 * u] = RejEnt{lv[u], lr[u]};
+  for (unsigned int c0 = 0; c0 < c; c0 += REJ_FUSED_CHUNK) {
+    const int nc = (int)min((unsigned int)REJ_FUSED_CHUNK, c - c0);
+    int P = 64;   // sorted length: a power of two, one entry per lane at least
+    while (P < nc) P <<= 1;
+    int nv = 0;   // candidates that take part (not NaN); they sort before the (+inf, max row) padding
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const unsigned int idx = c0 + (unsigned int)min(lane + 64 * u, nc - 1);
+      lv[u] = J.cand_val[idx];
+      lr[u] = J.cand_row[idx];
+    }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int i = lane + 64 * u;
+      const bool ok = i < nc && lv[u] == lv[u];
+      nv += __popcll(__ballot(ok));
+      if (i < P) ch[i] = ok ? RejEnt{lv[u], lr[u]} : RejEnt{inf, maxrow};
+    }
+    __syncthreads();   // (a one-wave workgroup: orders the LDS accesses of the wave's lanes)
+    for (int size = 2; size <= P; size <<= 1)
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        double av[PER / 2], bv[PER / 2];
+        long long ar[PER / 2], br[PER / 2];
+#pragma unroll
+        for (int u = 0; u < PER / 2; ++u) {
+          const int q = lane + 64 * u;   // pair q: (i, i + stride), i = 2 q - q mod stride
+          const int i = 2 * (q & (P / 2 - 1)) - (q & (stride - 1));   // (lanes beyond the pairs: any valid place)
+          const RejEnt x = ch[i], y = ch[i + stride];
+          av[u] = x.v;
+          ar[u] = x.r;
+          bv[u] = y.v;
+          br[u] = y.r;
+        }
+#pragma unroll
+        for (int u = 0; u < PER / 2; ++u) {
+          const int q = lane + 64 * u;
+          if (q < P / 2) {
+            const int i = 2 * q - (q & (stride - 1));
+            const bool asc = (i & size) == 0;
+            if (rej_before(RejEnt{bv[u], br[u]}, RejEnt{av[u], ar[u]}) == asc) {
+              ch[i] = RejEnt{bv[u], br[u]};
+              ch[i + stride] = RejEnt{av[u], ar[u]};
+            }
+          }
+        }
+        __syncthreads();
+      }
+    // merge path: lane l's places [d0, d1) of state (k) U sorted candidates (nv)
+    constexpr int QMAX = REJ_FUSED_MAX_K / 64;
+    const int Q = (k + 63) / 64;
+    const int d0 = min(lane * Q, k), d1 = min(d0 + Q, k);
+    int lo = max(0, d0 - nv), hi = min(d0, k);   // state entries among the first d0 places
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (rej_before(st[mid], ch[d0 - 1 - mid]))
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    double ov[QMAX];
+    long long orow[QMAX];
+    int ia = lo, ib = d0 - lo;
+#pragma unroll
+    for (int q = 0; q < QMAX; ++q) {
+      ov[q] = 0.0;
+      orow[q] = 0;
+      if (d0 + q < d1) {
+        const RejEnt sa = st[ia < k ? ia : k - 1], cb = ch[ib < nv ? ib : 0];
+        const bool take_state = ib >= nv || (ia < k && rej_before(sa, cb));
+        ov[q] = take_state ? sa.v : cb.v;
+        orow[q] = take_state ? sa.r : cb.r;
+        ia += take_state ? 1 : 0;
+        ib += take_state ? 0 : 1;
+      }
+    }
+    __syncthreads();   // every lane has read the state it needs
+#pragma unroll
+    for (int q = 0; q < QMAX; ++q)
+      if (d0 + q < d1) st[d0 + q] = RejEnt{ov[q], orow[q]};
+    __syncthreads();
+  }
+  __syncthreads();   // (an empty list: lane 0 reads the k-th entry another lane loaded)
+  // (the whole state into registers first: with LDS reads between them, every store was waited for before the next read)
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const RejEnt x = st[min(lane + 64 * u, k - 1)];
+    lv[u] = x.v;
+    lr[u] = x.r;
+  }
+  const double kth = st[k - 1].v;
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int e = lane + 64 * u;
+    if (e < k) {
+      J.best_val[e] = lv[u];
+      J.best_row[e] = lr[u];
+    }
+  }
+  if (J.export_val) {
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int e = lane + 64 * u;
+      if (e < k) {
+        J.export_val[e] = lv[u];
+        reinterpret_cast<long long*>(J.export_val + k)[e] = lr[u];
+      }
+    }
+  }
+  if (lane == 0) {
+    *J.thr = kth;
+    *J.count = 0u;
+  }
 }
 
 #endif

@@ -225,8 +225,11 @@ int elfihip_reject_state_dev(elfihip_reject* h, double** dvals, int64_t** drows)
 int elfihip_reject_export_dev(elfihip_reject* h, void* ddst);
 /* Candidates are merged into the state after every push at first and, once the threshold has settled, after every 8th
  * (a one-workgroup merge after every distance pass would cost a third of the pass); in between the list keeps growing against the last merged threshold, which still bounds the
- * current k-th distance from above, so nothing is missed.  elfihip_reject_flush merges what is pending now
- * (asynchronous); _result, _state_dev do so themselves. */
+ * current k-th distance from above, so nothing is missed.  States with k <= 1024 pushed through the row distances
+ * (m = 16 / 32 / 64) SEAL the list at a merge point instead, and the next such push merges it in one workgroup of its own
+ * distance launch; every other reader or push form merges a sealed list first.  The export buffer written is the one
+ * current when the merge is launched.  elfihip_reject_flush merges what is pending now (asynchronous); _result,
+ * _state_dev do so themselves. */
 int elfihip_reject_flush(elfihip_reject* h);
 /* vals / rows: k entries each; *count = entries in use.  A NaN distance never enters the state (the reference's argsort
  * would list such rows last, after every finite distance): while fewer than k finite distances have been seen, count is
