@@ -20,6 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libelfihip.so")
 
 OK, ERR_ARG, ERR_HIP, ERR_NOT_PD, ERR_STATE, ERR_NOMEM = range(6)
 
+# canonical cdist metric name -> id of include/elfihip.h
 METRICS = {
     "euclidean": 0,
     "sqeuclidean": 1,
@@ -28,7 +29,36 @@ METRICS = {
     "minkowski": 4,
     "seuclidean": 5,
     "mahalanobis": 6,
+    "canberra": 7,
+    "braycurtis": 8,
+    "cosine": 9,
+    "correlation": 10,
 }
+
+# every accepted name (SciPy's alias table, scipy.spatial.distance._METRICS[...].aka) -> (canonical name, id); looked
+# up in lower case, as SciPy does
+_ALIASES = {
+    "euclidean": ("e", "eu", "euclid"),
+    "sqeuclidean": ("sqe", "sqeuclid"),
+    "cityblock": ("c", "cb", "cblock"),
+    "chebyshev": ("ch", "cheb", "cheby", "chebychev"),
+    "minkowski": ("m", "mi", "pnorm"),
+    "seuclidean": ("s", "se"),
+    "mahalanobis": ("mah", "mahal"),
+    "canberra": (),
+    "braycurtis": (),
+    "cosine": ("cos",),
+    "correlation": ("co",),
+}
+METRIC_NAMES = {alias: (name, METRICS[name]) for name, aka in _ALIASES.items() for alias in (name,) + aka}
+
+
+def resolve_metric(metric):
+    """(canonical name, id) of a cdist metric name or alias, any letter case; ValueError for anything else."""
+    try:
+        return METRIC_NAMES[metric.lower()]
+    except (AttributeError, KeyError):
+        raise ValueError("Unknown Distance Metric: %s" % (metric,))
 
 c_double_p = C.POINTER(C.c_double)
 c_void_pp = C.POINTER(C.c_void_p)

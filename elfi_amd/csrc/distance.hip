@@ -17,11 +17,15 @@
 //     i walks column j at row i -- coalesced by construction, no LDS needed.
 //   * very wide rows (m >= 300): one wavefront per row with a shuffle tree (order
 //     differs from SciPy by a few ulp; documented tolerance).
+//   * canberra, braycurtis, cosine and correlation go through the same forms with
+//     their row sums in Row<METRIC, W> (below): SciPy's order again, so bit-identical
+//     up to m = 299 except weighted cosine / correlation (SciPy's np.dot order).
 // FMA contraction is off in this file: a fused d*d+s would round differently from the
 // reference's separate multiply and add.
 #include "common.hpp"
 #include "tile_stream.hpp"
 #include "internal.hpp"
+#include "np_sum.hpp"
 
 #pragma clang fp contract(off)
 
@@ -109,6 +113,219 @@ struct Op {
   }
 };
 
+// ---- canberra, braycurtis, cosine, correlation ----------------------------------------------------------------------
+// These do not fit Op's one left-to-right accumulator: braycurtis keeps two sums, cosine forms its dot products in SciPy's
+// two lanes (even j, odd j, then the odd last term), correlation first takes the row mean in NumPy's pairwise order.  A
+// kernel hands Row<METRIC, W>::dist its row as accessors -- x(j) (LDS, registers or global), y(j), a(j) -- and Row sums
+// in exactly the order SciPy does, so the unweighted forms (and weighted canberra / braycurtis) are bit-identical to
+// cdist.  Weighted cosine / correlation follow SciPy's Python correlation(u, v, w, centered): wn = w / sum w, means
+// x.wn, dots x.(y wn), 1 - uv / sqrt(uu vv) clipped to [0, 2]; SciPy's np.dot order is its BLAS's (held to 1e-13).
+// What depends on the observed row alone (Obs) is formed once per workgroup inside the kernel, from y and aux.
+template <int METRIC>
+constexpr bool kRowMetric = METRIC >= ELFIHIP_CANBERRA;
+
+struct Obs {
+  double sw;     // weighted cosine / correlation: sum w (the kernels keep wn_j = w_j / sw in place of w_j)
+  double ymu;    // correlation: mean of y (weighted: y.wn)
+  double ynorm;  // unweighted: |y| (correlation: |y - ymu|); weighted: (y - ymu).((y - ymu) wn)
+};
+
+template <int METRIC, bool W>
+struct Row {
+  static constexpr bool kCentered = METRIC == ELFIHIP_CORRELATION;
+  static constexpr bool kNormW = W && (METRIC == ELFIHIP_COSINE || METRIC == ELFIHIP_CORRELATION);
+
+  // the observed row's constants; y(j), w(j) are the raw observed row and weights
+  template <class YF, class WF>
+  __device__ static __forceinline__ Obs obs(YF y, WF w, int m) {
+    Obs o{1.0, 0.0, 0.0};
+    if constexpr (METRIC == ELFIHIP_COSINE || METRIC == ELFIHIP_CORRELATION) {
+      if constexpr (W) {
+        o.sw = np_pairwise_bounded<2>(w, 0, m);   // w.sum()
+        if constexpr (kCentered) {
+          double mu = 0.0;
+          for (int j = 0; j < m; ++j) mu += y(j) * (w(j) / o.sw);
+          o.ymu = mu;
+        }
+        double vv = 0.0;
+        for (int j = 0; j < m; ++j) {
+          const double yc = y(j) - o.ymu;
+          vv += yc * (yc * (w(j) / o.sw));
+        }
+        o.ynorm = vv;
+      } else {
+        if constexpr (kCentered) o.ymu = np_pairwise_bounded<2>(y, 0, m) / (double)m;
+        auto cy = [&](int j) { return kCentered ? y(j) - o.ymu : y(j); };
+        o.ynorm = sqrt(dot2(cy, cy, m));
+      }
+    }
+    return o;
+  }
+
+  // SciPy's dot_product: two lanes (even and odd j), added, then the last term of an odd length
+  template <class UF, class VF>
+  __device__ static __forceinline__ double dot2(UF u, VF v, int m) {
+    double s0 = 0.0, s1 = 0.0;
+    int j = 0;
+#pragma unroll 4
+    for (; j + 1 < m; j += 2) {
+      s0 += u(j) * v(j);
+      s1 += u(j + 1) * v(j + 1);
+    }
+    double s = s0 + s1;
+    if (m & 1) s += u(m - 1) * v(m - 1);
+    return s;
+  }
+
+  // x(j), y(j) the row and the observed row, a(j) the weight the kernel keeps (w_j, or wn_j for cosine / correlation)
+  template <class XF, class YF, class AF>
+  __device__ static __forceinline__ double dist(XF x, YF y, AF a, int m, const Obs& o) {
+    if constexpr (METRIC == ELFIHIP_CANBERRA) {
+      double s = 0.0;
+#pragma unroll 4
+      for (int j = 0; j < m; ++j) {
+        const double xj = x(j), yj = y(j);
+        double num = fabs(xj - yj);
+        const double den = fabs(xj) + fabs(yj);
+        if constexpr (W) num = a(j) * num;
+        s += num / (den + (den == 0.0 ? 1.0 : 0.0));
+      }
+      return s;
+    } else if constexpr (METRIC == ELFIHIP_BRAYCURTIS) {
+      double sn = 0.0, sd = 0.0;
+#pragma unroll 4
+      for (int j = 0; j < m; ++j) {
+        const double xj = x(j), yj = y(j);
+        double dn = fabs(xj - yj), dd = fabs(xj + yj);
+        if constexpr (W) {
+          dn = a(j) * dn;
+          dd = a(j) * dd;
+        }
+        sn += dn;
+        sd += dd;
+      }
+      return sn / sd;
+    } else if constexpr (W) {   // weighted cosine / correlation
+      double xmu = 0.0;
+      if constexpr (kCentered) {
+#pragma unroll 4
+        for (int j = 0; j < m; ++j) xmu += x(j) * a(j);
+      }
+      double uv = 0.0, uu = 0.0;
+#pragma unroll 4
+      for (int j = 0; j < m; ++j) {
+        const double xc = kCentered ? x(j) - xmu : x(j);
+        const double yc = kCentered ? y(j) - o.ymu : y(j);
+        uv += xc * (yc * a(j));
+        uu += xc * (xc * a(j));
+      }
+      return clip02(1.0 - uv / sqrt(uu * o.ynorm));
+    } else {                    // cosine / correlation
+      double xmu = 0.0;
+      if constexpr (kCentered) xmu = np_pairwise_bounded<2>(x, 0, m) / (double)m;
+      auto cx = [&](int j) { return kCentered ? x(j) - xmu : x(j); };
+      auto cy = [&](int j) { return kCentered ? y(j) - o.ymu : y(j); };
+      double s0 = 0.0, s1 = 0.0, q0 = 0.0, q1 = 0.0;
+      int j = 0;
+#pragma unroll 4
+      for (; j + 1 < m; j += 2) {
+        const double x0 = cx(j), x1 = cx(j + 1);
+        s0 += x0 * cy(j);
+        s1 += x1 * cy(j + 1);
+        q0 += x0 * x0;
+        q1 += x1 * x1;
+      }
+      double s = s0 + s1, q = q0 + q1;
+      if (m & 1) {
+        const double xl = cx(m - 1);
+        s += xl * cy(m - 1);
+        q += xl * xl;
+      }
+      return cos_finish(s, sqrt(q), o.ynorm);
+    }
+  }
+
+  // SciPy's cosine_distance_double: clip the cosine to [-1, 1], then 1 - c (NaN stays NaN)
+  __device__ static __forceinline__ double cos_finish(double dot, double nx, double ny) {
+    double c = dot / (nx * ny);
+    if (fabs(c) > 1.0) c = copysign(1.0, c);
+    return 1.0 - c;
+  }
+  // np.clip(d, 0, 2), NaN stays NaN
+  __device__ static __forceinline__ double clip02(double d) { return d < 0.0 ? 0.0 : (d > 2.0 ? 2.0 : d); }
+
+  // wide rows (one wavefront per row, lane-strided partial sums, butterfly): x, y, w raw pointers
+  __device__ static __forceinline__ double wide(const double* __restrict__ x, const double* __restrict__ y,
+                                                const double* __restrict__ w, int m, int lane, const Obs& o) {
+    auto wsum = [](double v) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      return v;
+    };
+    auto wn = [&](int j) { return kNormW ? w[j] / o.sw : (W ? w[j] : 1.0); };
+    if constexpr (METRIC == ELFIHIP_CANBERRA || METRIC == ELFIHIP_BRAYCURTIS) {
+      double s0 = 0.0, s1 = 0.0;
+      for (int j = lane; j < m; j += 64) {
+        const double xj = x[j], yj = y[j];
+        if constexpr (METRIC == ELFIHIP_CANBERRA) {
+          double num = fabs(xj - yj);
+          const double den = fabs(xj) + fabs(yj);
+          if constexpr (W) num = w[j] * num;
+          s0 += num / (den + (den == 0.0 ? 1.0 : 0.0));
+        } else {
+          double dn = fabs(xj - yj), dd = fabs(xj + yj);
+          if constexpr (W) {
+            dn = w[j] * dn;
+            dd = w[j] * dd;
+          }
+          s0 += dn;
+          s1 += dd;
+        }
+      }
+      s0 = wsum(s0);
+      if constexpr (METRIC == ELFIHIP_CANBERRA) return s0;
+      return s0 / wsum(s1);
+    } else {
+      double xmu = 0.0;
+      if constexpr (kCentered) {
+        for (int j = lane; j < m; j += 64) xmu += W ? x[j] * wn(j) : x[j];
+        xmu = wsum(xmu);
+        if constexpr (!W) xmu = xmu / (double)m;
+      }
+      double uv = 0.0, uu = 0.0;
+      for (int j = lane; j < m; j += 64) {
+        const double xc = x[j] - xmu, yc = y[j] - o.ymu;
+        if constexpr (W) {
+          uv += xc * (yc * wn(j));
+          uu += xc * (xc * wn(j));
+        } else {
+          uv += xc * yc;
+          uu += xc * xc;
+        }
+      }
+      uv = wsum(uv);
+      uu = wsum(uu);
+      if constexpr (W) return clip02(1.0 - uv / sqrt(uu * o.ynorm));
+      return cos_finish(uv, sqrt(uu), o.ynorm);
+    }
+  }
+};
+
+// the weight a kernel keeps for metric METRIC: w_j as given, wn_j = w_j / sum w for weighted cosine / correlation
+template <int METRIC, bool W>
+__device__ __forceinline__ double kept_aux(double w, const Obs& o) {
+  if constexpr (kRowMetric<METRIC> && Row<METRIC, W>::kNormW) return w / o.sw;
+  return w;
+}
+
+// the observed row's constants from global y / aux (every lane forms the same values; uniform loads)
+template <int METRIC, bool W>
+__device__ __forceinline__ Obs obs_of(const double* __restrict__ y, const double* __restrict__ aux, int m) {
+  if constexpr (kRowMetric<METRIC>)
+    return Row<METRIC, W>::obs([&](int j) { return y[j]; }, [&](int j) { return W ? aux[j] : 1.0; }, m);
+  return Obs{1.0, 0.0, 0.0};
+}
+
 // Pipelined form of dist_rows_kernel: requires vec2 and T * U >= T * m / 2 (whole tile per batch).
 template <int METRIC, bool W, int U>
 __global__ __launch_bounds__(256) void dist_rows_pipe_kernel(RowArgs A) {
@@ -118,9 +335,10 @@ __global__ __launch_bounds__(256) void dist_rows_pipe_kernel(RowArgs A) {
   const int R = A.R;
   double* ys = tile + (size_t)R * A.mp;
   double* as = ys + m;
+  const Obs o = obs_of<METRIC, W>(A.y, A.aux, m);
   for (int j = tid; j < m; j += T) {
     ys[j] = A.y[j];
-    if constexpr (W) as[j] = A.aux[j];
+    if constexpr (W) as[j] = kept_aux<METRIC, W>(A.aux[j], o);
   }
   const int64_t ntiles = (A.n + R - 1) / R;
   const double thr = A.F.thr ? *A.F.thr : 0.0;   // fused selection: the sampler state's current k-th best distance
@@ -138,10 +356,15 @@ __global__ __launch_bounds__(256) void dist_rows_pipe_kernel(RowArgs A) {
     double dist = 0.0;
     if (tid < rows) {
       const double* row = tile + (size_t)tid * A.mp;
-      double s = Op<METRIC, W>::init();
+      if constexpr (kRowMetric<METRIC>) {
+        dist = Row<METRIC, W>::dist([&](int j) { return row[j]; }, [&](int j) { return ys[j]; },
+                                    [&](int j) { return as[j]; }, m, o);
+      } else {
+        double s = Op<METRIC, W>::init();
 #pragma unroll 8
-      for (int j = 0; j < m; ++j) s = Op<METRIC, W>::step(s, row[j], ys[j], W ? as[j] : 1.0, A.p);
-      dist = Op<METRIC, W>::finish(s, A.inv_p);
+        for (int j = 0; j < m; ++j) s = Op<METRIC, W>::step(s, row[j], ys[j], W ? as[j] : 1.0, A.p);
+        dist = Op<METRIC, W>::finish(s, A.inv_p);
+      }
       A.out[row0 + tid] = dist;
     }
     if (A.F.thr) reject_offer(A.F, tid < rows && dist < thr, dist, A.F.row_base + row0 + tid);
@@ -181,9 +404,10 @@ __global__ __launch_bounds__(64) void dist_rows_dma_kernel(RowArgs A) {
   double* ys = lds + (size_t)D * SLOT;
   double* as = ys + MM;
   const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
+  const Obs o = obs_of<METRIC, W>(A.y, A.aux, MM);
   if (lane < MM) {
     ys[lane] = A.y[lane];
-    if constexpr (W) as[lane] = A.aux[lane];
+    if constexpr (W) as[lane] = kept_aux<METRIC, W>(A.aux[lane], o);
   }
   const int64_t nslots = (A.n + ROWS - 1) / ROWS;
   const int64_t stride = MERGE ? gridDim.x - 1 : gridDim.x;
@@ -228,17 +452,22 @@ __global__ __launch_bounds__(64) void dist_rows_dma_kernel(RowArgs A) {
     if (ROWS == 64 || lane < ROWS) {
       const double* row = ring + (size_t)cur * SLOT + (size_t)lane * MM;
       const int key = dma_swizzle_key<MM>(lane);
-      double s = Op<METRIC, W>::init();
+      if constexpr (kRowMetric<METRIC>) {
+        dist = Row<METRIC, W>::dist([&](int j) { return row[2 * ((j >> 1) ^ key) + (j & 1)]; },
+                                    [&](int j) { return ys[j]; }, [&](int j) { return as[j]; }, MM, o);
+      } else {
+        double s = Op<METRIC, W>::init();
 #pragma unroll
-      for (int c = 0; c < H; ++c) {
-        const double2 v = *reinterpret_cast<const double2*>(row + 2 * (c ^ key));
-        const double2 yv = *reinterpret_cast<const double2*>(ys + 2 * c);
-        double2 av = make_double2(1.0, 1.0);
-        if constexpr (W) av = *reinterpret_cast<const double2*>(as + 2 * c);
-        s = Op<METRIC, W>::step(s, v.x, yv.x, av.x, A.p);
-        s = Op<METRIC, W>::step(s, v.y, yv.y, av.y, A.p);
+        for (int c = 0; c < H; ++c) {
+          const double2 v = *reinterpret_cast<const double2*>(row + 2 * (c ^ key));
+          const double2 yv = *reinterpret_cast<const double2*>(ys + 2 * c);
+          double2 av = make_double2(1.0, 1.0);
+          if constexpr (W) av = *reinterpret_cast<const double2*>(as + 2 * c);
+          s = Op<METRIC, W>::step(s, v.x, yv.x, av.x, A.p);
+          s = Op<METRIC, W>::step(s, v.y, yv.y, av.y, A.p);
+        }
+        dist = Op<METRIC, W>::finish(s, A.inv_p);
       }
-      dist = Op<METRIC, W>::finish(s, A.inv_p);
       if (mine) A.out[row0 + lane] = dist;
     }
     if (A.F.thr) reject_offer(A.F, mine && dist < thr, dist, A.F.row_base + row0 + lane);
@@ -313,9 +542,10 @@ __global__ void dist_rows_kernel(RowArgs A) {
   double* tile = lds;
   double* ys = tile + (size_t)T * A.mp;
   double* as = ys + m;
+  const Obs o = obs_of<METRIC, W>(A.y, A.aux, m);
   for (int j = tid; j < m; j += T) {
     ys[j] = A.y[j];
-    if constexpr (W) as[j] = A.aux[j];
+    if constexpr (W) as[j] = kept_aux<METRIC, W>(A.aux[j], o);
   }
   const int64_t ntiles = (A.n + T - 1) / T;
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -326,10 +556,15 @@ __global__ void dist_rows_kernel(RowArgs A) {
     __syncthreads();
     if (tid < rows) {
       const double* row = tile + (size_t)tid * A.mp;
-      double s = Op<METRIC, W>::init();
+      if constexpr (kRowMetric<METRIC>) {
+        A.out[row0 + tid] = Row<METRIC, W>::dist([&](int j) { return row[j]; }, [&](int j) { return ys[j]; },
+                                                 [&](int j) { return as[j]; }, m, o);
+      } else {
+        double s = Op<METRIC, W>::init();
 #pragma unroll 4
-      for (int j = 0; j < m; ++j) s = Op<METRIC, W>::step(s, row[j], ys[j], W ? as[j] : 1.0, A.p);
-      A.out[row0 + tid] = Op<METRIC, W>::finish(s, A.inv_p);
+        for (int j = 0; j < m; ++j) s = Op<METRIC, W>::step(s, row[j], ys[j], W ? as[j] : 1.0, A.p);
+        A.out[row0 + tid] = Op<METRIC, W>::finish(s, A.inv_p);
+      }
     }
   }
 }
@@ -495,14 +730,23 @@ __global__ void dist_cols_kernel(ColArgs A) {
   const int m = A.m;
   double* ys = lds;
   double* as = ys + m;
+  const Obs o = obs_of<METRIC, W>(A.y, A.aux, m);
   for (int j = threadIdx.x; j < m; j += blockDim.x) {
     ys[j] = A.y[j];
-    if constexpr (W) as[j] = A.aux[j];
+    if constexpr (W) as[j] = kept_aux<METRIC, W>(A.aux[j], o);
   }
   __syncthreads();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (A.vec2) {
+  if constexpr (kRowMetric<METRIC>) {
+    // lane i owns row i (8-byte loads, consecutive lanes on consecutive rows); correlation reads its columns twice, for
+    // the mean and for the dot products (the second read is served by the caches for the rows a wave has in flight)
+    for (int64_t i = gid; i < A.n; i += stride) {
+      const double* __restrict__ c = A.C + i;
+      A.out[i] = Row<METRIC, W>::dist([&](int j) { return c[(int64_t)j * A.ldc]; }, [&](int j) { return ys[j]; },
+                                      [&](int j) { return as[j]; }, m, o);
+    }
+  } else if (A.vec2) {
     const int64_t npair = A.n >> 1;
     for (int64_t i2 = gid; i2 < npair; i2 += stride) {
       double s0 = Op<METRIC, W>::init(), s1 = s0;
@@ -567,6 +811,14 @@ __global__ void dist_rows_wide_kernel(RowArgs A) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  if constexpr (kRowMetric<METRIC>) {
+    const Obs o = obs_of<METRIC, W>(A.y, A.aux, A.m);
+    for (int64_t r = wave; r < A.n; r += nwaves) {
+      const double d = Row<METRIC, W>::wide(A.X + r * A.ldx, A.y, A.aux, A.m, lane, o);
+      if (lane == 0) A.out[r] = d;
+    }
+    return;
+  }
   for (int64_t r = wave; r < A.n; r += nwaves) {
     const double* __restrict__ x = A.X + r * A.ldx;
     double s = Op<METRIC, W>::init();
@@ -633,10 +885,11 @@ template <int METRIC, bool W, int M, int U>
 __global__ __launch_bounds__(256) void dist_rows_narrow_kernel(RowArgs A) {
   const int tid = threadIdx.x;
   double yv[M], av[M];
+  const Obs o = obs_of<METRIC, W>(A.y, A.aux, M);
 #pragma unroll
   for (int j = 0; j < M; ++j) {
     yv[j] = A.y[j];
-    av[j] = W ? A.aux[j] : 1.0;
+    av[j] = W ? kept_aux<METRIC, W>(A.aux[j], o) : 1.0;
   }
   const double thr = A.F.thr ? *A.F.thr : 0.0;   // fused selection: the sampler state's current k-th best distance
   const int64_t per = 256 * U;
@@ -650,10 +903,16 @@ __global__ __launch_bounds__(256) void dist_rows_narrow_kernel(RowArgs A) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t r = base + u * 256 + tid;
-      double s = Op<METRIC, W>::init();
+      double dist;
+      if constexpr (kRowMetric<METRIC>) {
+        dist = Row<METRIC, W>::dist([&](int j) { return x[u][j]; }, [&](int j) { return yv[j]; },
+                                    [&](int j) { return av[j]; }, M, o);
+      } else {
+        double s = Op<METRIC, W>::init();
 #pragma unroll
-      for (int j = 0; j < M; ++j) s = Op<METRIC, W>::step(s, x[u][j], yv[j], av[j], A.p);
-      const double dist = Op<METRIC, W>::finish(s, A.inv_p);
+        for (int j = 0; j < M; ++j) s = Op<METRIC, W>::step(s, x[u][j], yv[j], av[j], A.p);
+        dist = Op<METRIC, W>::finish(s, A.inv_p);
+      }
       if (r < A.n) A.out[r] = dist;
       if (A.F.thr) reject_offer(A.F, r < A.n && dist < thr, dist, A.F.row_base + r);
     }
@@ -773,6 +1032,16 @@ static int pipe_unroll(int m, bool light) {
   return m <= 32 ? 4 : (m <= 64 ? 8 : 16);
 }
 
+// Where the LDS-DMA form is used for the Row metrics: where it was measured faster than the register-staged pipeline
+// (scripts/time_metrics.py, profiles/distance_metrics.md).  Canberra's division per element makes it VALU-bound in the DMA form's
+// one-wave workgroups except at 32 summaries (2 10^6 x 16: 55.0 us against 49.3; 10^6 x 32: 54.0 against 64.2;
+// 1.25 10^6 x 64: 175 against 152).  At 64 summaries the slots hold 32 rows -- half the lanes sum rows -- and weighted
+// correlation (three sums per element) loses there too (166 against 151 us).  Everything else streams faster by DMA.
+template <int METRIC, bool W>
+constexpr bool kDma16 = METRIC != ELFIHIP_CANBERRA;
+template <int METRIC, bool W>
+constexpr bool kDma64 = !(METRIC == ELFIHIP_CANBERRA || (METRIC == ELFIHIP_CORRELATION && W));
+
 template <int METRIC, bool W>
 static int launch_rows(elfihip_ctx* ctx, RowArgs A, bool* filtered, bool* merged) {
   if (A.m > kMaxTileM) {
@@ -797,7 +1066,7 @@ static int launch_rows(elfihip_ctx* ctx, RowArgs A, bool* filtered, bool* merged
   const int64_t ntiles = (A.n + T - 1) / T;
   const int g = grid_for(ctx, ntiles, lds, T);
   if (A.vec2 && ctx->dist_form != 1 && METRIC != ELFIHIP_MINKOWSKI && METRIC != ELFIHIP_SEUCLIDEAN &&
-      (A.m == 16 || A.m == 32 || A.m == 64) && A.ldx <= (1 << 21)) {
+      ((A.m == 16 && kDma16<METRIC, W>) || A.m == 32 || (A.m == 64 && kDma64<METRIC, W>)) && A.ldx <= (1 << 21)) {
     // LDS-DMA form: one-wave workgroups, each with a ring of two 16 KiB slots (64 rows of 32 summaries, 32 rows of 64; four
     // 8 KiB slots of 64 rows at 16 summaries), four workgroups per CU.  Measured on 10^6 x 32 / 5 10^5 x 64, plain | weighted
     // (scripts/native/glds_probe.hip, profiles/r05_glds_probe.md): ring of 2 x 4 per CU 41.9 | 42.0 and 40.7 | 41.1 us; ring
@@ -816,18 +1085,20 @@ static int launch_rows(elfihip_ctx* ctx, RowArgs A, bool* filtered, bool* merged
     if (gd < 1) gd = 1;
     const dim3 grid((unsigned)gd), block(64);
     if (merge) {
-      if (A.m == 16)
-        hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 16, 64, 4, true>), grid, block, ldsd, ctx->stream, A);
-      else if (A.m == 32)
+      if (A.m == 16) {
+        if constexpr (kDma16<METRIC, W>)
+          hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 16, 64, 4, true>), grid, block, ldsd, ctx->stream, A);
+      } else if (A.m == 32)
         hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 32, 64, 2, true>), grid, block, ldsd, ctx->stream, A);
-      else
+      else if constexpr (kDma64<METRIC, W>)
         hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 64, 32, 2, true>), grid, block, ldsd, ctx->stream, A);
       if (merged) *merged = true;
     } else if (A.m == 16) {
-      hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 16, 64, 4, false>), grid, block, ldsd, ctx->stream, A);
+      if constexpr (kDma16<METRIC, W>)
+        hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 16, 64, 4, false>), grid, block, ldsd, ctx->stream, A);
     } else if (A.m == 32) {
       hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 32, 64, 2, false>), grid, block, ldsd, ctx->stream, A);
-    } else {
+    } else if constexpr (kDma64<METRIC, W>) {
       hipLaunchKernelGGL((dist_rows_dma_kernel<METRIC, W, 64, 32, 2, false>), grid, block, ldsd, ctx->stream, A);
     }
     if (filtered) *filtered = A.F.thr != nullptr;   // this form offers its candidates itself, too
@@ -865,7 +1136,7 @@ static int launch_rows(elfihip_ctx* ctx, RowArgs A, bool* filtered, bool* merged
 template <int METRIC, bool W>
 static int launch_cols(elfihip_ctx* ctx, ColArgs A) {
   const int T = 256;
-  int64_t work = A.vec2 ? ((A.n + 1) >> 1) : A.n;
+  int64_t work = (A.vec2 && !kRowMetric<METRIC>) ? ((A.n + 1) >> 1) : A.n;   // (the Row metrics take one row per lane)
   int64_t g = (work + T - 1) / T;
   int64_t cap = (int64_t)ctx->cu_count * 8;
   if (g > cap) g = cap;
@@ -901,6 +1172,12 @@ static int canonical_metric(elfihip_ctx* ctx, int metric, double p, const double
       return ELFIHIP_OK;
     case ELFIHIP_MAHALANOBIS:
       if (!aux) return fail(ctx, ELFIHIP_ERR_ARG, "mahalanobis needs VI");
+      *out_metric = metric;
+      return ELFIHIP_OK;
+    case ELFIHIP_CANBERRA:
+    case ELFIHIP_BRAYCURTIS:
+    case ELFIHIP_COSINE:
+    case ELFIHIP_CORRELATION:
       *out_metric = metric;
       return ELFIHIP_OK;
     default:
@@ -1176,6 +1453,10 @@ int dist_rows_dev_impl(elfihip_ctx* ctx, int metric, const double* dX, int64_t n
     ELFIHIP_DISPATCH_ROWS(ELFIHIP_CITYBLOCK)
     ELFIHIP_DISPATCH_ROWS(ELFIHIP_CHEBYSHEV)
     ELFIHIP_DISPATCH_ROWS(ELFIHIP_MINKOWSKI)
+    ELFIHIP_DISPATCH_ROWS(ELFIHIP_CANBERRA)
+    ELFIHIP_DISPATCH_ROWS(ELFIHIP_BRAYCURTIS)
+    ELFIHIP_DISPATCH_ROWS(ELFIHIP_COSINE)
+    ELFIHIP_DISPATCH_ROWS(ELFIHIP_CORRELATION)
     case ELFIHIP_SEUCLIDEAN:
       return launch_rows<ELFIHIP_SEUCLIDEAN, true>(ctx, A, filtered, merged);
   }
@@ -1214,6 +1495,10 @@ static int dist_cols_dev_impl(elfihip_ctx* ctx, int metric, const double* dC, in
     ELFIHIP_DISPATCH_COLS(ELFIHIP_CITYBLOCK)
     ELFIHIP_DISPATCH_COLS(ELFIHIP_CHEBYSHEV)
     ELFIHIP_DISPATCH_COLS(ELFIHIP_MINKOWSKI)
+    ELFIHIP_DISPATCH_COLS(ELFIHIP_CANBERRA)
+    ELFIHIP_DISPATCH_COLS(ELFIHIP_BRAYCURTIS)
+    ELFIHIP_DISPATCH_COLS(ELFIHIP_COSINE)
+    ELFIHIP_DISPATCH_COLS(ELFIHIP_CORRELATION)
     case ELFIHIP_SEUCLIDEAN:
       return launch_cols<ELFIHIP_SEUCLIDEAN, true>(ctx, A);
   }

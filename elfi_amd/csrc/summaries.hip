@@ -19,6 +19,7 @@
 #include "common.hpp"
 #include <cstdlib>
 
+#include "np_sum.hpp"
 #include "philox.hpp"
 #include "tile_stream.hpp"
 
@@ -27,32 +28,6 @@
 namespace elfihip {
 
 enum { SUM_MEAN = 0, SUM_VAR = 1, SUM_AUTOCOV = 2, SUM_MA2 = 3 };
-
-// NumPy's pairwise_sum over a[0..n): f(i) yields element i.
-template <class F>
-__device__ double np_pairwise(F f, int lo, int n) {
-  if (n < 8) {
-    double r = 0.0;
-    for (int i = 0; i < n; ++i) r += f(lo + i);
-    return r;
-  }
-  if (n <= 128) {
-    double r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = f(lo + j);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r[j] += f(lo + i + j);
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += f(lo + i);
-    return res;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return np_pairwise(f, lo, n2) + np_pairwise(f, lo + n2, n - n2);
-}
 
 // The same sum for n <= 128 computed by EIGHT lanes: NumPy's eight interleaved accumulators are
 // independent chains (r[j] takes elements j, j+8, ...), so lane j of an aligned 8-lane group owns

@@ -31,10 +31,7 @@ def _as_f64(a):
 
 
 def _metric_id(metric):
-    try:
-        return _lib.METRICS[metric]
-    except KeyError:
-        raise ValueError("Unknown Distance Metric: %s" % metric)
+    return _lib.resolve_metric(metric)[1]
 
 
 def _metric_aux(metric, m, p, w, V, VI):
@@ -89,7 +86,7 @@ def cdist_rows(X, y, metric='euclidean', p=2.0, w=None, V=None, VI=None, ctx=Non
     n, m = X.shape
     if m < 1:
         raise ValueError('XA must have at least one column')
-    mid = _metric_id(metric)
+    metric, mid = _lib.resolve_metric(metric)
     aux, p = _metric_aux(metric, m, p, w, V, VI)
     # row-major with unit inner stride is passed as is (ldx = row pitch); anything else is copied
     if X.dtype != np.float64 or X.strides[1] != 8 or X.strides[0] % 8 or X.strides[0] < 8 * m:
@@ -122,7 +119,7 @@ def cdist_cols(cols, y, metric='euclidean', p=2.0, w=None, V=None, ctx=None):
     if y.shape[0] != m:
         raise ValueError('XA and XB must have the same number of columns '
                          '(i.e. feature dimension.)')
-    mid = _metric_id(metric)
+    metric, mid = _lib.resolve_metric(metric)
     if metric == 'mahalanobis':
         raise ValueError('mahalanobis needs the stacked (row-major) form')
     aux, p = _metric_aux(metric, m, p, w, V, None)
@@ -246,7 +243,7 @@ class HipDistance:
     `elfi.Distance(elfi_amd.HipDistance('euclidean', w=...), S1, S2)`."""
 
     def __init__(self, metric='euclidean', p=2.0, w=None, V=None, VI=None, device=-1):
-        _metric_id(metric)
+        metric = _lib.resolve_metric(metric)[0]   # SciPy's aliases, any letter case; kept by canonical name
         if metric == 'seuclidean' and V is None:
             raise ValueError('Parameter V must be specified for distance=seuclidean.')
         if metric == 'mahalanobis' and VI is None:

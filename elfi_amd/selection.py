@@ -89,9 +89,7 @@ class RunningBest:
         self.ctx = ctx or _lib.default_context()
         self.lib = self.ctx.lib
         self.k = int(k)
-        if metric not in _lib.METRICS:
-            raise ValueError('unknown metric %r' % (metric,))
-        self.metric = _lib.METRICS[metric]
+        self.metric = _lib.resolve_metric(metric)[1]
         self.aux = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
         self.p = float(p)
         h = C.c_void_p()

@@ -51,7 +51,11 @@ enum {
   ELFIHIP_CHEBYSHEV = 3,   /* max_j |x_j-y_j|   (w ignored unless 0: SciPy drops w_j==0 columns) */
   ELFIHIP_MINKOWSKI = 4,   /* (sum w_j |x_j-y_j|^p)^(1/p)          */
   ELFIHIP_SEUCLIDEAN = 5,  /* sqrt(sum (x_j-y_j)^2 / V_j), aux = V */
-  ELFIHIP_MAHALANOBIS = 6  /* sqrt(d' VI d), aux = VI (m x m row-major) */
+  ELFIHIP_MAHALANOBIS = 6, /* sqrt(d' VI d), aux = VI (m x m row-major) */
+  ELFIHIP_CANBERRA = 7,    /* sum w_j |x_j-y_j| / (|x_j|+|y_j|)   (a 0/0 term counts 0) */
+  ELFIHIP_BRAYCURTIS = 8,  /* sum w_j |x_j-y_j| / sum w_j |x_j+y_j| */
+  ELFIHIP_COSINE = 9,      /* 1 - x.y / (|x| |y|)   (w: weighted dots with w / sum w) */
+  ELFIHIP_CORRELATION = 10 /* cosine of x - mean(x) and y - mean(y)  (w: weighted means and dots) */
 };
 
 typedef struct elfihip_ctx elfihip_ctx;
@@ -91,8 +95,14 @@ int elfihip_timer_stop(elfihip_ctx* ctx, float* elapsed_ms); /* synchronises on 
  * elfi.Distance (elfi/model/elfi_model.py:1037) and AdaptiveDistance (:1084).
  * out has n doubles -- the (n,1)->(n,) squeeze of utils.py:50-51 is built in.
  *
- * aux: w (m) for EUCLIDEAN/SQEUCLIDEAN/CITYBLOCK/MINKOWSKI/CHEBYSHEV (NULL = unweighted),
- *      V (m) for SEUCLIDEAN, VI (m*m, row-major) for MAHALANOBIS.  p only for MINKOWSKI.
+ * aux: w (m) for EUCLIDEAN/SQEUCLIDEAN/CITYBLOCK/MINKOWSKI/CHEBYSHEV/CANBERRA/BRAYCURTIS/COSINE/CORRELATION
+ *      (NULL = unweighted), V (m) for SEUCLIDEAN, VI (m*m, row-major) for MAHALANOBIS.  p only for MINKOWSKI.
+ * Ids 0..10 are the canonical metrics.  The Python layer (elfi_amd/_lib.py: METRIC_NAMES) also takes SciPy's aliases,
+ * in any letter case: e eu euclid | sqe sqeuclid | c cb cblock | ch cheb cheby chebychev | m mi pnorm | s se |
+ * mah mahal | cos | co (canberra and braycurtis have none).
+ * canberra, braycurtis, cosine and correlation sum in SciPy's order (cosine: SciPy's two-lane dot products; correlation:
+ * the row mean in NumPy's pairwise order) and match cdist bit for bit up to m = 299, except weighted cosine / correlation
+ * (1e-13: SciPy's np.dot order is its BLAS's); wider rows are summed by a butterfly (1e-14).
  */
 
 /* X row-major (n, m) with leading dimension ldx >= m (doubles). */
