@@ -53,9 +53,7 @@ struct elfihip_gp {
   double* W11 = nullptr;    // 2 x (NB, NB): inverse of the diagonal block being eliminated (lower), alternating
   double* alpha = nullptr;  // (cap) K^-1 y
   double* red = nullptr;    // small reduction scratch
-  int* info = nullptr;      // device: 1-based index of the first non-positive pivot, 0 if none; from word 4 on the
-  int ov_flags_off = 0;     // first word of the overlapped sweep's counters in `info`
-  int ninfo = 0;            // arrival counters of the fused sweep's steps (four words each); ninfo words in all
+  int* info = nullptr;      // device, one word: 1-based index of the first non-positive pivot, 0 if none
   double* h_fit = nullptr;  // pinned, device-visible: sum log L_ii, z'z and the pivot report of the latest rebuild;
                             // words 15 / 14: tickets of the latest rebuild / hyper-gradient (host_wait_ticket)
   unsigned long long fit_ticket = 0, hyper_ticket = 0;
@@ -77,7 +75,6 @@ struct elfihip_gp {
   const void* sched_heads = nullptr;
   std::vector<int> sched_step_off, sched_step_nwg;   // per step: first offset entry, workgroups with work
   int sched_nb = 0, sched_nwg = 0;
-  bool sched_far_first = false;   // a workgroup's units by descending column (the chained form of the step launch)
   // per-phase device timing (elfihip_gp_profile): HIP events around the phases of a fit / prediction / gradient call
   // while enabled; sums in milliseconds and call counts per phase (indices: ELFIHIP_PHASE_* in include/elfihip.h)
   bool profile = false;

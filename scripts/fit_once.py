@@ -1,5 +1,5 @@
 """Developer tool: `reps` GP rebuilds with one sweep schedule (for rocprofv3 runs).
-usage: python scripts/fit_once.py n d schedule [reps] [group]"""
+usage: python scripts/fit_once.py n d schedule(0, 1, 2) [reps] [group]"""
 import os
 import sys
 import time

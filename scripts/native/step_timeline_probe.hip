@@ -20,7 +20,7 @@ int main(int argc, char** argv) {
   for (int i = 0; i < n; ++i) y[i] = std::sin(X[(size_t)i * d]) + 0.1 * U(rng);
   CKE(elfihip_gp_set_hyper(gp, 1.0, 1.5, 0.0, 0.1));
   CKE(elfihip_gp_set_data(gp, X.data(), y.data(), n));
-  CKE(elfihip_gp_set_schedule(gp, argc > 4 ? atoi(argv[4]) : 3, 0));   // 3: the chained step launch (the stamps' subject)
+  CKE(elfihip_gp_set_schedule(gp, 2, 0));   // the fused steps: step_kernel is the stamps' subject
   (void)hipMemcpyToSymbol(HIP_SYMBOL(elfihip::g_step_stamp_k), &step, sizeof(int));
   double lml;
   for (int rep = 0; rep < 5; ++rep) CKE(elfihip_gp_factorize(gp, &lml));
@@ -36,12 +36,8 @@ int main(int argc, char** argv) {
     printf(" %7lld %7lld %7lld   (%zu)", v.front(), v[v.size() / 2], v.back(), v.size());
   };
   printf("n %d d %d step %d (log marginal %.6f); ticks of s_memtime since the workgroup's own start: min median max (workgroups)\n", n, d, step, lml);
-  printf("diagonal-block workgroup: tile arrived %lld  block done %lld\n", st[1] - st[0], st[2] - st[0]);
-  printf("lead workgroups 1-8:\n  strip piece solved, arrived"); col(1, 1, 9);
-  printf("\n  strip complete seen        "); col(2, 1, 9); printf("\n  tile pieces done, arrived  "); col(3, 1, 9);
-  printf("\n  waits for the panel        "); col(4, 1, 9); printf("\n  panel seen                 "); col(5, 1, 9); printf("\n  end                        "); col(6, 1, 9);
-  printf("\nother workgroups:\n  panel pieces solved, arrived"); col(1, 9, nwg);
-  printf("\n  waits for the panel        "); col(4, 9, nwg); printf("\n  panel seen                 "); col(5, 9, nwg); printf("\n  end                        "); col(6, 9, nwg);
+  printf("diagonal-block workgroup: block done %lld\n", st[2] - st[0]);
+  printf("update workgroups:\n  end                        "); col(6, 1, nwg);
   printf("\n");
   elfihip_gp_free(gp); elfihip_ctx_destroy(ctx);
   return 0;
