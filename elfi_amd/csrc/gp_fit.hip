@@ -197,13 +197,6 @@ typedef double v2d_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) v2d_t ldouble2;
 typedef __attribute__((address_space(1))) v2d_t gdouble2;
 
-#ifdef ELFIHIP_POTF2_STAMP   // developer probe (scripts/native/potf2_probe.hip): cycle stamps per wave, panel and phase
-__device__ long long g_potf2_stamp[16 * 8 * 8];
-#define STAMP(p, slot) do { if ((threadIdx.x & 63) == 0) g_potf2_stamp[(R * 8 + (p)) * 8 + (slot)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define STAMP(p, slot) do { } while (0)
-#endif
-
 template <int NT>
 __device__ __forceinline__ void potf2_tiles_body(double* Akk_, int64_t lda, double* Wkk_, int64_t ldw, double* W11_, int* info,
                                                  int kblock, double* sm) {
@@ -225,9 +218,6 @@ __device__ __forceinline__ void potf2_tiles_body(double* Akk_, int64_t lda, doub
   gdouble* Wkk = (gdouble*)Wkk_;
   gdouble* W11 = (gdouble*)W11_;
   const int l = threadIdx.x & 63;
-#ifdef ELFIHIP_POTF2_STAMP
-  if ((threadIdx.x & 63) == 0) g_potf2_stamp[(R * 8 + 0) * 8 + 7] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
-#endif
   ldouble* MA = (ldouble*)sm + PT_MA;
   ldouble* NP = (ldouble*)sm + PT_NP;
   ldouble* CV = (ldouble*)sm + PT_CV;
@@ -258,7 +248,6 @@ __device__ __forceinline__ void potf2_tiles_body(double* Akk_, int64_t lda, doub
 #pragma unroll 1
     for (int p = 0; p < NB / 16; ++p) {
       ldouble* MAp = MA + (p & 1) * 256;
-      STAMP(p, 0);
       if (p > 0) {
         // wave p has put its diagonal tile into CV and then raised the flag (LDS operations of one wave complete in
         // order); polling it instead of a barrier keeps the other waves' panel solves off this chain
@@ -266,11 +255,9 @@ __device__ __forceinline__ void potf2_tiles_body(double* Akk_, int64_t lda, doub
         while (*flag != p && ++spins < (1 << 22)) {
         }
         if (spins >= (1 << 22) && bad == 0) bad = kblock * NB + 16 * p + 1;   // cannot happen: a pivot report, not a hang
-        STAMP(p, 5);
 #pragma unroll
         for (int c = 0; c < 16; ++c) a[c] = CV[(l & 31) * 17 + c];   // no masks: tile rows, then the identity rows
       }
-      STAMP(p, 1);
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
         double acc0 = a[c], acc1 = 0.0;
@@ -295,16 +282,13 @@ __device__ __forceinline__ void potf2_tiles_body(double* Akk_, int64_t lda, doub
         if (!(pc > 0.0) && bad == 0) bad = kblock * NB + 16 * p + c + 1;
         a[c] = fma(ay0 * ec, sc_, ay0);  // on tile row c this is p / sqrt(p): the diagonal of the factor
       }
-      STAMP(p, 2);
       // M for everybody: identity row t = l - 16 holds L^-T[t][c] = M[c][t]
       if (is_aug) {
         ldouble* mrow = MAp + 16 * trow;
 #pragma unroll
         for (int c = 0; c < 16; c += 2) *(ldouble2*)(mrow + c) = (v2d_t){a[c], a[c + 1]};
       }
-      STAMP(p, 3);
       lds_barrier();   // B(p)
-      STAMP(p, 4);
       // off the chain: the diagonal tile of L11 (lower triangle) to global memory, through LDS so that a store
       // instruction covers 8 rows x 128 bytes (one lane per row: 16 partial lines per instruction, and the CU's
       // memory pipe, not the elimination, sets the pace -- 1.5 us per panel)
@@ -368,7 +352,6 @@ __device__ __forceinline__ void potf2_tiles_body(double* Akk_, int64_t lda, doub
     const ldouble* MAp = MA + (p & 1) * 256;
     const ldouble* NPr = NP + ((p - 1) & 1) * 8 * 256;   // panels of step p-1
     ldouble* NPw = NP + (p & 1) * 8 * 256;
-    STAMP(p, 0);
     // ---- on the chain: U(p-1) on tile (R, p), the panel solve, U(p) on the wave's own diagonal tile
     // (the wave whose diagonal tile is factored next goes first at the SIMD's matrix pipe, which it shares with two
     // other waves and their deferred updates)
@@ -410,7 +393,6 @@ __device__ __forceinline__ void potf2_tiles_body(double* Akk_, int64_t lda, doub
 #pragma unroll
       for (int r = 0; r < 4; ++r) NPw[R * 256 + 64 * r + l] = -y[r];
     }
-    STAMP(p, 1);
     // ---- off the chain: U(p-1) on the remaining tiles right of column p (matrix tiles C < R; identity tiles C > R
     // once panel R has been eliminated, i.e. R <= p-1)
     if (p > 0) {
@@ -424,7 +406,6 @@ __device__ __forceinline__ void potf2_tiles_body(double* Akk_, int64_t lda, doub
         }
       }
     }
-    STAMP(p, 2);
     // ---- the solved panel to global memory: L11 rows (R > p); L^-T rows (R <= p) into WT's diagonal block and,
     // transposed, into W11 = L11^-1 (entries on and right of the diagonal only).  Row-major destinations go through the
     // wave's LDS staging tile: 8 rows x 128 bytes per store instruction instead of 16 rows x 32 bytes.
@@ -465,7 +446,6 @@ __device__ __forceinline__ void potf2_tiles_body(double* Akk_, int64_t lda, doub
 #pragma unroll
     for (int j = 0; j < 6; ++j) q[j] = q[j + 1];
     q[6] = (v4d){0.0, 0.0, 0.0, 0.0};
-    STAMP(p, 3);
     if (p + 1 < NB / 16) lds_barrier();   // B(p+1)
   }
 }
@@ -841,14 +821,6 @@ __device__ __forceinline__ StepUnit step_unit(const StepArgs& S, int i) {
   return step_decode(S, *reinterpret_cast<const int4*>(S.units + i));
 }
 
-#ifdef ELFIHIP_STEP_STAMP   // developer probe (scripts/native/step_timeline_probe.hip): shader-clock stamps of ONE step
-__device__ long long g_step_stamp[1024 * 8];
-__device__ int g_step_stamp_k = 16;
-#define SSTAMP(slot) do { if (threadIdx.x == 0 && S.P.k == g_step_stamp_k) g_step_stamp[blockIdx.x * 8 + (slot)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define SSTAMP(slot) do { } while (0)
-#endif
-
 // The update workgroup's walk through its units of one step (wgi: its index among the update workgroups).
 __device__ __forceinline__ void step_units(const StepArgs& S, double* sm, int wgi) {
   const PanelArgs& P = S.P;
@@ -950,10 +922,7 @@ __device__ __forceinline__ void step_units(const StepArgs& S, double* sm, int wg
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) cp[(int64_t)(i * 16 + 4 * r) * lda + j * 16] = cur.keep * cv[i][j][r] - acc[i][j][r];
-    if (!more) {
-      SSTAMP(6);
-      break;
-    }
+    if (!more) break;
     // the next unit's old values: in flight during its k loop
     const double* cn = nxt.C + coff;
 #pragma unroll
@@ -970,14 +939,11 @@ __device__ __forceinline__ void step_units(const StepArgs& S, double* sm, int wg
 __global__ __launch_bounds__(1024) void step_kernel(StepArgs S) {
   extern __shared__ __align__(16) double sm[];
   const PanelArgs& P = S.P;
-  SSTAMP(0);
   if (blockIdx.x == 0) {
     const int kk = P.k + 1;
     double* Akk = P.A + ((int64_t)kk * NB) * P.lda + (int64_t)kk * NB;
     double* Wkk = P.WT + ((int64_t)kk * NB) * P.lda + (int64_t)kk * NB;
-    SSTAMP(1);
     if (S.W11) potf2_tiles_call(Akk, P.lda, Wkk, P.lda, S.W11, S.info, kk, sm);   // (NULL: the update alone, scripts/native/step_probe.hip)
-    SSTAMP(2);
     return;
   }
   step_units(S, sm, blockIdx.x - 1);

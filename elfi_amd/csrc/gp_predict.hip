@@ -55,17 +55,6 @@ struct QueryArgs {
   double x2[PC];
 };
 
-#ifdef ELFIHIP_TRI_STAMP   // developer probe (scripts/tri_timeline.py): wall-clock stamps (100 MHz) per workgroup and phase
-__device__ unsigned long long g_tri_stamp[8192 * 8];
-#define PSTAMP(slot) do { const unsigned pidx_ = (MODE == 1 ? 4096u : 0u) + blockIdx.x + blockIdx.y * gridDim.x; \
-    if (threadIdx.x == 0 && pidx_ < 8192) g_tri_stamp[pidx_ * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define KSTAMP(slot) do { const unsigned kidx_ = 7168u + blockIdx.x + 16u * blockIdx.y; \
-    if (threadIdx.x == 0 && blockIdx.z == 0 && kidx_ < 8192) g_tri_stamp[kidx_ * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define PSTAMP(slot) do { } while (0)
-#define KSTAMP(slot) do { } while (0)
-#endif
-
 // ---- kr[s][i], partial mu ----------------------------------------------------------
 __global__ __launch_bounds__(256) void kstar_kernel(const double* X, const double* x2, const double* alpha,
                                                     const double* xs, const double* xs2, double* kr, double* kb,
@@ -75,7 +64,6 @@ __global__ __launch_bounds__(256) void kstar_kernel(const double* X, const doubl
   __shared__ double red[256];
   __shared__ double sx[256 + 1];  // this workgroup's query point and its squared norm
   const int s = blockIdx.y;
-  KSTAMP(0);
   // several 16-point passes in one launch (blockIdx.z): per-pass slices of the query points and outputs
   xs += (int64_t)blockIdx.z * PC * dp;
   xs2 += (int64_t)blockIdx.z * PC;
@@ -107,7 +95,6 @@ __global__ __launch_bounds__(256) void kstar_kernel(const double* X, const doubl
     if (threadIdx.x == 0) sx[256] = xs2[s];
   }
   __syncthreads();
-  KSTAMP(1);
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   double contrib = 0.0;
   if (i < np) {
@@ -130,7 +117,6 @@ __global__ __launch_bounds__(256) void kstar_kernel(const double* X, const doubl
   for (int off = 32; off > 0; off >>= 1) contrib += __shfl_xor(contrib, off, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = contrib;
   __syncthreads();
-  KSTAMP(2);
   if (threadIdx.x == 0) mu_part[s * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
@@ -198,7 +184,6 @@ __device__ __forceinline__ void tri_apply_body(const TriArgs& T, const int rb, c
   // through L2 again (16 passes at n = 8192: 8.6 GB per evaluation round, L2-bound at 1.6 ms against 0.45 ms of
   // matrix-pipe time).
   if (rb >= T.nrb) return;
-  PSTAMP(0);
   const int64_t i0 = (int64_t)rb * RB;
   int64_t k0 = (int64_t)kc * KC, k1 = k0 + KC;
   if (MODE == 1) {
@@ -243,7 +228,6 @@ __device__ __forceinline__ void tri_apply_body(const TriArgs& T, const int rb, c
 #pragma unroll
     for (int p = 0; p < 8; ++p) *reinterpret_cast<v2d*>(Bs + p * 512 + 2 * t) = breg[p];
     __syncthreads();
-    PSTAMP(2);
     if (pass + 1 < T.npass) load_b(pass + 1);   // in flight during this pass's products
     v4d acc0 = (v4d){0, 0, 0, 0}, acc1 = (v4d){0, 0, 0, 0};
 #pragma unroll
@@ -274,7 +258,6 @@ __device__ __forceinline__ void tri_apply_body(const TriArgs& T, const int rb, c
   }
   if (!FUSE || MODE == 2) return;
   int& s_last = *s_last_p;
-  PSTAMP(3);
   // ---- arrival at the row block (MI355X_MICROARCH.md, hand-off price list: write-through payload, every storing wave
   // drains, ONE lane arrives on the block's counter with a relaxed device-scope atomic; the last arriver takes ONE
   // agent-scope acquire -- its CU's L1 may hold the other workgroups' lines from an earlier launch -- then plain loads)
@@ -294,7 +277,6 @@ __device__ __forceinline__ void tri_apply_body(const TriArgs& T, const int rb, c
     s_last = last;
   }
   __syncthreads();
-  PSTAMP(4);
   if (!s_last) return;
   if (MODE == 0) {
     // what tri_reduce_kernel does for these 32 rows (same order of summation, same per-16-row blocks of v^2)
@@ -332,7 +314,6 @@ __device__ __forceinline__ void tri_apply_body(const TriArgs& T, const int rb, c
                             T.g_part + (int64_t)pass * PC * T.nrb * 2 * T.dp, rb, T.nrb, i0, T.n, T.np, T.dp, red, T.bias,
                             T.sq_part + (int64_t)pass * (T.np / 16) * PC);
   }
-  PSTAMP(5);
 }
 
 constexpr int RB_PER_KC = KC / RB;
@@ -1540,16 +1521,6 @@ static int cross_cov_impl(elfihip_gp* gp, const double* Q, int64_t S, double* co
 using namespace elfihip;
 
 extern "C" {
-
-#ifdef ELFIHIP_TRI_STAMP
-int elfihip_debug_tri_stamps(unsigned long long* out, int clear) {
-  if (clear) {
-    static unsigned long long zero[8192 * 8];
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(elfihip::g_tri_stamp), zero, sizeof(zero));
-  }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(elfihip::g_tri_stamp), sizeof(unsigned long long) * 8192 * 8);
-}
-#endif
 
 int elfihip_gp_lockstep_info(const elfihip_gp* gp, int* kinv_in_use, int64_t* steps, double* cond_estimate) {
   if (!gp) return fail(nullptr, ELFIHIP_ERR_ARG, "gp is NULL");

@@ -564,16 +564,9 @@ __global__ __launch_bounds__(SEL_NT) void sel_persistent_kernel(const double* d,
 // Why LDS and not registers: the first form of this kernel held sixteen values per thread in registers, which needs every
 // loop over them unrolled -- 30 KB of code, and a kernel that runs each instruction once or twice pays for FETCHING it:
 // the first histogram pass took 12.5 us against 3.4 us for the second pass through the same (then cached) code
-// (wall-clock stamps, scripts/native/sel_probe.hip).  With the keys in LDS the loops stay rolled.
+// (wall-clock stamps).  With the keys in LDS the loops stay rolled.
 // Same passes, same barriers between workgroups, same result (row order inside "< k-th", then "== k-th") as
 // sel_persistent_kernel.
-#ifdef ELFIHIP_SEL_STAMP   // developer probe (scripts/native/sel_probe.hip): wall-clock stamps (100 MHz) per workgroup and phase
-__device__ unsigned long long g_sel_stamp[512 * 32];
-#define SEL_STAMP() do { if (threadIdx.x == 0 && sel_si < 32) g_sel_stamp[blockIdx.x * 32 + sel_si] = __builtin_amdgcn_s_memrealtime(); ++sel_si; } while (0)
-#else
-#define SEL_STAMP() do { } while (0)
-#endif
-
 constexpr int SEL_RU = 16;
 constexpr size_t SEL_SLICE_LDS = (size_t)SEL_RU * SEL_NT * sizeof(unsigned long long);   // 128 KiB of dynamic LDS
 
@@ -586,10 +579,6 @@ __global__ __launch_bounds__(SEL_NT) void sel_resident_lds_kernel(const double* 
   __shared__ unsigned long long cand[SEL_SMALL];
   __shared__ unsigned int wl[SEL_NT / 64], we[SEL_NT / 64], base[2];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#ifdef ELFIHIP_SEL_STAMP
-  int sel_si = 0;
-#endif
-  SEL_STAMP();   // 0: start
   const unsigned int G = gridDim.x;
   const int64_t lo = (int64_t)blockIdx.x * (SEL_RU * SEL_NT);
   const int64_t hi = lo + SEL_RU * SEL_NT < n ? lo + SEL_RU * SEL_NT : n;
@@ -605,11 +594,6 @@ __global__ __launch_bounds__(SEL_NT) void sel_resident_lds_kernel(const double* 
 #pragma unroll
     for (int u = 0; u < SEL_RU; ++u) mine[64 * u] = key_of(v[u]);
   }
-  SEL_STAMP();   // 1: keys in LDS
-#ifdef ELFIHIP_SEL_STAMP
-  __syncthreads();
-  SEL_STAMP();   // 2 (stamped build only): every wave's keys are in LDS
-#endif
   unsigned long long prefix = 0, rem = (unsigned long long)k, n_lt = 0;
   unsigned int bar_no = 0;
   for (int pass = 0; pass < SEL_PASSES; ++pass) {
@@ -621,7 +605,7 @@ __global__ __launch_bounds__(SEL_NT) void sel_resident_lds_kernel(const double* 
     if (pass == 0) {
       // The exponent bits: a workgroup's 16 384 keys share a handful of digits, and LDS atomics on a handful of words are
       // serialised -- one atomic per key made this pass 8 us against 2 us for a pass whose digits spread (stamps:
-      // scripts/native/sel_probe.hip).  Every THREAD therefore counts up to four digits of its own sixteen keys in
+      // profiles/r06_selection_timeline.md).  Every THREAD therefore counts up to four digits of its own sixteen keys in
       // registers (compares and adds, nothing crosses lanes) and adds them once; a key with a fifth digit adds itself.
       // (Measured against it, first + second pass: one atomic per wave, digit and 64 keys for up to four digits 16 + 2.8 us;
       // four digits counted per WAVE in scalar registers 9.2 + 6.9 us -- the ballots cost more than they save.)
@@ -669,12 +653,9 @@ __global__ __launch_bounds__(SEL_NT) void sel_resident_lds_kernel(const double* 
       }
     }
     __syncthreads();
-    SEL_STAMP();   // pass: workgroup histogram complete
     for (int b = tid; b < SEL_BINS; b += SEL_NT)
       if (h[b]) atomicAdd(&w->hist[pass][b], h[b]);
-    SEL_STAMP();   // pass: histogram flushed
     sel_grid_barrier(w, G * ++bar_no);
-    SEL_STAMP();   // pass: barrier passed
     // every workgroup picks the digit of this pass from the complete histogram (as sel_persistent_kernel)
     constexpr int PER = SEL_BINS / 256;
     unsigned int c[PER], sum = 0;
@@ -732,7 +713,6 @@ __global__ __launch_bounds__(SEL_NT) void sel_resident_lds_kernel(const double* 
     n_lt = picked[2];
     const unsigned long long csize = picked[3];
     __syncthreads();
-    SEL_STAMP();   // pass: digit picked
     if (pass + 1 < SEL_PASSES && csize <= SEL_SMALL) {
       const unsigned long long cmask = ~0ull << shift;
       // the class's keys of this workgroup: places inside the workgroup from an LDS counter, ONE global reservation per
@@ -755,9 +735,7 @@ __global__ __launch_bounds__(SEL_NT) void sel_resident_lds_kernel(const double* 
                                                                                                     // matters if the input changes under the kernel)
         }
       }
-      SEL_STAMP();   // small class: keys stored
       sel_grid_barrier(w, G * ++bar_no);
-      SEL_STAMP();   // small class: barrier passed
       const int m = (int)csize;
       for (int j = tid; j < m; j += SEL_NT)
         cand[j] = __hip_atomic_load(&w->cand[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -779,7 +757,6 @@ __global__ __launch_bounds__(SEL_NT) void sel_resident_lds_kernel(const double* 
       prefix = picked[0];
       n_lt = picked[2];
       __syncthreads();
-      SEL_STAMP();   // small class: ranked
       break;
     }
   }
@@ -807,9 +784,7 @@ __global__ __launch_bounds__(SEL_NT) void sel_resident_lds_kernel(const double* 
     __hip_atomic_store(&w->counts[2 * blockIdx.x], tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&w->counts[2 * blockIdx.x + 1], te, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  SEL_STAMP();   // counts stored
   sel_grid_barrier(w, G * ++bar_no);
-  SEL_STAMP();   // counts: barrier passed
   {
     unsigned int o0 = 0, o1 = 0;
     for (unsigned int b = tid; b < blockIdx.x; b += SEL_NT) {
@@ -822,7 +797,6 @@ __global__ __launch_bounds__(SEL_NT) void sel_resident_lds_kernel(const double* 
     if (o1) atomicAdd(&base[1], o1);
     __syncthreads();
   }
-  SEL_STAMP();   // offsets formed
   // ---- stable write: slice order = wave order, then u, then lane
   int64_t at_l = (int64_t)base[0] + pl, at_e = (int64_t)n_lt + (int64_t)base[1] + pe;
   const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
@@ -846,7 +820,6 @@ __global__ __launch_bounds__(SEL_NT) void sel_resident_lds_kernel(const double* 
     at_l += __popcll(bl);
     at_e += __popcll(be);
   }
-  SEL_STAMP();   // written
 }
 
 // force_multi: use the nine-launch form (the host entry point does when the resident form reports a timed-out barrier)

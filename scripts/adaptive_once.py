@@ -46,7 +46,7 @@ def one(i):
 
 
 modes = ['fused', 'nostats', 'noout', 'state', 'multiw'] if mode == 'all' else [mode]
-for form in (2, 1):
+for form in (0, 1):
     ctx.call('elfihip_dist_set_form', form)
     for mode in modes:
         one(0)
@@ -57,4 +57,4 @@ for form in (2, 1):
         ms = ctx.timer_stop() / reps
         by = (8.0 * m + 8.0 * K) * n
         print("form %d (%s) %s n=%d m=%d K=%d: %.4f ms  %.0f GB/s  %.3f of 8 TB/s" % (
-            form, 'LDS-DMA' if form == 2 else 'register stage', mode, n, m, K, ms, by / ms / 1e6, by / ms / 1e6 / 8000), flush=True)
+            form, 'nt loads' if form == 0 else 'default loads', mode, n, m, K, ms, by / ms / 1e6, by / ms / 1e6 / 8000), flush=True)

@@ -11,7 +11,6 @@ tail -c 400 $OUT/bench_default.err
 timeout 600 python scripts/time_schedules.py > $OUT/schedules.txt 2>&1
 timeout 600 python scripts/bench_kernels.py > $OUT/kernels.md 2> $OUT/kernels.err
 timeout 60 ./scripts/native/step_probe > $OUT/step_probe.txt 2>&1
-timeout 60 ./scripts/native/potf2_probe > $OUT/potf2_probe.txt 2>&1
 timeout 60 ./scripts/native/mfma_probe > $OUT/mfma_probe.txt 2>&1
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/trace -o bench -- python $R/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline > $R/$OUT/trace.log 2>&1
