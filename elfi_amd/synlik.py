@@ -1,0 +1,277 @@
+"""Bayesian synthetic likelihood (BSL) on the GPU: the batched evaluation and drop-ins for the reference's tools.
+
+    lik = elfi_amd.standard_likelihood(shrinkage='warton', penalty=0.3)       # instead of elfi's pdf_methods factory
+    bsl = elfi.BSL(model, n_sim_round=500, likelihood=lik)                    # nothing in ELFI edited
+    bsl = elfi_amd.HipBSL(model, n_sim_round=500)                             # the same with the device default
+    elfi_amd.log_SL_stdev(model, theta, [100, 200, 500], ['S1', 'S2'], M=20)  # ONE device call for M x 3 evaluations
+    elfi_amd.select_penalty(model, 500, theta, ['S1', 'S2'], shrinkage='warton')   # ONE call for M x 31 (the default penalties)
+
+`syn_loglik` is the thin mirror of `elfihip_syn_loglik` (csrc/synlik.hip): G groups of n summary rows, K prefixes of
+every group and P Warton penalties in one launch.  The factories carry the reference's names and call signatures
+(elfi/methods/bsl/pdf_methods.py:19-74) and return callables with the reference's return types (`np.array([ll])`; a
+scalar for the robust one, a `functools.partial` with an `adjustment` keyword, which is how `BSL.__init__` detects
+misspecification, bsl.py:54).  `log_SL_stdev` / `select_penalty` (pre_sample_methods.py:102-143, 215-318) draw the same
+child seeds through `model.generate` as the reference and stack the M matrices as M groups.
+
+Not on the device: graphical-lasso shrinkage, the semiparametric likelihood, estimate_whitening_matrix, the
+slice samplers for gamma.  They raise or stay the reference's; nothing falls back quietly.
+"""
+import sys
+from functools import partial
+
+import numpy as np
+
+from . import _lib
+
+MAX_FEATURES = 64
+_VARIANTS = {'standard': 0, 'unbiased': 1, 'mean': 2, 'variance': 3}
+_CLASSES = {}
+
+
+def _variant_code(variant, adjustment):
+    if adjustment is not None:
+        if adjustment not in ('mean', 'variance'):
+            raise ValueError("adjustment must be 'mean' or 'variance', not %r" % (adjustment,))
+        if variant not in ('standard', 'robust', adjustment):
+            raise ValueError("adjustment=%r does not go with variant=%r" % (adjustment, variant))
+        return _VARIANTS[adjustment]
+    if variant == 'robust':
+        raise ValueError("variant='robust' needs adjustment='mean' or 'variance'")
+    if variant not in _VARIANTS:
+        raise ValueError("unknown variant %r (standard, unbiased, robust)" % (variant,))
+    return _VARIANTS[variant]
+
+
+def syn_loglik(ssx, ssy, n_groups=1, variant='standard', shrinkage=None, penalty=None, whitening=None, gamma=None,
+               adjustment=None, prefixes=None, penalties=None, return_moments=False, ctx=None):
+    """Gaussian synthetic log-likelihoods of `n_groups` groups of simulated summaries in one device call.
+
+    ssx: (n_groups * n, m), group g = rows g n ... g n + n - 1, or (n_groups, n, m); ssy: the m observed summaries.
+    variant: 'standard' | 'unbiased' | 'robust' (with adjustment 'mean' | 'variance' and gamma (m)).
+    shrinkage: None | 'warton' with `penalty` (one) or `penalties` (several, an axis of the result).
+    prefixes: row counts, ascending, the last == n: the likelihood of the first prefixes[k] rows of every group (an axis).
+    Returns an array (n_groups[, len(prefixes)][, len(penalties)]); a float for one group given as a 2-d array and
+    neither list.  With return_moments: (loglik, mean (G, m), cov (G, m, m)) of the full groups after whitening.
+    """
+    X = np.asarray(ssx, dtype=np.float64)
+    keep_group_axis = X.ndim == 3 or n_groups != 1
+    if X.ndim == 3:
+        if n_groups not in (1, X.shape[0]):
+            raise ValueError('n_groups=%d but ssx has %d groups' % (n_groups, X.shape[0]))
+        n_groups = X.shape[0]
+        X = X.reshape(-1, X.shape[2])
+    if X.ndim == 1:
+        X = X.reshape(-1, 1)
+    if X.ndim != 2:
+        raise ValueError('ssx must be 2d (rows of summaries) or 3d (groups of rows)')
+    n_groups = int(n_groups)
+    rows, m = X.shape
+    if n_groups < 1 or rows % n_groups:
+        raise ValueError('%d rows do not divide into %d groups' % (rows, n_groups))
+    n = rows // n_groups
+    if n < 2:
+        raise ValueError('a group needs at least 2 rows (n=%d)' % n)
+    if m < 1 or m > MAX_FEATURES:
+        raise ValueError('%d summaries: the device kernel takes 1 to %d' % (m, MAX_FEATURES))
+    y = np.ascontiguousarray(np.asarray(ssy, dtype=np.float64).reshape(-1))
+    if y.shape != (m,):
+        raise ValueError('ssy has %d entries, ssx has %d columns' % (y.size, m))
+    code = _variant_code(variant, adjustment)
+    g = None
+    if code >= 2:
+        if gamma is None:
+            raise ValueError('the robust likelihood needs gamma')
+        g = np.ascontiguousarray(np.broadcast_to(np.asarray(gamma, dtype=np.float64).reshape(-1), (m,)))
+    if shrinkage == 'glasso':
+        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
+    if shrinkage not in (None, 'warton'):
+        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    if shrinkage is not None and code != 0:
+        raise ValueError('shrinkage goes with the standard likelihood only (the unbiased and robust ones have none)')
+    pen = None
+    if shrinkage == 'warton':
+        if penalties is None and penalty is None:
+            raise ValueError("shrinkage='warton' needs penalty or penalties")
+        pen = np.ascontiguousarray(np.atleast_1d(np.asarray(penalty if penalties is None else penalties, dtype=np.float64)))
+        if pen.ndim != 1 or pen.size < 1:
+            raise ValueError('penalties must be a non-empty list')
+        if not np.all((pen >= 0) & (pen <= 1)):
+            raise ValueError('Gamma must be between 0 and 1')           # cov_warton.py:21-22
+    elif penalties is not None:
+        raise ValueError("penalties need shrinkage='warton'")
+    pre = None
+    if prefixes is not None:
+        pre = np.ascontiguousarray(np.atleast_1d(np.asarray(prefixes)).astype(np.int64))
+        if pre.ndim != 1 or pre.size < 1 or np.any(np.diff(pre) <= 0) or pre[0] < 2 or pre[-1] != n:
+            raise ValueError('prefixes must be ascending row counts >= 2 whose last entry is n=%d' % n)
+    W = None
+    if whitening is not None:
+        W = np.ascontiguousarray(whitening, dtype=np.float64)
+        if W.shape != (m, m):
+            raise ValueError('whitening must be (%d, %d)' % (m, m))
+    X = np.ascontiguousarray(X)
+    K = 1 if pre is None else pre.size
+    P = 0 if pen is None else pen.size
+    ll = np.empty((n_groups, K, max(P, 1)), dtype=np.float64)
+    mean = np.empty((n_groups, m), dtype=np.float64) if return_moments else None
+    cov = np.empty((n_groups, m, m), dtype=np.float64) if return_moments else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_syn_loglik", _lib.ptr(X), n_groups, n, m, m, _lib.ptr(y), _lib.ptr(W), code, _lib.ptr(g),
+             _lib.ptr(pre), 0 if pre is None else K, _lib.ptr(pen), P, _lib.ptr(ll), _lib.ptr(mean), _lib.ptr(cov))
+    if penalties is None:
+        ll = ll[:, :, 0]
+    if prefixes is None:
+        ll = ll[:, 0]
+    if not keep_group_axis:
+        ll = ll[0]
+        if ll.ndim == 0:
+            ll = float(ll)
+    return (ll, mean, cov) if return_moments else ll
+
+
+# ---- the reference's likelihood callables (pdf_methods.py:77-135, 138-176, 267-316) ----------------------------------
+
+def gaussian_syn_likelihood(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
+    """Standard synthetic log-likelihood of one (n, m) summary matrix; np.array([ll]) as the reference returns."""
+    return np.array([syn_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, shrinkage=shrinkage,
+                                penalty=penalty, whitening=whitening)])
+
+
+def gaussian_syn_likelihood_ghurye_olkin(ssx, ssy):
+    """The unbiased estimator of the synthetic likelihood (Ghurye & Olkin); np.array([ll])."""
+    return np.array([syn_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, variant='unbiased')])
+
+
+def syn_likelihood_misspec(ssx, ssy, gamma, adjustment):
+    """Mean- or variance-adjusted synthetic log-likelihood (Frazier & Drovandi); a scalar."""
+    return syn_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, gamma=gamma, adjustment=adjustment)
+
+
+def standard_likelihood(shrinkage=None, penalty=None, whitening=None):
+    """pdf_methods.standard_likelihood on the device (Warton shrinkage or none)."""
+    if shrinkage == 'glasso':
+        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
+    if shrinkage not in (None, 'warton'):
+        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    return partial(gaussian_syn_likelihood, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
+
+
+def unbiased_likelihood():
+    """pdf_methods.unbiased_likelihood on the device."""
+    return gaussian_syn_likelihood_ghurye_olkin
+
+
+def robust_likelihood(adjustment):
+    """pdf_methods.robust_likelihood on the device: a partial with the `adjustment` keyword BSL looks for."""
+    if adjustment not in ('mean', 'variance'):
+        raise ValueError("adjustment must be 'mean' or 'variance', not %r" % (adjustment,))
+    return partial(syn_likelihood_misspec, adjustment=adjustment)
+
+
+def _likelihood_setup(likelihood, **override):
+    """syn_loglik keywords of one of the callables above (None: the standard one)."""
+    kw = {}
+    fn = likelihood
+    if isinstance(likelihood, partial):
+        fn, kw = likelihood.func, dict(likelihood.keywords)
+    if fn is None or fn is gaussian_syn_likelihood:
+        kw.update({k: v for k, v in override.items()})
+        return dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw.get('whitening'))
+    if fn is gaussian_syn_likelihood_ghurye_olkin and not override:
+        return dict(variant='unbiased')
+    raise TypeError('the batched evaluation takes the device likelihoods of elfi_amd (standard_likelihood(...), '
+                    'unbiased_likelihood()); got %r' % (likelihood,))
+
+
+def _generate_groups(model, theta, max_sim, feature_names, M, seed):
+    """(M, max_sim, m) summaries and the (m,) observed ones: repeat i is one `model.generate` call of max_sim simulations
+    at theta under child seed i of SeedSequence(seed) -- the draws the reference's tools make, so the matrices are theirs."""
+    names = [feature_names] if isinstance(feature_names, str) else list(feature_names)
+    if isinstance(theta, dict):
+        fixed = dict(theta)
+    else:
+        fixed = {name: value for name, value in zip(model.parameter_names, theta)}
+    y = np.concatenate([np.ravel(model[name].observed) for name in names])
+    groups = np.empty((M, max_sim, y.size))
+    for i, child in enumerate(np.random.SeedSequence(seed).generate_state(M)):
+        sims = model.generate(max_sim, outputs=names, with_values=fixed, seed=child)
+        col = 0
+        for name in names:
+            block = np.reshape(sims[name], (max_sim, -1))
+            groups[i, :, col:col + block.shape[1]] = block
+            col += block.shape[1]
+    return groups, y
+
+
+def _prefix_axis(n_sim):
+    counts = np.atleast_1d(np.asarray(n_sim)).astype(np.int64).reshape(-1)
+    uniq = np.unique(counts)
+    return counts, uniq, np.searchsorted(uniq, counts)
+
+
+def log_SL_stdev(model, theta, n_sim, feature_names, likelihood=None, M=20, seed=None):
+    """pre_sample_methods.log_SL_stdev: the standard deviation of the log synthetic likelihood for every simulation
+    count of n_sim, from M repeats -- the M x len(n_sim) likelihoods in one device call."""
+    setup = _likelihood_setup(likelihood)
+    counts, uniq, where = _prefix_axis(n_sim)
+    groups, observed = _generate_groups(model, theta, int(uniq[-1]), feature_names, M, seed)
+    ll = syn_loglik(groups, observed, prefixes=uniq, **setup)          # (M, len(uniq))
+    return np.std(np.ascontiguousarray(ll[:, where].T), axis=1)     # (len(n_sim), M), the reference's layout
+
+
+def select_penalty(model, n_sim, theta, feature_names, likelihood=None, lmdas=None, M=20, sigma=1.5,
+                   shrinkage='warton', whitening=None, seed=None, verbose=False):
+    """pre_sample_methods.select_penalty with Warton shrinkage: for every simulation count the penalty whose log-likelihood
+    standard deviation over M repeats is closest to sigma -- the M x len(n_sim) x len(lmdas) likelihoods in one call."""
+    if shrinkage == 'glasso':
+        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
+    if shrinkage != 'warton':
+        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    setup = _likelihood_setup(likelihood, shrinkage=shrinkage, whitening=whitening)
+    if lmdas is None:
+        lmdas = list(np.arange(0.2, 0.8, 0.02))
+    counts, uniq, where = _prefix_axis(n_sim)
+    groups, observed = _generate_groups(model, theta, int(uniq[-1]), feature_names, M, seed)
+    setup.pop('penalty', None)
+    logliks = syn_loglik(groups, observed, prefixes=uniq, penalties=lmdas, **setup)     # (M, len(uniq), len(lmdas))
+    spread = logliks.std(axis=0)[where]                    # over the repeats: (len(n_sim), len(lmdas))
+    pick = np.abs(spread - sigma).argmin(axis=1)           # ties go to the smaller penalty index, as argmin does
+    if verbose:
+        print('log-likelihoods (repeat, simulation count, penalty):', logliks[:, where], sep='\n')
+        print('standard deviations (simulation count, penalty):', spread, sep='\n')
+    return np.asarray(lmdas, dtype=float)[pick], spread[np.arange(len(pick)), pick]
+
+
+# ---- elfi.BSL with the device likelihood as its default ----------------------------------------------------------------
+
+def _reference_bsl():
+    mod = sys.modules.get('elfi.methods.inference.bsl')
+    if mod is None:
+        raise ImportError("HipBSL subclasses the running program's elfi.BSL: `import elfi` first")
+    return mod.BSL
+
+
+def hip_bsl_class():
+    """The subclass of the imported ELFI's BSL (made once per reference class): the loop, the proposals, the gamma
+    samplers and the BslSample are the reference's; the default likelihood is the device one."""
+    BSL = _reference_bsl()
+    cls = _CLASSES.get(BSL)
+    if cls is not None:
+        return cls
+
+    class HipBSL(BSL):
+        __doc__ = hip_bsl_class.__doc__
+
+        def __init__(self, model, n_sim_round, feature_names=None, likelihood=None, **kwargs):
+            super(HipBSL, self).__init__(model, n_sim_round, feature_names=feature_names,
+                                         likelihood=likelihood or standard_likelihood(), **kwargs)
+
+    HipBSL.__name__ = 'HipBSL'
+    HipBSL.__qualname__ = 'HipBSL'
+    _CLASSES[BSL] = HipBSL
+    return HipBSL
+
+
+def HipBSL(model, n_sim_round, **kwargs):
+    """elfi.BSL(model, n_sim_round, feature_names=None, likelihood=None, ...) with the synthetic likelihood on the GPU."""
+    return hip_bsl_class()(model, n_sim_round, **kwargs)

@@ -304,6 +304,29 @@ int elfihip_weighted_var(elfihip_ctx* ctx, const double* X, int64_t n, int m, in
 int elfihip_weighted_var_dev(elfihip_ctx* ctx, const double* dX, int64_t n, int m, int64_t ldx, const double* dw,
                              double* ds2);
 
+/* ------------------------------------------------------------------ Bayesian synthetic likelihood
+ * The Gaussian synthetic log-likelihood of G groups of n simulated summary rows in one launch
+ * (elfi/methods/bsl/pdf_methods.py:77-176, 267-316; the loops of pre_sample_methods.py:102-143, 215-318).
+ * X (G n, m) row-major with pitch ldx, group g = rows g n ... g n + n - 1; m <= 64; n >= 2.  y (m) observed summaries.
+ * W (m, m) row-major or NULL: whitening, rows -> rows W^T and y -> W y before the moments (pdf_methods.py:105-108).
+ * variant: 0 standard, 1 unbiased (Ghurye-Olkin), 2 mean-adjusted, 3 variance-adjusted (2, 3: gamma_adj (m), else NULL).
+ * prefixes: K row counts, ascending, >= 2, the last == n; NULL (K 0 or 1) = {n}.  Prefix k takes the moments of the
+ * first prefixes[k] rows of every group, with the bits a group of that many rows has.
+ * penalties: P Warton penalties in [0, 1] (cov_warton(S, 1 - penalty), cov_warton.py:6-30); NULL (P 0) = no shrinkage.
+ * Variant 0 only: the reference defines no shrinkage for the others, ELFIHIP_ERR_ARG.
+ * loglik (G, K, max(P, 1)): -inf where the matrix has a non-positive Cholesky pivot (variant 1: also psi) or a value is
+ * not finite -- the status stays ELFIHIP_OK.  mean (G, m), cov (G, m, m) or NULL: sample mean and np.cov(rowvar=False)
+ * of the full group after whitening, before shrinkage and adjustment.
+ * Host form: host pointers, synchronises.  _dev form: X, y, W, gamma_adj, loglik, mean, cov are device pointers, no
+ * synchronisation; prefixes and penalties are host arrays in both forms (they are checked before the launch).
+ * Deterministic; a group's result does not depend on G. */
+int elfihip_syn_loglik(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, int m, int64_t ldx, const double* y,
+                       const double* W, int variant, const double* gamma_adj, const int64_t* prefixes, int K,
+                       const double* penalties, int P, double* loglik, double* mean, double* cov);
+int elfihip_syn_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx, const double* dy,
+                           const double* dW, int variant, const double* dgamma_adj, const int64_t* prefixes, int K,
+                           const double* penalties, int P, double* dloglik, double* dmean, double* dcov);
+
 /* ------------------------------------------------------------------ summaries
  * Row-wise summary statistics that ELFI's example models install as elfi.Summary operations, with
  * NumPy's exact (pairwise) summation order, i.e. bit-identical results:
