@@ -3,8 +3,15 @@
 // evaluates scipy.stats.skewnorm.cdf there; with z = (x - loc) / scale that is  Phi(z) - 2 T(z, a)  [Owen 1956],
 // T(h, a) = (1 / 2 pi) int_0^a exp(-h^2 (1 + x^2) / 2) / (1 + x^2) dx.  Every shape parameter on this path lies in [0, 1]
 // (sigma_n / sqrt(sigma_n^2 + 2 v), sqrt((A - d) / (A + d))), so the integral is taken directly: Gauss-Legendre panels
-// whose width shrinks with |h| (the integrand falls like exp(-h^2 x^2 / 2)), ten points each -- relative accuracy about
-// 1e-13 or better, no case analysis.
+// whose width shrinks with |h| (the integrand falls like exp(-h^2 x^2 / 2)), ten points each, no case analysis.
+// Accuracy of this rule, measured in binary64 against 50-digit values (tests/golden/special_fn.npz, written by
+// oracle/make_golden_special.py; tests/test_special_reference.py holds a transcription of the loop below to them):
+//   absolute:  |T - exact| <= 1.1e-14 for every h and 0 <= a <= 1;  W = Phi(z) Phi(-z) - 2 T(z, b) to 2.1e-14
+//   relative:  |h| <= 6: 2.5e-13 (worst just below a panel edge, |h| a = 4/3 with one panel; 1.6e-13 on the test grid)
+//              6 < |h| <= 12: 6e-15;  12 < |h| <= 28: 4e-14;  28 < |h| <= 37: 6e-14 (the rounding of h^2 (1 + x^2) / 2
+//              near 700 in front of exp);  beyond |h| = 37.5 T is subnormal and only the absolute figure holds
+// A first CPU comparison had suggested 8e-8 relative at |h| = 20, a >= 0.9: that was the reference integration's
+// setting, not this rule (1.1e-14 relative there).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -24,8 +31,8 @@ __device__ inline double owens_t(double h, double a) {
                         0.14945134915058059315, 0.06667134430868813759};
   if (!(a > 0.0)) return 0.0;
   const double ah = fabs(h) * a;
-  int panels = 1 + (int)(0.75 * ah);       // panel width <= 4 / (3 |h|); checked against scipy.special.owens_t over
-  if (panels > 96) panels = 96;            // |h| <= 37: 2e-13 relative (the rounding of exp at arguments near -700)
+  int panels = 1 + (int)(0.75 * ah);       // panel width <= 4 / (3 |h|): accuracy in the header comment
+  if (panels > 96) panels = 96;
   const double w = a / panels, hh = -0.5 * h * h;
   double sum = 0.0;
   for (int p = 0; p < panels; ++p) {
