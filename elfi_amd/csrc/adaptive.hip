@@ -11,7 +11,7 @@
 //     (AdaptiveDistanceSMC hands a list, samplers.py:657-660), rank by the last column.
 // The three are independent given the rows, so one kernel does them while a tile of rows is on the chip: 8 m bytes read
 // per row, 8 K written (the distances, when the caller wants them), nothing else -- against three reads of the matrix
-// by welford.hip (two passes) + distance.hip (round 3: 3.35 ms per round of 10^7 x 64 where one read takes 0.85 ms).
+// by welford.hip (two passes) + multiw.hip (round 3: 3.35 ms per round of 10^7 x 64 where one read takes 0.85 ms).
 //
 //   * rows stream exactly as in distance.hip (software-pipelined 16-byte loads -> LDS tile with an odd pitch); lane r sums
 //     row r left to right for each weight vector: the distances are bit-identical to dist_multiw_pipe_kernel / cdist;
@@ -28,6 +28,7 @@
 #include "common.hpp"
 #include "tile_stream.hpp"
 #include "internal.hpp"
+#include "dist_launch.hpp"
 
 #include <algorithm>
 
@@ -396,15 +397,13 @@ __global__ __launch_bounds__(ADA_T, ADA_OCC) void adaptive_pass_kernel(AdaptArgs
   if (P.acc && (tid & 63) == 0 && nacc) atomicAdd(P.acc_count, nacc);
 }
 
-static bool ada_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // ---- narrow rows (round 6): m = 2 or 4 summaries -------------------------------------------------------------------------------
 // A row is one or two 16-byte granules: lane r of a 256-thread workgroup OWNS rows r, r + 256, ... (U rows = U 16- or 32-byte
 // non-temporal loads in flight per lane, a wave-instruction covers 1 KiB of contiguous rows; no LDS tile, no barrier per tile).
 // Rounds 4-5 sent m = 2 through the separate K-weight and two-pass statistics kernels (three reads: 0.126 ms for 4 10^6 x 2,
 // K = 3 = 0.16 of HBM) because the tile kernel above streams such rows at a quarter of their rate.
 //   * distances: every sum left to right over the row's M elements with the weights in registers -- the expressions of
-//     dist_multiw_narrow_kernel (distance.hip): bit-identical to it and to cdist;
+//     dist_multiw_narrow_kernel (multiw.hip): bit-identical to it and to cdist;
 //   * column statistics: the lane's U rows of an iteration -> two-pass (mean, M2) per column in registers (chunk_stats) ->
 //     Chan's update of the lane's running triples; at the end the 256 lanes' triples are merged by a fixed tree in LDS and
 //     one (1 + 2m) partial per workgroup leaves for adaptive_finish_kernel: no atomics, bit-reproducible for a launch shape;
@@ -616,14 +615,14 @@ static int ada_rows_per_tile(int m) {
 }
 
 static bool adaptive_narrow(const double* dX, int m, int64_t ldx, int K) {
-  return (m == 2 || m == 4) && K >= 1 && K <= ADA_NARROW_KMAX && !(ldx & 1) && ada_aligned16(dX);
+  return (m == 2 || m == 4) && K >= 1 && K <= ADA_NARROW_KMAX && !(ldx & 1) && aligned16(dX);
 }
 
 bool adaptive_pass_supported(const double* dX, int m, int64_t ldx, int K) {
   if (adaptive_narrow(dX, m, ldx, K)) return true;   // lane-owned rows (adaptive_narrow_kernel)
   // (m = 2 with more than eight weight vectors: the generic addressing streams such rows at a quarter of the separate
   // kernels' rate -- they take those)
-  if (m < 4 || m > ADA_T / 2 || (m & 1) || (ldx & 1) || !ada_aligned16(dX)) return false;
+  if (m < 4 || m > ADA_T / 2 || (m & 1) || (ldx & 1) || !aligned16(dX)) return false;
   return ada_lds_bytes(m, K, ada_rows_per_tile(m)) <= 64 * 1024;
 }
 
@@ -638,22 +637,10 @@ int adaptive_pass_impl(elfihip_ctx* ctx, const double* dX, int64_t n, int m, int
   if (n <= 0) return ELFIHIP_OK;
   AdaptArgs P;
   RowArgs& A = P.A;
-  A.X = dX;
-  A.n = n;
-  A.ldx = ldx;
-  A.y = dy;
-  A.aux = dW;
-  A.out = dout;
-  A.p = 2.0;
-  A.inv_p = 0.5;
-  A.m = m;
-  A.mp = m | 1;
+  A = make_row_args(ctx, dX, n, m, ldx, dy, dW, 2.0, dout);   // (vec2 holds: adaptive_pass_supported)
   A.K = K;
-  A.vec2 = 1;
   A.R = ada_rows_per_tile(m);
-  A.nt = ctx->dist_form != 1;   // the rows are read once
-  A.div_h = make_fastdiv((uint32_t)(m / 2));
-  A.F = F ? *F : RejectFilter{nullptr, nullptr, nullptr, nullptr, 0u, 0ll};
+  if (F) A.F = *F;
   P.acc = dacc;
   P.acc_count = dacc_count;
   P.partial = partial;

@@ -8,12 +8,14 @@ struct elfihip_reject;
 
 namespace elfihip {
 
-// distance.hip: device-pointer distance passes, optionally with the fused selection filter (see RejectFilter).
+// distance.hip / multiw.hip: device-pointer distance passes, optionally with the fused selection filter (see RejectFilter).
 // *filtered reports whether the kernel that ran offered the candidates itself; *merged whether it also merged the sealed
 // candidate list M (RejectMergeJob) into the sampler state.
 int dist_rows_dev_impl(elfihip_ctx* ctx, int metric, const double* dX, int64_t n, int m, int64_t ldx, const double* dy,
                        const double* daux, double p, double* dout, const RejectFilter* F, bool* filtered,
                        const RejectMergeJob* M = nullptr, bool* merged = nullptr);
+// mahalanobis.hip: picks and launches the Mahalanobis kernel for A's shape (A from make_row_args, aux = VI)
+int launch_mahalanobis(elfihip_ctx* ctx, const RowArgs& A);
 int dist_multiw_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t n, int m, int64_t ldx, const double* dy,
                          const double* dW, int K, double* dout, const RejectFilter* F, bool* filtered);
 

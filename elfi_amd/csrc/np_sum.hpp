@@ -1,4 +1,4 @@
-// NumPy's summation order on the device (summaries.hip's row statistics, distance.hip's correlation mean).
+// NumPy's summation order on the device (summaries.hip's row statistics, dist_metrics.hpp's correlation mean).
 //
 // np.add.reduce along a contiguous axis is a pairwise sum: fewer than 8 terms in order; 8 .. 128 terms by eight
 // interleaved accumulators over stride 8, combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the tail in order; more than

@@ -87,7 +87,7 @@ constexpr int REJ_MERGE_EVERY = 8;        // pushes per merge
 constexpr unsigned int REJ_CAP = 1u << 16;   // smallest candidate list
 constexpr int64_t REJ_MAX_K_HOST = 1 << 20;  // host-merge states
 constexpr double REJ_HEAVY = 8192.0;         // expected candidates from which a push takes the radix selection
-constexpr int REJ_ACC_COLS = 64;             // nested columns an acceptance condition can cover (= kMaxK of distance.hip)
+constexpr int REJ_ACC_COLS = 64;             // nested columns an acceptance condition can cover (= kMaxK of dist_launch.hpp)
 constexpr int64_t REJ_ACC_SELECT_MIN = 1 << 15;   // batch rows from which an acceptance push selects instead of listing
 // provisional threshold of a large first batch (adaptive_push_impl)
 constexpr int64_t REJ_PROV_MIN_ROWS = 1 << 20;

@@ -22,6 +22,7 @@
 #include "np_sum.hpp"
 #include "philox.hpp"
 #include "tile_stream.hpp"
+#include "dist_launch.hpp"
 
 #pragma clang fp contract(off)
 
@@ -243,26 +244,6 @@ static int launch_summary(elfihip_ctx* ctx, SumArgs S) {
   return launch_status(ctx, "row_summary_kernel");
 }
 
-static RowArgs summary_row_args(const double* dX, int64_t n, int L, int64_t ldx) {
-  RowArgs A;
-  A.X = dX;
-  A.n = n;
-  A.ldx = ldx;
-  A.y = nullptr;
-  A.aux = nullptr;
-  A.out = nullptr;
-  A.p = 2.0;
-  A.inv_p = 0.5;
-  A.m = L;
-  A.mp = L | 1;
-  A.K = 0;
-  A.R = 0;
-  A.nt = 0;
-  A.vec2 = (L % 2 == 0) && (ldx % 2 == 0) && tile_aligned16(dX);
-  A.div_h = make_fastdiv((uint32_t)(A.vec2 ? L / 2 : L));
-  return A;
-}
-
 static int summary_dev_impl(elfihip_ctx* ctx, int kind, const double* dX, int64_t n, int L, int64_t ldx, int lag,
                             double* dout) {
   ELFIHIP_REQUIRE(ctx, n >= 0 && L >= 1 && ldx >= L, "bad shape n=%lld L=%d ldx=%lld", (long long)n, L, (long long)ldx);
@@ -270,8 +251,7 @@ static int summary_dev_impl(elfihip_ctx* ctx, int kind, const double* dX, int64_
   ELFIHIP_REQUIRE(ctx, n == 0 || (dX && dout), "NULL data pointer");
   if (n == 0) return ELFIHIP_OK;
   SumArgs S;
-  S.R = summary_row_args(dX, n, L, ldx);
-  S.R.nt = ctx->dist_form != 1;
+  S.R = make_row_args(ctx, dX, n, L, ldx, nullptr, nullptr, 2.0, nullptr);   // (no observed row, no output of its own)
   S.lag = lag;
   S.t1 = S.t2 = nullptr;
   S.obs1 = S.obs2 = 0.0;
@@ -297,8 +277,7 @@ static int ma2_dev_impl(elfihip_ctx* ctx, const double* dW, int64_t n, int n_obs
   ELFIHIP_REQUIRE(ctx, !draw || n_obs + 2 <= 128, "the drawing form handles up to 126 observations per simulation");
   if (n == 0) return ELFIHIP_OK;
   SumArgs S;
-  S.R = summary_row_args(draw ? nullptr : dW, n, n_obs + 2, ldw);
-  S.R.nt = ctx->dist_form != 1;
+  S.R = make_row_args(ctx, draw ? nullptr : dW, n, n_obs + 2, ldw, nullptr, nullptr, 2.0, nullptr);
   S.seed = seed;
   S.stream = stream;
   S.lag = 0;

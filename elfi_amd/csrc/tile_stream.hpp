@@ -445,6 +445,4 @@ __device__ __forceinline__ void reject_merge_wave(const RejectMergeJob& J, void*
 
 #endif
 
-static inline bool tile_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace elfihip

@@ -464,7 +464,7 @@ def test_lds_dma_row_stream_equals_the_register_pipeline_and_cdist(hip_ctx, m):
 @pytest.mark.parametrize('m', [2, 4])
 def test_narrow_row_kernels_equal_the_tile_kernels_and_cdist(hip_ctx, m):
     """Round 6: rows of 2 or 4 summaries (configs[0]'s own shape) are owned by lanes -- U 16-/32-byte loads per lane, no LDS
-    (csrc/distance.hip: dist_rows_narrow_kernel, dist_rows_mahalanobis_narrow_kernel, dist_multiw_narrow_kernel) -- against
+    (csrc/distance.hip: dist_rows_narrow_kernel, csrc/mahalanobis.hip: dist_rows_mahalanobis_narrow_kernel, csrc/multiw.hip: dist_multiw_narrow_kernel) -- against
     SciPy's cdist and against the tile kernels they replace (form 1), bit for bit: every metric, weights, ragged and tiny n
     on both sides of the 1024-row granule, a row pitch that is not the width, the K-weight form, and the sampler state fed
     by the same pass."""
