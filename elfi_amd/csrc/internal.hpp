@@ -26,11 +26,11 @@ int topk_dev_impl(elfihip_ctx* ctx, const double* dD, int64_t n, int64_t stride,
 
 const void* topk_resident_err_dev(elfihip_ctx* ctx);   // see topk.hip: device address of the resident selection's time-out flag, or NULL
 
-// reject.hip: the sampler state; push of a device-resident batch (no device guard, no argument checks)
+// reject.hip: the sampler state; push of a device-resident batch (no device guard, no argument checks).  Every push form
+// takes the same walk (reject_push) under the policy of reject_policy.hpp.
 elfihip_ctx* reject_ctx(elfihip_reject* h);
 int reject_push_rows_impl(elfihip_reject* h, int metric, const double* dX, int64_t n, int m, int64_t ldx,
                           const double* dy, const double* daux, double p, double* dout, int64_t row_base);
-
 
 // welford.hip: AdaptiveDistance.add_data in the reference's own (two-pass) form, into dstate (1 + 2m)
 int welford_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t n, int m, int64_t ldx, double* dstate);
@@ -42,7 +42,7 @@ int adaptive_pass_impl(elfihip_ctx* ctx, const double* dX, int64_t n, int m, int
                        const double* dW, int K, double* dout, const RejectFilter* F, const double* dacc,
                        unsigned long long* dacc_count, double* partial, int* nparts);
 int adaptive_stats_finish(elfihip_ctx* ctx, const double* partial, int nparts, int m, double* bst, double* dstate);
-// reject.hip: the batch against a sampler state (h may be NULL: distances and statistics only)
+// reject.hip: the batch against a sampler state, through that walk (h may be NULL: distances and statistics only)
 int adaptive_push_impl(elfihip_ctx* ctx, elfihip_reject* h, const double* dX, int64_t n, int m, int64_t ldx,
                        const double* dy, const double* dW, int K, double* dout, double* dwelford, int64_t row_base);
 

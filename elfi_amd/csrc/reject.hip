@@ -7,37 +7,34 @@
 //   * once the state holds k finite distances its k-th is a threshold, and the distance kernel itself appends the rows
 //     below it to a candidate list (RejectFilter, distance.hip: one wave-aggregated atomic per wave that has a hit --
 //     after j batches of the same distribution about k / j rows per batch qualify);
-//   * a single-workgroup kernel merges state and candidates by ranks and keeps the first k -- not after every batch
-//     but, once the threshold has settled, after every REJ_MERGE_EVERY-th (the list simply keeps growing in between, against a threshold that is then a
-//     few batches old: still an upper bound of the current k-th distance, so nothing is missed), because a 15 us
-//     one-workgroup launch between two 48 us distance passes is a third of their time, and running it on a second
-//     stream costs a 10 us event hand-over per batch on this stack (both measured); result / reset / state_dev /
-//     flush merge what is pending first;
+//   * a single-workgroup kernel merges state and candidates by ranks and keeps the first k -- not after every batch but,
+//     once the threshold has settled, after every REJ_MERGE_EVERY-th (the list keeps growing in between, against a
+//     threshold that is a few batches old: still an upper bound of the current k-th distance, so nothing is missed),
+//     because a 15 us one-workgroup launch between two 48 us distance passes is a third of their time (a second stream
+//     costs a 10 us event hand-over per batch; both measured); result / reset / state_dev / flush merge what is pending;
 //   * states with k <= REJ_FUSED_MAX_K hold TWO lists.  Pushed through the DMA row kernel, such a state does not merge
 //     at a merge point: it SEALS the open list and opens the other (empty) one, and the next push's distance launch takes
 //     the merge as a job -- workgroup 0 merges the sealed list in one wave (reject_merge_wave, tile_stream.hpp) while
-//     the other workgroups stream (dist_rows_dma_kernel<..., MERGE>).  Such states seal every p / 3 pushes, so that a
-//     sealed list stays within the 512-entry sort the wave finishes inside the pass.  Whatever cannot hand a sealed list
-//     to such a launch (flush, result, state_dev, meta, growing the lists, the selection and acceptance paths, the other
-//     push forms, adaptive_push_impl) merges it first with the standalone kernel.  Measured at 10^6 x 32, k = 1000:
-//     the fused launches take ~1 us more than the plain pass, against 16 us per standalone merge;
+//     the other workgroups stream (dist_rows_dma_kernel<..., MERGE>).  Whatever cannot hand a sealed list to such a
+//     launch (flush, result, state_dev, meta, growing the lists, the selection and acceptance routes, the other push
+//     forms) merges it with the standalone kernel.  Measured at 10^6 x 32, k = 1000: the fused launches take ~1 us
+//     more than the plain pass, against 16 us per standalone merge;
 //   * only while the state is still filling up (the first batch) the batch goes through the radix selection of topk.hip.
 // Only the k best rows ever leave the GPU; row numbers are global (row_base + row in the batch), so the host fetches the
 // parameters / summaries of the accepted rows from its own batch store (as ELFI's OutputPool keeps them).
 //
-// The state never fails for valid input (round 2's fixed 65 536-entry list could overflow -- a small first batch, a
-// round change without reset -- and reported it only at result(), when the batches were gone):
-//   * the list holds 8 x (largest batch pushed) entries and merges happen at least every 8th push, so it cannot overflow;
-//   * a push expected to offer many candidates (n k / rows seen > 8192: the threshold is still weak) takes the radix
-//     selection of its k best instead of the list -- exact either way, this only keeps one-workgroup merges short.
+// What a batch does when it meets the state -- select, filter, seal, merge, or the provisional threshold of a large
+// first batch -- is decided in reject_policy.hpp and carried out by ONE walk for every push form (reject_push).  The
+// state never fails for valid input: a list holds 8 x (largest batch pushed) entries and is merged or sealed at least
+// every 8th push; a push expected to offer very many candidates takes the radix selection instead -- exact either way.
 // k > 2048 ("host-merge" states, up to 2^20): the candidates of every push -- a few hundred rows once the threshold has
 // settled -- are merged into a sorted host copy of the state, the k-th distance goes back as the device threshold.
 // An acceptance threshold (the objective of Rejection.sample(threshold=...), samplers.py:219-225: EVERY nested column of
 // a row must be <= threshold) is applied by the candidate pass; accepted rows are counted on the device.
 #include "internal.hpp"
+#include "reject_policy.hpp"
 
 #include <algorithm>
-#include <cmath>
 #include <limits>
 #include <vector>
 
@@ -83,15 +80,8 @@ namespace elfihip {
 
 constexpr int64_t REJ_MAX_K = 2048;       // state entries (LDS-resident during a merge)
 constexpr int REJ_CHUNK = 1024;           // candidates merged per round
-constexpr int REJ_MERGE_EVERY = 8;        // pushes per merge
-constexpr unsigned int REJ_CAP = 1u << 16;   // smallest candidate list
 constexpr int64_t REJ_MAX_K_HOST = 1 << 20;  // host-merge states
-constexpr double REJ_HEAVY = 8192.0;         // expected candidates from which a push takes the radix selection
 constexpr int REJ_ACC_COLS = 64;             // nested columns an acceptance condition can cover (= kMaxK of dist_launch.hpp)
-constexpr int64_t REJ_ACC_SELECT_MIN = 1 << 15;   // batch rows from which an acceptance push selects instead of listing
-// provisional threshold of a large first batch (adaptive_push_impl)
-constexpr int64_t REJ_PROV_MIN_ROWS = 1 << 20;
-constexpr unsigned int REJ_PROV_MAX_CAND = 1u << 16;
 
 __device__ __forceinline__ bool rej_less(double av, long long ar, double bv, long long br) {
   return av < bv || (av == bv && ar < br);
@@ -343,53 +333,50 @@ __global__ void reject_init_kernel(double* best_val, long long* best_row, double
   }
 }
 
-static RejArgs merge_args(elfihip_reject* h, int ncand, long long row_offset) {
-  RejArgs S;
-  S.best_val = h->best_val;
-  S.best_row = h->best_row;
-  S.thr = h->thr;
-  S.cand_val = h->cand_val;
-  S.cand_row = h->cand_row;
-  S.count = h->count;
-  S.status = h->status;
-  S.cap = h->cap;
-  S.k = (int)h->k;
+// What every merge of a list -- the open one or the sealed one -- takes from the state, whichever struct carries it to its
+// kernel (RejArgs: reject_merge_kernel; RejectMergeJob: the next DMA row launch).
+template <class Args>
+static Args merge_fields(elfihip_reject* h, bool sealed_list) {
+  Args A{};
+  A.best_val = h->best_val;
+  A.best_row = h->best_row;
+  A.thr = h->thr;
+  A.cand_val = sealed_list ? h->sealed_val : h->cand_val;
+  A.cand_row = sealed_list ? h->sealed_row : h->cand_row;
+  A.count = sealed_list ? h->sealed_count : h->count;
+  A.status = h->status;
+  A.cap = h->cap;
+  A.k = (int)h->k;
+  A.export_val = reinterpret_cast<double*>(h->export_dst);   // (the buffer current at the launch)
+  return A;
+}
+
+// the one launch of reject_merge_kernel; ncand < 0: the list's own counter, merged only if it says ok_lo .. ok_hi entries
+static void launch_merge(elfihip_reject* h, bool sealed_list, int ncand, long long row_offset, unsigned int ok_lo = 0u,
+                         unsigned int ok_hi = ~0u) {
+  RejArgs S = merge_fields<RejArgs>(h, sealed_list);
   S.ncand = ncand;
   S.row_offset = row_offset;
-  S.export_val = reinterpret_cast<double*>(h->export_dst);
-  S.ok_lo = 0u;
-  S.ok_hi = ~0u;
-  return S;
+  S.ok_lo = ok_lo;
+  S.ok_hi = ok_hi;
+  hipLaunchKernelGGL(reject_merge_kernel, dim3(1), dim3(1024), REJ_MERGE_LDS, h->ctx->stream, S);
 }
 
 static int host_merge(elfihip_reject* h, unsigned int ncand, long long row_offset);
+
+// merge the open list (ncand < 0: as many as its counter says): on the device, or into the host copy of a host-merge state
+static int merge_list(elfihip_reject* h, int ncand, long long row_offset) {
+  if (h->host_mode) return host_merge(h, ncand < 0 ? ~0u : (unsigned int)ncand, row_offset);
+  launch_merge(h, false, ncand, row_offset);
+  return launch_status(h->ctx, "reject_merge_kernel");
+}
 
 // the sealed list by the standalone merge, where no fused launch takes it (see reject_push)
 static int merge_sealed(elfihip_reject* h) {
   if (!h->sealed) return ELFIHIP_OK;
   h->sealed = false;
-  RejArgs S = merge_args(h, -1, 0);
-  S.cand_val = h->sealed_val;
-  S.cand_row = h->sealed_row;
-  S.count = h->sealed_count;
-  hipLaunchKernelGGL(reject_merge_kernel, dim3(1), dim3(1024), REJ_MERGE_LDS, h->ctx->stream, S);
+  launch_merge(h, true, -1, 0);
   return launch_status(h->ctx, "reject_merge_kernel");
-}
-
-// the sealed list's merge as a job for the next DMA row launch (export: the buffer current at that launch)
-static RejectMergeJob sealed_job(elfihip_reject* h) {
-  RejectMergeJob J;
-  J.best_val = h->best_val;
-  J.best_row = h->best_row;
-  J.thr = h->thr;
-  J.cand_val = h->sealed_val;
-  J.cand_row = h->sealed_row;
-  J.count = h->sealed_count;
-  J.status = h->status;
-  J.cap = h->cap;
-  J.k = (int)h->k;
-  J.export_val = reinterpret_cast<double*>(h->export_dst);
-  return J;
 }
 
 // merge whatever the lists hold (asynchronous on the context's stream; host-merge states synchronise)
@@ -398,15 +385,17 @@ static int reject_flush(elfihip_reject* h) {
   if (h->unmerged == 0) return ELFIHIP_OK;
   h->unmerged = 0;
   h->pending_rows = 0;
-  if (h->host_mode) return host_merge(h, ~0u, 0);
-  hipLaunchKernelGGL(reject_merge_kernel, dim3(1), dim3(1024), REJ_MERGE_LDS, h->ctx->stream, merge_args(h, -1, 0));
-  return launch_status(h->ctx, "reject_merge_kernel");
+  return merge_list(h, -1, 0);
+}
+
+static void launch_init(elfihip_reject* h) {
+  const int kd = (int)std::min<int64_t>(h->k, REJ_MAX_K);
+  hipLaunchKernelGGL(reject_init_kernel, dim3((unsigned)((kd + 255) / 256)), dim3(256), 0, h->ctx->stream, h->best_val,
+                     h->best_row, h->thr, h->count, h->sealed_count, h->status, h->acc_count, kd);
 }
 
 static int reject_reset_impl(elfihip_reject* h) {
-  hipLaunchKernelGGL(reject_init_kernel, dim3((unsigned)((std::min<int64_t>(h->k, REJ_MAX_K) + 255) / 256)), dim3(256), 0,
-                     h->ctx->stream, h->best_val, h->best_row, h->thr, h->count, h->sealed_count, h->status, h->acc_count,
-                     (int)std::min<int64_t>(h->k, REJ_MAX_K));
+  launch_init(h);
   h->filled = 0;
   h->unmerged = 0;
   h->sealed = false;
@@ -435,11 +424,10 @@ static void rej_lay_out_lists(elfihip_reject* h) {
   }
 }
 
-// A list holds 8 x the largest batch (>= 65 536 entries) and receives at most REJ_MERGE_EVERY pushes before it is merged
-// or sealed -- a sealed list receives nothing until its merge has emptied it -- so neither list can overflow.  (Two lists:
-// 2 x 128 MB at 10^6-row batches.)  Growing them merges what is pending, waits, and reallocates.
+// A list holds rej_list_size(largest batch) entries -- a sealed list receives nothing until its merge has emptied it -- so
+// neither list can overflow.  (Two lists: 2 x 128 MB at 10^6-row batches.)  Growing them merges what is pending, waits, and reallocates.
 static int ensure_cap(elfihip_reject* h, int64_t n) {
-  const int64_t want = std::max<int64_t>(REJ_CAP, REJ_MERGE_EVERY * n);
+  const int64_t want = rej_list_size(n);
   if (want <= (int64_t)h->cap) return ELFIHIP_OK;
   elfihip_ctx* ctx = h->ctx;
   ELFIHIP_REQUIRE(ctx, want < (int64_t)1 << 31, "batch of %lld rows is too large for the sampler state", (long long)n);
@@ -533,127 +521,6 @@ static int host_upload(elfihip_reject* h) {
   return ELFIHIP_OK;
 }
 
-// Fold a batch into the state.  run(F, M, &filtered, &merged) launches the distance pass with the filter F (or without:
-// F == nullptr) on the context's stream, and with it, if it can, the merge M of the sealed list; dsel / stride address the
-// batch's ranking distances (the last of `ncols` nested columns) for the passes that need them.  fusable: the pass is one
-// that can take a merge job (the row distances), so the state seals its open list at a merge point instead of merging it.
-template <class Run>
-static int reject_push(elfihip_reject* h, int64_t n, const double* dsel, int64_t stride, int ncols, long long row_base,
-                       bool fusable, Run run) {
-  elfihip_ctx* ctx = h->ctx;
-  hipStream_t st = ctx->stream;
-  ELFIHIP_TRY(ensure_cap(h, n));
-  const bool full = h->host_mode ? (int64_t)h->hval.size() >= h->k : h->filled >= h->k;
-  // rows this push is expected to offer against the current threshold (batches of one distribution): n k / rows seen
-  const double expect = full ? (double)n * (double)h->k / (double)std::max<int64_t>(h->rows_seen, 1) : 1e300;
-  const bool select = !h->has_accept && (!full || expect > REJ_HEAVY);
-  h->rows_seen += n;
-  if (h->has_accept && !h->host_mode && n >= REJ_ACC_SELECT_MIN && (!full || expect > REJ_HEAVY)) {
-    // acceptance condition, state still filling up (or very many rows would qualify): mask, count, select (above)
-    ELFIHIP_TRY(reject_flush(h));
-    bool dummy = false;
-    ELFIHIP_TRY(run(nullptr, nullptr, &dummy, &dummy));
-    ELFIHIP_CHECK_HIP(ctx, h->mask_mem.reserve(((size_t)n + 2) * sizeof(double)));
-    unsigned long long* bcount = h->mask_mem.as<unsigned long long>();
-    double* masked = h->mask_mem.as<double>() + 2;
-    ELFIHIP_CHECK_HIP(ctx, hipMemsetAsync(bcount, 0, sizeof(unsigned long long), st));
-    int g = (int)((n + 255) / 256);
-    if (g > ctx->cu_count * 8) g = ctx->cu_count * 8;
-    hipLaunchKernelGGL(reject_mask_kernel, dim3(g), dim3(256), 0, st, dsel, n, stride, ncols, h->acc_dev, masked, bcount,
-                       h->acc_count);
-    ELFIHIP_TRY(mail_post(ctx, MailSrc{{bcount, nullptr, nullptr, nullptr}, {8, 0, 0, 0}, 1}));
-    ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(st));
-    const unsigned long long accepted = mail_read(ctx, 0);
-    const int64_t kb = (int64_t)accepted < h->k ? (int64_t)accepted : h->k;
-    if (kb > 0) {
-      ELFIHIP_TRY(topk_dev_impl(ctx, masked, n, 1, kb, h->cand_val, reinterpret_cast<int64_t*>(h->cand_row), true));
-      hipLaunchKernelGGL(reject_merge_kernel, dim3(1), dim3(1024), REJ_MERGE_LDS, st, merge_args(h, (int)kb, row_base));
-    }
-    return launch_status(ctx, "acceptance push: mask, select, merge");
-  }
-  if (select) {
-    // every row could enter (state still filling up) or very many would: plain distance pass, radix selection of the
-    // batch's k best (batch-local rows), merge.  What the list holds from earlier pushes is merged first -- the
-    // selection writes its result there.
-    ELFIHIP_TRY(reject_flush(h));
-    bool dummy = false;
-    ELFIHIP_TRY(run(nullptr, nullptr, &dummy, &dummy));
-    const int64_t kb = n < h->k ? n : h->k;
-    if (kb > 0) {
-      ELFIHIP_TRY(topk_dev_impl(ctx, dsel, n, stride, kb, h->cand_val, reinterpret_cast<int64_t*>(h->cand_row), true));
-      if (h->host_mode)
-        ELFIHIP_TRY(host_merge(h, (unsigned int)kb, row_base));
-      else
-        hipLaunchKernelGGL(reject_merge_kernel, dim3(1), dim3(1024), REJ_MERGE_LDS, st, merge_args(h, (int)kb, row_base));
-    }
-    h->filled = h->filled + n < h->k ? h->filled + n : h->k;
-    return launch_status(ctx, "reject_merge_kernel");
-  }
-  if (h->pending_rows + n > (int64_t)h->cap) ELFIHIP_TRY(reject_flush(h));   // (cannot happen with a merge every 8th push)
-  RejectFilter F;
-  F.thr = h->thr;
-  F.cval = h->cand_val;
-  F.crow = h->cand_row;
-  F.count = h->count;
-  F.cap = h->cap;
-  F.row_base = row_base;
-  bool filtered = false, merged = false;
-  // an acceptance threshold needs every column of a row: the separate candidate pass applies it.  A sealed list goes with
-  // the pass as its merge job; a pass that cannot take it leaves it to the standalone merge below.
-  const RejectMergeJob J = h->sealed ? sealed_job(h) : RejectMergeJob{};
-  ELFIHIP_TRY(run(h->has_accept ? nullptr : &F, h->sealed ? &J : nullptr, &filtered, &merged));
-  if ((!filtered || h->has_accept) && n > 0) {
-    int g = (int)((n + 255) / 256);
-    if (g > ctx->cu_count * 8) g = ctx->cu_count * 8;
-    hipLaunchKernelGGL(reject_filter_kernel, dim3(g), dim3(256), 0, st, dsel, n, stride, ncols, F, h->has_accept ? 1 : 0,
-                       h->acc_dev, h->acc_count);
-  }
-  if (merged)
-    h->sealed = false;
-  else
-    ELFIHIP_TRY(merge_sealed(h));
-  h->pending_rows += n;
-  // rows that ENTERED the state: every offered row without an acceptance condition; with one, the accepted rows -- the
-  // count elfihip_reject_meta reads back (until then the state keeps merging after every push, which is always correct)
-  if (!full && !h->has_accept) h->filled = h->filled + n < h->k ? h->filled + n : h->k;
-  // Merge interval: the p-th push after the state became full offers about k / p candidates (batches of one
-  // distribution), so merging every p / 2 pushes -- at most every REJ_MERGE_EVERY-th -- keeps a merge at about k / 2
-  // candidates: early on, while the threshold still falls quickly, after every push.  Host-merge states and states
-  // that are still filling merge after every push.
-  // A state that seals its lists (the merge rides on the next row pass) seals every p / 3 pushes instead: about k / 3
-  // candidates, which one wave sorts and merges inside the pass (measured at 10^6 x 32, k = 1000: lists of <= 512 cost
-  // the pass 1-2 us; lists just above 512 -- the 1024-entry sort -- 25 us more than the pass).
-  const bool seals = fusable && rej_nlists(h) == 2 && !h->has_accept;
-  ++h->armed_pushes;
-  int64_t interval = h->armed_pushes / (seals ? 3 : 2);
-  interval = interval < 1 ? 1 : (interval > REJ_MERGE_EVERY ? REJ_MERGE_EVERY : interval);
-  if (h->host_mode || !full) interval = 1;
-  if (++h->unmerged >= interval) {
-    if (!seals) return reject_flush(h);
-    // seal the open list (its merge goes with the next push's pass) and open the other one, which is empty: its own merge
-    // ran before this push's pass was queued, or in it
-    std::swap(h->cand_val, h->sealed_val);
-    std::swap(h->cand_row, h->sealed_row);
-    std::swap(h->count, h->sealed_count);
-    h->sealed = true;
-    h->unmerged = 0;
-    h->pending_rows = 0;
-  }
-  return launch_status(ctx, "distance pass with selection");
-}
-
-elfihip_ctx* reject_ctx(elfihip_reject* h) { return h->ctx; }
-
-int reject_push_rows_impl(elfihip_reject* h, int metric, const double* dX, int64_t n, int m, int64_t ldx,
-                          const double* dy, const double* daux, double p, double* dout, int64_t row_base) {
-  elfihip_ctx* ctx = h->ctx;
-  return reject_push(h, n, dout, 1, 1, (long long)row_base, true,
-                     [&](const RejectFilter* F, const RejectMergeJob* M, bool* filtered, bool* merged) {
-                       return dist_rows_dev_impl(ctx, metric, dX, n, m, ldx, dy, daux, p, dout, F, filtered, M, merged);
-                     });
-}
-
-// ---- one AdaptiveDistance batch: distances + column statistics + selection in one read (adaptive.hip) -------------
 // The j best rows of a batch's prefix sit at the head of the candidate list with batch-local row numbers: make the
 // numbers global, make the j-th distance the threshold of the pass over the rest, and let the list continue behind them.
 __global__ __launch_bounds__(256) void reject_seed_kernel(double* thr, unsigned int* count, const double* cand_val,
@@ -683,198 +550,273 @@ __global__ void reject_unseed_kernel(double* thr, unsigned int* count, const dou
   *count = 0u;
 }
 
-// h == nullptr: distances and statistics only (what the AdaptiveDistance node computes when a batch is generated).
+// ---- a batch meets the state: the policy is reject_policy.hpp's, the actions are the helpers below ----------------
+static RejMeet meet(const elfihip_reject* h) {
+  return RejMeet{h->k, h->host_mode ? (int64_t)h->hval.size() : h->filled, h->rows_seen, h->host_mode, h->has_accept};
+}
+
+// the open list as the filter of a distance pass
+static RejectFilter open_filter(const elfihip_reject* h, long long row_base) {
+  return RejectFilter{h->thr, h->cand_val, h->cand_row, h->count, h->cap, row_base};
+}
+
+// n more rows were offered to a state that takes every row (capped at k: the filter is armed from there)
+static void note_entered(elfihip_reject* h, int64_t n) { h->filled = std::min(h->filled + n, h->k); }
+
+// radix selection of the batch's k best (batch-local rows) from a strided column into the open list, and their merge
+static int select_merge(elfihip_reject* h, const double* d, int64_t n, int64_t stride, long long row_base) {
+  const int64_t kb = std::min(n, h->k);
+  if (kb <= 0) return ELFIHIP_OK;
+  ELFIHIP_TRY(topk_dev_impl(h->ctx, d, n, stride, kb, h->cand_val, reinterpret_cast<int64_t*>(h->cand_row), true));
+  return merge_list(h, (int)kb, row_base);
+}
+
+// The step after a filtered push: count it and, when the interval is over, merge the open list -- or seal it.
+static int after_filtered_push(elfihip_reject* h, int64_t n, bool full, bool seals) {
+  h->pending_rows += n;
+  // rows that ENTERED the state: every offered row without an acceptance condition; with one, the accepted rows -- the
+  // count elfihip_reject_meta reads back (until then the state keeps merging after every push, which is always correct)
+  if (!full && !h->has_accept) note_entered(h, n);
+  ++h->armed_pushes;
+  if (++h->unmerged >= rej_merge_interval(h->armed_pushes, seals, h->host_mode, full)) {
+    if (!seals) return reject_flush(h);
+    // seal the open list (its merge goes with the next push's pass) and open the other one, which is empty: its own merge
+    // ran before this push's pass was queued, or in it
+    std::swap(h->cand_val, h->sealed_val);
+    std::swap(h->cand_row, h->sealed_row);
+    std::swap(h->count, h->sealed_count);
+    h->sealed = true;
+    h->unmerged = 0;
+    h->pending_rows = 0;
+  }
+  return launch_status(h->ctx, "distance pass with selection");
+}
+
+// what a push form's distance pass reports to reject_push
+struct RejDid {
+  const double* dsel = nullptr;   // the batch's ranking distances (the last nested column), where the pass left them
+  bool filtered = false;          // the pass offered the candidates itself, as asked
+  bool merged = false;            // the pass merged the sealed list it was handed
+};
+
+// the runner of the push forms whose distances exist already: candidates come from the separate pass
+struct DistancesExist {
+  const double* dsel;
+  int operator()(const RejectFilter*, bool, const RejectMergeJob*, RejDid* did) const { return did->dsel = dsel, ELFIHIP_OK; }
+};
+
+// ---- one AdaptiveDistance batch: distances + column statistics + selection in one read (adaptive.hip) -------------
 // dwelford: the running (count, mean, M2) store of add_data, 1 + 2m doubles on the device (nullptr: no statistics).
 // dout: (n, K) or nullptr (the distances are then kept only as far as the selection needs them).
-int adaptive_push_impl(elfihip_ctx* ctx, elfihip_reject* h, const double* dX, int64_t n, int m, int64_t ldx,
-                       const double* dy, const double* dW, int K, double* dout, double* dwelford, int64_t row_base) {
-  hipStream_t st = ctx->stream;
-  const bool fused = adaptive_pass_supported(dX, m, ldx, K);
-  const size_t ns = 1 + 2 * (size_t)m;
-  const int maxp = adaptive_max_parts(ctx);
+struct AdaptiveBatch {
+  elfihip_ctx* ctx;
+  elfihip_reject* h;
+  const double *dX, *dy, *dW;
+  int64_t n, ldx;
+  int m, K;
+  double *dout, *dwelford;
+  bool fused;   // adaptive.hip's pass takes this shape (else: multiw.hip's + the two-pass statistics)
   double *partial = nullptr, *bst = nullptr;
-  if (dwelford && fused) {
-    ELFIHIP_CHECK_HIP(ctx, ctx->stat.reserve((2 * (size_t)maxp * ns + ns) * sizeof(double)));
-    partial = ctx->stat.as<double>();
-    bst = partial + 2 * (size_t)maxp * ns;
-  }
   int nparts = 0;
+  bool stats_done = false;
+
+  size_t ns() const { return 1 + 2 * (size_t)m; }
   // the pass over rows [lo, hi): distances to o (may be nullptr when fused), statistics into the next partial slots
-  auto pass = [&](int64_t lo, int64_t hi, const RejectFilter* F, bool with_acc, double* o) -> int {
+  int pass(int64_t lo, int64_t hi, const RejectFilter* F, bool with_acc, double* o) {
     const double* X = dX + lo * ldx;
-    if (fused) {
-      int np = 0;
-      ELFIHIP_TRY(adaptive_pass_impl(ctx, X, hi - lo, m, ldx, dy, dW, K, o, F, with_acc ? h->acc_dev : nullptr,
-                                     with_acc ? h->acc_count : nullptr, partial ? partial + (size_t)nparts * ns : nullptr,
-                                     &np));
-      nparts += np;
-      return ELFIHIP_OK;
-    }
-    return dist_multiw_dev_impl(ctx, X, hi - lo, m, ldx, dy, dW, K, o, nullptr, nullptr);
-  };
-  auto finish_stats = [&]() -> int {
-    if (!dwelford) return ELFIHIP_OK;
+    if (!fused) return dist_multiw_dev_impl(ctx, X, hi - lo, m, ldx, dy, dW, K, o, nullptr, nullptr);
+    int np = 0;
+    const int rc = adaptive_pass_impl(ctx, X, hi - lo, m, ldx, dy, dW, K, o, F, with_acc ? h->acc_dev : nullptr,
+                                      with_acc ? h->acc_count : nullptr, partial ? partial + (size_t)nparts * ns() : nullptr, &np);
+    nparts += np;
+    return rc;
+  }
+  int finish_stats() {   // (once per batch, wherever the route has room for it)
+    if (!dwelford || stats_done) return ELFIHIP_OK;
+    stats_done = true;
     if (fused) return adaptive_stats_finish(ctx, partial, nparts, m, bst, dwelford);
     return welford_dev_impl(ctx, dX, n, m, ldx, dwelford);   // (odd m, wide rows, many weight vectors: the two-pass form)
-  };
+  }
   // distances the selection can read when the caller keeps none
-  auto scratch_out = [&](int64_t rows, double** o) -> int {
+  int scratch_out(int64_t rows, double** o) {
     ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((size_t)rows * K * sizeof(double)));
     *o = ctx->out.as<double>();
     return ELFIHIP_OK;
-  };
+  }
+};
+
+// RejRoute::Provisional (the lists are flushed).  An SMC round starts from an empty state (samplers.py:474-487): every row
+// could enter, so the kernel has no threshold to filter with, and a radix selection over all n distances costs as much as
+// the pass itself (10^7 x 3: 0.65 ms).  Instead: the j-th smallest distance T of a PREFIX of s rows (rej_provisional) is
+// almost surely above the batch's k-th smallest, and then the prefix's j best + the rows of the rest below T -- about j n / s
+// -- hold the batch's k best.  That is CHECKED (the list's length is read back); if not, all n distances are selected from.
+static int push_provisional(elfihip_reject* h, int64_t n, long long row_base, AdaptiveBatch& B) {
+  elfihip_ctx* ctx = h->ctx;
+  hipStream_t st = ctx->stream;
+  const int K = B.K;
+  const RejProv P = rej_provisional(n, h->k, (int64_t)h->cap);
+  double* pre = B.dout;
+  if (!pre) ELFIHIP_TRY(B.scratch_out(P.s, &pre));
+  ELFIHIP_TRY(B.pass(0, P.s, nullptr, false, pre));
+  // (the prefix's selection as ONE resident launch: its barrier time-out flag is read back with the list's length below,
+  // and a time-out takes the route of a failed check)
+  ELFIHIP_TRY(topk_dev_impl(ctx, pre + (K - 1), P.s, K, P.j, h->cand_val, reinterpret_cast<int64_t*>(h->cand_row), false));
+  const void* sel_err_dev = topk_resident_err_dev(ctx);   // (NULL: the nine-launch form ran -- nothing to time out)
+  hipLaunchKernelGGL(reject_seed_kernel, dim3(1), dim3(256), 0, st, h->thr, h->count, h->cand_val, h->cand_row, (int)P.j,
+                     row_base);
+  const RejectFilter F = open_filter(h, row_base + P.s);
+  ELFIHIP_TRY(B.pass(P.s, n, &F, false, B.dout ? B.dout + P.s * K : nullptr));
+  // the list's length and the selection's time-out flag in ONE read-back
+  ELFIHIP_TRY(mail_post(ctx, MailSrc{{h->count, sel_err_dev ? sel_err_dev : h->count, nullptr, nullptr}, {4, 4, 0, 0}, 2}));
+  // An EMPTY state (every SMC round starts with one) is merged -- and the batch's statistics are finished -- BEFORE the
+  // verdict is known: the host waits for the mail kernel alone (mail_wait), the device works on while it wakes up (a stream
+  // synchronisation here left it idle for 20-30 us per round), and a wrong merge is undone by emptying the state again.
+  const bool early = !h->host_mode && h->filled == 0;
+  if (early) {
+    // (the merge applies the verdict's bounds on the list's length itself: a list that fails them -- sorted input: a
+    // handful of candidates, or every row of the batch -- is not touched, nor is the state)
+    launch_merge(h, false, -1, 0, (unsigned int)h->k, (unsigned int)P.c_hi);
+    ELFIHIP_TRY(launch_status(ctx, "reject_merge_kernel"));
+    ELFIHIP_TRY(B.finish_stats());
+    ELFIHIP_TRY(mail_wait(ctx));
+  } else {
+    ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(st));
+  }
+  const unsigned int c = (unsigned int)mail_read(ctx, 0);
+  const unsigned int sel_err = sel_err_dev ? (unsigned int)mail_read(ctx, 1) : 0u;
+  if (sel_err == 0 && (int64_t)c >= h->k && (int64_t)c <= P.c_hi) {
+    if (!early) ELFIHIP_TRY(merge_list(h, -1, 0));
+  } else {
+    // the prefix did not represent the batch: selection over all n distances (recomputed when the caller kept none)
+    if (early) launch_init(h);   // (only a timed-out selection with a list of plausible length has been merged)
+    hipLaunchKernelGGL(reject_unseed_kernel, dim3(1), dim3(1), 0, st, h->thr, h->count, h->best_val,
+                       (int)std::min<int64_t>(h->k, REJ_MAX_K));
+    if (h->host_mode) {
+      const double thr = (int64_t)h->hval.size() >= h->k ? h->hval[h->k - 1] : std::numeric_limits<double>::infinity();
+      ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(h->thr, &thr, sizeof thr, hipMemcpyHostToDevice, st));
+      ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(st));
+    }
+    double* all = B.dout;
+    if (!all) {
+      ELFIHIP_TRY(B.scratch_out(n, &all));
+      ELFIHIP_TRY(dist_multiw_dev_impl(ctx, B.dX, n, B.m, B.ldx, B.dy, B.dW, K, all, nullptr, nullptr));
+    }
+    ELFIHIP_TRY(select_merge(h, all + (K - 1), n, K, row_base));
+  }
+  h->filled = h->k;
+  h->unmerged = 0;
+  h->pending_rows = 0;
+  return ELFIHIP_OK;
+}
+
+// Fold a batch into the state: the one walk of every push form.  run(F, with_accept, M, &did) launches the form's distance
+// pass on the context's stream and reports in did.  F: offer the rows below *F->thr to this list (nullptr: distances only)
+// -- with_accept: only rows within the state's acceptance thresholds, so a pass that cannot apply those must not filter;
+// M: a sealed list to merge beside the pass, if it can.  Ranking distances: the last of `ncols` nested columns, `stride`
+// apart.  fusable: the pass can take a merge job.  prefix: the form can run its pass over a part of the batch (provisional route).
+template <class Run>
+static int reject_push(elfihip_reject* h, int64_t n, int64_t stride, int ncols, long long row_base, bool fusable, Run run,
+                       AdaptiveBatch* prefix = nullptr) {
+  elfihip_ctx* ctx = h->ctx;
+  hipStream_t st = ctx->stream;
+  ELFIHIP_TRY(ensure_cap(h, n));
+  const RejMeet S = meet(h);
+  const RejRoute route = rej_route(S, n, prefix != nullptr);
+  h->rows_seen += n;
+  int g = (int)((n + 255) / 256);   // grid of the candidate / mask pass
+  if (g > ctx->cu_count * 8) g = ctx->cu_count * 8;
+  RejDid did;
+  if (route != RejRoute::Filter) {
+    // What the open list holds from earlier pushes is merged first -- the selection writes its result there.
+    ELFIHIP_TRY(reject_flush(h));
+    if (route == RejRoute::Provisional) return push_provisional(h, n, row_base, *prefix);
+    ELFIHIP_TRY(run(nullptr, false, nullptr, &did));
+    if (route == RejRoute::Select) {
+      note_entered(h, n);
+      return select_merge(h, did.dsel, n, stride, row_base);
+    }
+    // an acceptance threshold and no useful k-th distance yet: mask, count, select (see reject_mask_kernel)
+    ELFIHIP_CHECK_HIP(ctx, h->mask_mem.reserve(((size_t)n + 2) * sizeof(double)));
+    unsigned long long* bcount = h->mask_mem.as<unsigned long long>();
+    double* masked = h->mask_mem.as<double>() + 2;
+    ELFIHIP_CHECK_HIP(ctx, hipMemsetAsync(bcount, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(reject_mask_kernel, dim3(g), dim3(256), 0, st, did.dsel, n, stride, ncols, h->acc_dev, masked,
+                       bcount, h->acc_count);
+    ELFIHIP_TRY(mail_post(ctx, MailSrc{{bcount, nullptr, nullptr, nullptr}, {8, 0, 0, 0}, 1}));
+    ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(st));
+    const int64_t kb = std::min((int64_t)mail_read(ctx, 0), h->k);
+    if (kb > 0) {
+      ELFIHIP_TRY(topk_dev_impl(ctx, masked, n, 1, kb, h->cand_val, reinterpret_cast<int64_t*>(h->cand_row), true));
+      launch_merge(h, false, (int)kb, row_base);
+    }
+    return launch_status(ctx, "acceptance push: mask, select, merge");
+  }
+  // (never fires while rej_list_size and rej_merge_interval share REJ_MERGE_EVERY; kept: an overflow shows only at result())
+  if (h->pending_rows + n > (int64_t)h->cap) ELFIHIP_TRY(reject_flush(h));
+  const RejectFilter F = open_filter(h, row_base);
+  const RejectMergeJob J = h->sealed ? merge_fields<RejectMergeJob>(h, true) : RejectMergeJob{};
+  ELFIHIP_TRY(run(&F, h->has_accept, h->sealed ? &J : nullptr, &did));
+  // An acceptance threshold needs every column of a row.  A pass that reads them all applies it itself (the fused adaptive
+  // pass); after any other, and after a pass that does not filter, the separate candidate pass lists the rows.
+  if (!did.filtered && n > 0)
+    hipLaunchKernelGGL(reject_filter_kernel, dim3(g), dim3(256), 0, st, did.dsel, n, stride, ncols, F,
+                       h->has_accept ? 1 : 0, h->acc_dev, h->acc_count);
+  if (did.merged) h->sealed = false;
+  ELFIHIP_TRY(merge_sealed(h));   // (a pass that could not take the job)
+  // only the row pushes seal -- theirs is the one pass that takes a merge job, and it filters only without acceptance
+  return after_filtered_push(h, n, S.full(), fusable && rej_nlists(h) == 2 && !h->has_accept);
+}
+
+elfihip_ctx* reject_ctx(elfihip_reject* h) { return h->ctx; }
+
+int reject_push_rows_impl(elfihip_reject* h, int metric, const double* dX, int64_t n, int m, int64_t ldx,
+                          const double* dy, const double* daux, double p, double* dout, int64_t row_base) {
+  return reject_push(h, n, 1, 1, (long long)row_base, true,
+                     [&](const RejectFilter* F, bool with_accept, const RejectMergeJob* M, RejDid* did) {
+    did->dsel = dout;
+    return dist_rows_dev_impl(h->ctx, metric, dX, n, m, ldx, dy, daux, p, dout, with_accept ? nullptr : F, &did->filtered, M,
+                              &did->merged);
+  });
+}
+
+// h == nullptr: distances and statistics only (what the AdaptiveDistance node computes when a batch is generated).
+int adaptive_push_impl(elfihip_ctx* ctx, elfihip_reject* h, const double* dX, int64_t n, int m, int64_t ldx,
+                       const double* dy, const double* dW, int K, double* dout, double* dwelford, int64_t row_base) {
+  AdaptiveBatch B{ctx, h, dX, dy, dW, n, ldx, m, K, dout, dwelford, adaptive_pass_supported(dX, m, ldx, K)};
+  if (dwelford && B.fused) {
+    const size_t slots = 2 * (size_t)adaptive_max_parts(ctx) * B.ns();
+    ELFIHIP_CHECK_HIP(ctx, ctx->stat.reserve((slots + B.ns()) * sizeof(double)));
+    B.partial = ctx->stat.as<double>();
+    B.bst = B.partial + slots;
+  }
+  double* o = dout;
   if (!h) {
-    double* o = dout;
-    if (!fused && !o) ELFIHIP_TRY(scratch_out(n, &o));
-    ELFIHIP_TRY(pass(0, n, nullptr, false, o));
-    return finish_stats();
+    if (!B.fused && !o) ELFIHIP_TRY(B.scratch_out(n, &o));
+    ELFIHIP_TRY(B.pass(0, n, nullptr, false, o));
+    return B.finish_stats();
   }
   ELFIHIP_REQUIRE(ctx, h->acc_ncols == 0 || h->acc_ncols == K, "%d acceptance thresholds but K = %d nested distances",
                   h->acc_ncols, K);
-  ELFIHIP_TRY(merge_sealed(h));   // (a list sealed by a row push: this pass takes no merge job)
+  // This form merges a list sealed by a row push FIRST (its pass takes no merge job), and so before the lists may grow;
+  // the other forms leave it to reject_push, behind their pass.  Either order is exact.
+  ELFIHIP_TRY(merge_sealed(h));
   ELFIHIP_TRY(ensure_cap(h, n));
-  const bool full = h->host_mode ? (int64_t)h->hval.size() >= h->k : h->filled >= h->k;
-  const bool acc_select = h->has_accept && !h->host_mode && n >= REJ_ACC_SELECT_MIN &&
-                          (!full || (double)n * (double)h->k / (double)std::max<int64_t>(h->rows_seen, 1) > REJ_HEAVY);
-  if (!fused || acc_select) {
-    // distances (and, fused, the statistics) first, then the state's own candidate pass over them
-    double* o = dout;
-    if (!o) ELFIHIP_TRY(scratch_out(n, &o));
-    ELFIHIP_TRY(pass(0, n, nullptr, false, o));
-    ELFIHIP_TRY(reject_push(h, n, o + (K - 1), K, K, (long long)row_base, false,
-                            [&](const RejectFilter*, const RejectMergeJob*, bool* filtered, bool*) {
-      *filtered = false;
-      return ELFIHIP_OK;
-    }));
-    return finish_stats();
+  if (!B.fused || rej_route(meet(h), n, true) == RejRoute::AcceptSelect) {
+    // the pass cannot serve the route: distances (and, fused, the statistics) first, then the state's own passes over them
+    if (!o) ELFIHIP_TRY(B.scratch_out(n, &o));
+    ELFIHIP_TRY(B.pass(0, n, nullptr, false, o));
+    ELFIHIP_TRY(reject_push(h, n, K, K, (long long)row_base, false, DistancesExist{o + (K - 1)}));
+    return B.finish_stats();
   }
-  const double expect = full ? (double)n * (double)h->k / (double)std::max<int64_t>(h->rows_seen, 1) : 1e300;
-  const bool select = !h->has_accept && (!full || expect > REJ_HEAVY);
-  h->rows_seen += n;
-  auto merge_list = [&](int ncand, long long row_offset) -> int {
-    if (h->host_mode) return host_merge(h, ncand < 0 ? ~0u : (unsigned int)ncand, row_offset);
-    hipLaunchKernelGGL(reject_merge_kernel, dim3(1), dim3(1024), REJ_MERGE_LDS, st, merge_args(h, ncand, row_offset));
-    return launch_status(ctx, "reject_merge_kernel");
-  };
-  if (select && !full && n >= REJ_PROV_MIN_ROWS && 64 * h->k <= n) {
-    // A large first batch (an SMC round starts from an empty state: samplers.py:474-487).  Every row could enter, so
-    // there is no threshold for the kernel to filter with, and a radix selection over all n distances costs as much
-    // as the pass itself (10^7 x 3: 0.65 ms).  Instead: the j-th smallest distance T of a PREFIX of s rows (j a few
-    // standard deviations -- five -- above the k s / n of the batch's k best that fall into the prefix of exchangeable rows) is
-    // with overwhelming probability above the batch's k-th smallest, and then the prefix's j best + the rows of the
-    // rest below T -- about j n / s of them -- contain the batch's k best.  That is CHECKED (the list's length is read
-    // back): if fewer than k rows qualified (the rows were not exchangeable: sorted input), or far too many, the
-    // selection of all n distances runs instead.  Exact either way.
-    ELFIHIP_TRY(reject_flush(h));
-    // (s = n / 16: j n / s = 1700 +- 160 candidates for k = 1000, i.e. two 1024-chunks of the merge; with n / 32 -- rounds 4-5 --
-    // they were 2050 +- 250, a third chunk every other round)
-    const int64_t s = std::min<int64_t>(std::max<int64_t>(n / 16, 16384), n / 2);
-    const double mu = (double)h->k * (double)s / (double)n;
-    int64_t j = (int64_t)std::ceil(mu + 5.0 * std::sqrt(mu) + 4.0);
-    if (j > h->k) j = h->k;
-    double* pre = dout;
-    if (!pre) ELFIHIP_TRY(scratch_out(s, &pre));
-    ELFIHIP_TRY(pass(0, s, nullptr, false, pre));
-    // (the prefix's selection as ONE resident launch: its barrier time-out flag is read back with the list's length below,
-    // and a time-out takes the route of a failed check)
-    ELFIHIP_TRY(topk_dev_impl(ctx, pre + (K - 1), s, K, j, h->cand_val, reinterpret_cast<int64_t*>(h->cand_row), false));
-    const void* sel_err_dev = topk_resident_err_dev(ctx);   // (NULL: the nine-launch form ran -- nothing to time out)
-    hipLaunchKernelGGL(reject_seed_kernel, dim3(1), dim3(256), 0, st, h->thr, h->count, h->cand_val, h->cand_row, (int)j,
-                       (long long)row_base);
-    RejectFilter F;
-    F.thr = h->thr;
-    F.cval = h->cand_val;
-    F.crow = h->cand_row;
-    F.count = h->count;
-    F.cap = h->cap;
-    F.row_base = (long long)row_base + s;
-    ELFIHIP_TRY(pass(s, n, &F, false, dout ? dout + s * K : nullptr));
-    // the list's length and the selection's time-out flag in ONE read-back
-    ELFIHIP_TRY(mail_post(ctx, MailSrc{{h->count, sel_err_dev ? sel_err_dev : h->count, nullptr, nullptr}, {4, 4, 0, 0}, 2}));
-    // An EMPTY state (every SMC round starts with one) is merged -- and the batch's statistics are finished -- BEFORE the
-    // verdict is known: the host waits for the mail kernel alone (mail_wait), the device works on while it wakes up, and a
-    // wrong merge is undone by emptying the state again.  (Rounds 4-5 synchronised the stream here: 20-30 us of idle device
-    // per round between the pass and the merge.)
-    const bool early = !h->host_mode && h->filled == 0;
-    bool stats_done = false;
-    const int64_t c_hi = std::min<int64_t>(std::max<int64_t>(REJ_PROV_MAX_CAND, 64 * j), (int64_t)h->cap);
-    if (early) {
-      // (the merge applies the verdict's bounds on the list's length itself: a list that fails them -- sorted input: a
-      // handful of candidates, or every row of the batch -- is not touched, nor is the state)
-      RejArgs A = merge_args(h, -1, 0);
-      A.ok_lo = (unsigned int)h->k;
-      A.ok_hi = (unsigned int)c_hi;
-      hipLaunchKernelGGL(reject_merge_kernel, dim3(1), dim3(1024), REJ_MERGE_LDS, st, A);
-      ELFIHIP_TRY(launch_status(ctx, "reject_merge_kernel"));
-      ELFIHIP_TRY(finish_stats());
-      stats_done = true;
-      ELFIHIP_TRY(mail_wait(ctx));
-    } else {
-      ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(st));
-    }
-    const unsigned int c = (unsigned int)mail_read(ctx, 0);
-    const unsigned int sel_err = sel_err_dev ? (unsigned int)mail_read(ctx, 1) : 0u;
-    if (sel_err == 0 && (int64_t)c >= h->k && (int64_t)c <= c_hi) {
-      if (!early) ELFIHIP_TRY(merge_list(-1, 0));
-    } else {
-      // the prefix did not represent the batch: selection over all n distances (recomputed when the caller kept none)
-      if (early)   // the state as reject_reset leaves it (only a timed-out selection with a list of plausible length has been merged)
-        hipLaunchKernelGGL(reject_init_kernel, dim3((unsigned)((std::min<int64_t>(h->k, REJ_MAX_K) + 255) / 256)), dim3(256), 0, st,
-                           h->best_val, h->best_row, h->thr, h->count, h->sealed_count, h->status, h->acc_count,
-                           (int)std::min<int64_t>(h->k, REJ_MAX_K));
-      hipLaunchKernelGGL(reject_unseed_kernel, dim3(1), dim3(1), 0, st, h->thr, h->count, h->best_val,
-                         (int)std::min<int64_t>(h->k, REJ_MAX_K));
-      if (h->host_mode) {
-        const double inf = std::numeric_limits<double>::infinity();
-        const double thr = (int64_t)h->hval.size() >= h->k ? h->hval[h->k - 1] : inf;
-        ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(h->thr, &thr, sizeof thr, hipMemcpyHostToDevice, st));
-        ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(st));
-      }
-      double* all = dout;
-      if (!all) {
-        ELFIHIP_TRY(scratch_out(n, &all));
-        ELFIHIP_TRY(dist_multiw_dev_impl(ctx, dX, n, m, ldx, dy, dW, K, all, nullptr, nullptr));
-      }
-      const int64_t kb = n < h->k ? n : h->k;
-      ELFIHIP_TRY(topk_dev_impl(ctx, all + (K - 1), n, K, kb, h->cand_val, reinterpret_cast<int64_t*>(h->cand_row), true));
-      ELFIHIP_TRY(merge_list((int)kb, (long long)row_base));
-    }
-    h->filled = h->k;
-    h->unmerged = 0;
-    h->pending_rows = 0;
-    return stats_done ? ELFIHIP_OK : finish_stats();
-  }
-  if (select) {
-    // (as reject_push: the state is still filling up, or very many rows would qualify) plain pass, radix selection of
-    // the batch's k best, merge
-    ELFIHIP_TRY(reject_flush(h));
-    double* o = dout;
-    if (!o) ELFIHIP_TRY(scratch_out(n, &o));
-    ELFIHIP_TRY(pass(0, n, nullptr, false, o));
-    const int64_t kb = n < h->k ? n : h->k;
-    ELFIHIP_TRY(topk_dev_impl(ctx, o + (K - 1), n, K, kb, h->cand_val, reinterpret_cast<int64_t*>(h->cand_row), true));
-    ELFIHIP_TRY(merge_list((int)kb, (long long)row_base));
-    h->filled = h->filled + n < h->k ? h->filled + n : h->k;
-    return finish_stats();
-  }
-  // the kernel lists the acceptable rows below the state's k-th distance itself
-  if (h->pending_rows + n > (int64_t)h->cap) ELFIHIP_TRY(reject_flush(h));
-  RejectFilter F;
-  F.thr = h->thr;
-  F.cval = h->cand_val;
-  F.crow = h->cand_row;
-  F.count = h->count;
-  F.cap = h->cap;
-  F.row_base = (long long)row_base;
-  ELFIHIP_TRY(pass(0, n, &F, h->has_accept, dout));
-  h->pending_rows += n;
-  if (!full && !h->has_accept) h->filled = h->filled + n < h->k ? h->filled + n : h->k;
-  ++h->armed_pushes;
-  int64_t interval = h->armed_pushes / 2;
-  interval = interval < 1 ? 1 : (interval > REJ_MERGE_EVERY ? REJ_MERGE_EVERY : interval);
-  if (h->host_mode || !full) interval = 1;
-  if (++h->unmerged >= interval) ELFIHIP_TRY(reject_flush(h));
-  return finish_stats();
+  ELFIHIP_TRY(reject_push(h, n, K, K, (long long)row_base, false,
+                          [&](const RejectFilter* F, bool with_accept, const RejectMergeJob*, RejDid* did) {
+    // the kernel lists the acceptable rows below the k-th distance itself; the selection reads distances kept somewhere
+    if (!F && !o) ELFIHIP_TRY(B.scratch_out(n, &o));
+    did->dsel = o ? o + (K - 1) : nullptr;
+    did->filtered = F != nullptr;
+    return B.pass(0, n, F, with_accept, o);
+  }, &B));
+  return B.finish_stats();
 }
 
 }  // namespace elfihip
@@ -964,10 +906,11 @@ int elfihip_reject_push_multiw_dev(elfihip_reject* h, const double* dX, int64_t 
   ELFIHIP_REQUIRE(ctx, n >= 0 && K >= 1 && (n == 0 || dout), "the batch's distances need a destination (dout)");
   DeviceGuard g(ctx->device);
   // nested distances are ranked by their LAST column (samplers.py:233)
-  return reject_push(h, n, dout ? dout + (K - 1) : nullptr, K, K, (long long)row_base, false,
-                     [&](const RejectFilter* F, const RejectMergeJob*, bool* filtered, bool*) {
-                       return dist_multiw_dev_impl(ctx, dX, n, m, ldx, dy, dW, K, dout, F, filtered);
-                     });
+  return reject_push(h, n, K, K, (long long)row_base, false,
+                     [&](const RejectFilter* F, bool with_accept, const RejectMergeJob*, RejDid* did) {
+    did->dsel = dout ? dout + (K - 1) : nullptr;
+    return dist_multiw_dev_impl(ctx, dX, n, m, ldx, dy, dW, K, dout, with_accept ? nullptr : F, &did->filtered);
+  });
 }
 
 int elfihip_reject_push_dev(elfihip_reject* h, const double* dD, int64_t n, int64_t stride, int64_t row_base) {
@@ -975,11 +918,7 @@ int elfihip_reject_push_dev(elfihip_reject* h, const double* dD, int64_t n, int6
   elfihip_ctx* ctx = h->ctx;
   ELFIHIP_REQUIRE(ctx, n >= 0 && stride >= 1 && (n == 0 || dD), "bad arguments");
   DeviceGuard g(ctx->device);
-  return reject_push(h, n, dD, stride, 1, (long long)row_base, false,
-                     [&](const RejectFilter*, const RejectMergeJob*, bool* filtered, bool*) {
-    *filtered = false;   // the distances exist already: candidates come from the separate pass
-    return ELFIHIP_OK;
-  });
+  return reject_push(h, n, stride, 1, (long long)row_base, false, DistancesExist{dD});
 }
 
 int elfihip_reject_push_kept(elfihip_reject* h, uint64_t epoch, int64_t row_base) {
@@ -995,14 +934,8 @@ int elfihip_reject_push_kept(elfihip_reject* h, uint64_t epoch, int64_t row_base
                   h->acc_ncols, K);
   if (n == 0) return ELFIHIP_OK;
   DeviceGuard g(ctx->device);
-  const double* dD = ctx->keep.as<double>();
-  ELFIHIP_TRY(reject_push(h, n, dD + (K - 1), K, K, (long long)row_base, false,
-                          [&](const RejectFilter*, const RejectMergeJob*, bool* filtered, bool*) {
-    *filtered = false;
-    return ELFIHIP_OK;
-  }));
   // the kept copy belongs to the context: what reads it is queued before the next distance call can replace it (same stream)
-  return ELFIHIP_OK;
+  return reject_push(h, n, K, K, (long long)row_base, false, DistancesExist{ctx->keep.as<double>() + (K - 1)});
 }
 
 int elfihip_reject_state_dev(elfihip_reject* h, double** dvals, int64_t** drows) {
@@ -1101,11 +1034,7 @@ int elfihip_reject_push(elfihip_reject* h, const double* D, int64_t n, int ncols
   ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(bytes));
   double* dD = ctx->in.as<double>();
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dD, D, bytes, hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(reject_push(h, n, dD + (ncols - 1), ncols, ncols, (long long)row_base, false,
-                          [&](const RejectFilter*, const RejectMergeJob*, bool* filtered, bool*) {
-    *filtered = false;
-    return ELFIHIP_OK;
-  }));
+  ELFIHIP_TRY(reject_push(h, n, ncols, ncols, (long long)row_base, false, DistancesExist{dD + (ncols - 1)}));
   // the staging buffer is the context's: merged before the next call may overwrite it (selection route: already done)
   ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ELFIHIP_OK;
