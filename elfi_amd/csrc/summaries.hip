@@ -112,7 +112,8 @@ __global__ __launch_bounds__(256) void row_summary_kernel(SumArgs S) {
       load_tile<8>(A, tile, row0, rows);
     }
     __syncthreads();
-    const int red_len = KIND == SUM_AUTOCOV ? L - S.lag : (KIND == SUM_MA2 ? L - 3 : L);  // longest reduction
+    // longest reduction (MA2: the n_obs values of x the eight lanes of a row form in place, two halves of 64)
+    const int red_len = KIND == SUM_AUTOCOV ? L - S.lag : (KIND == SUM_MA2 ? L - 2 : L);
     if (PIPE || red_len <= 128) {  // the pipelined kernel is only launched for L <= 128
       // eight lanes per row (np_pairwise8): 16 rows at a time with 128 threads
       const int j = tid & 7, gpr = blockDim.x >> 3;

@@ -105,7 +105,20 @@ int elfihip_timer_stop(elfihip_ctx* ctx, float* elapsed_ms); /* synchronises on 
  * (1e-13: SciPy's np.dot order is its BLAS's); wider rows are summed by a butterfly (1e-14).
  */
 
-/* X row-major (n, m) with leading dimension ldx >= m (doubles). */
+/* X row-major (n, m) with leading dimension ldx >= m (doubles).
+ *
+ * Layout contract of the _dev row entry points (elfihip_dist_rows_dev, _dist_multiw_dev, _reject_push_rows_dev,
+ * _reject_push_multiw_dev, _adaptive_push_dev, _row_summary_dev, _ma2_distance_dev, _welford_update_dev,
+ * _weighted_var_dev): ANY ldx >= m and ANY 8-byte aligned dX are correct -- a view of a wider device matrix needs no
+ * copy -- and so is any 8-byte aligned result pointer (dout, and a (n, K) dout at any such address: the kernels that write
+ * results in 16-byte pieces test dout themselves and store single doubles otherwise).  The fast paths (16-byte row loads:
+ * the narrow, pipelined, LDS-DMA, matrix-core Mahalanobis and fused adaptive kernels) need m even, ldx even and dX 16-byte
+ * aligned; every other layout takes the 8-byte-load kernels, whose results are the same up to the documented tolerance of
+ * the metric (bit for bit for the exact metrics).  Two forms address a tile's rows with 32-bit offsets and are taken only
+ * below a pitch limit: the LDS-DMA row form for ldx <= 2^21, the matrix-core Mahalanobis kernels for ldx < 2^22; above,
+ * the register-staged forms run.  elfihip_dist_cols_dev reads and writes two rows per lane when ldc is even and dC and dout
+ * are both 16-byte aligned, and one row per lane otherwise.  tests/test_device_layouts_gpu.py runs every one of them at
+ * packed, even, odd and offset layouts. */
 int elfihip_dist_rows(elfihip_ctx* ctx, int metric, const double* X, int64_t n, int m, int64_t ldx,
                       const double* y, const double* aux, double p, double* out);
 int elfihip_dist_rows_dev(elfihip_ctx* ctx, int metric, const double* dX, int64_t n, int m,

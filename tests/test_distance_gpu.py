@@ -165,7 +165,9 @@ def test_shapes_vs_oracle(hip_ctx, n, m):
 def test_mahalanobis_shapes_vs_oracle(hip_ctx, n, m):
     """sqrt(d' VI d): the matrix-core kernel (m <= 64, every padding case of its 4-deep / 16-wide tiles) and the
     lane-per-row kernel beyond, against SciPy's cdist through the oracle.  VI is a proper inverse covariance with
-    negative off-diagonal entries, so the quadratic form's terms cancel."""
+    negative off-diagonal entries, so the quadratic form's terms cancel.  The view with a row pitch of m + 3 goes through the
+    host form, which stages it into a packed buffer: it tests the staging copy; the kernels at a caller's pitch are in
+    tests/test_device_layouts_gpu.py and tests/test_mahalanobis_widths_gpu.py."""
     import elfi_amd
     rs = np.random.RandomState(77 * m + n)
     Z = rs.randn(4 * m + 5, m) @ rs.randn(m, m)
@@ -180,6 +182,8 @@ def test_mahalanobis_shapes_vs_oracle(hip_ctx, n, m):
 
 
 def test_strided_rows_and_dtypes(hip_ctx):
+    """Views and other dtypes through the host form: the staging copy (hipMemcpy2D into a packed buffer) and the cast, not
+    the kernels' own pitch handling -- that is tests/test_device_layouts_gpu.py."""
     import elfi_amd
     rs = np.random.RandomState(5)
     big = rs.randn(777, 40)
@@ -415,8 +419,9 @@ def test_config4_shape_adaptive_round(hip_ctx):
 def test_lds_dma_row_stream_equals_the_register_pipeline_and_cdist(hip_ctx, m):
     """The LDS-DMA form of the row stream (csrc/distance.hip: dist_rows_dma_kernel, the default for 16 / 32 / 64 summaries)
     against SciPy's cdist and against the register-staged form it replaces, bit for bit: ragged and tiny n (slots of 64 / 32
-    rows, rings of four), weights, every light metric, a row pitch that is not the width, and the sampler state fed by the
-    same pass (the fused selection sees the same distances)."""
+    rows, rings of four), weights, every light metric, a host view whose row pitch is not the width (the host form stages
+    it packed: that leg tests the staging copy; the DMA kernel at a real pitch is tests/test_device_layouts_gpu.py), and the
+    sampler state fed by the same pass (the fused selection sees the same distances)."""
     import elfi_amd
     rs = np.random.RandomState(500 + m)
     y, w = rs.randn(1, m), rs.uniform(0.1, 3, m)
@@ -466,8 +471,9 @@ def test_narrow_row_kernels_equal_the_tile_kernels_and_cdist(hip_ctx, m):
     """Round 6: rows of 2 or 4 summaries (configs[0]'s own shape) are owned by lanes -- U 16-/32-byte loads per lane, no LDS
     (csrc/distance.hip: dist_rows_narrow_kernel, csrc/mahalanobis.hip: dist_rows_mahalanobis_narrow_kernel, csrc/multiw.hip: dist_multiw_narrow_kernel) -- against
     SciPy's cdist and against the tile kernels they replace (form 1), bit for bit: every metric, weights, ragged and tiny n
-    on both sides of the 1024-row granule, a row pitch that is not the width, the K-weight form, and the sampler state fed
-    by the same pass."""
+    on both sides of the 1024-row granule, a host view whose row pitch is not the width (staged packed by the host form: the
+    staging copy; the kernels at a real pitch are in tests/test_device_layouts_gpu.py), the K-weight form, and the sampler
+    state fed by the same pass."""
     import elfi_amd
     rs = np.random.RandomState(900 + m)
     y, w = rs.randn(1, m), rs.uniform(0.1, 3, m)
