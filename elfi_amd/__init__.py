@@ -32,7 +32,7 @@ from .bolfi import HipBOLFI, hip_bolfi_class  # noqa: F401
 from . import chains, fused_models, multistart, priors  # noqa: F401
 from .maxvar_acquisition import HipExpIntVar, HipMaxVar, HipRandMaxVar  # noqa: F401
 from .synlik import (HipBSL, hip_bsl_class, log_SL_stdev, robust_likelihood, select_penalty,  # noqa: F401
-                     standard_likelihood, syn_loglik, unbiased_likelihood)
+                     semi_loglik, semiparametric_likelihood, standard_likelihood, syn_loglik, unbiased_likelihood)
 
 
 

@@ -22,8 +22,9 @@
 //              quadratic form.  A non-positive pivot or a non-finite value gives -inf.
 // Whitening (rows -> rows W^T, y -> W y) is a launch of its own in front.
 // Determinism: no atomics, fixed order everywhere; a group's result does not depend on G.
+// The shape of the LDS buffers, the MFMA step and the factorisation are shared with semibsl.hip (syn_gram.hpp).
 #include "common.hpp"
-#include "mfma_f64.hpp"
+#include "syn_gram.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -31,9 +32,6 @@
 #pragma clang fp contract(off)
 
 namespace elfihip {
-
-constexpr int SL_RC = 32;        // rows per staged chunk (8 MFMA steps)
-constexpr int SL_MAX_M = 64;
 
 struct SynArgs {
   const double* X;          // (G n, m), pitch ldx
@@ -51,12 +49,10 @@ struct SynArgs {
 };
 
 template <int T>
-struct SynShape {
-  static constexpr int MP = 16 * T;                          // padded m
-  static constexpr int SP = (MP % 32 == 0) ? MP + 16 : MP;   // pitch of the staged rows: pitch mod 32 == 16, so the two
-                                                             // rows a half-wave reads fall into different banks
-  static constexpr int LP = MP + 1;                          // pitch of the m x m matrices
-  static constexpr int NT = (T * T + 3) / 4;                 // tiles per wave
+struct SynShape : GramShape<T> {
+  using GramShape<T>::MP;
+  using GramShape<T>::SP;
+  using GramShape<T>::LP;
   static constexpr int DOUBLES = SL_RC * SP + MP * LP + (MP + 1) * LP + 6 * MP;
 };
 
@@ -128,23 +124,7 @@ __device__ void synlik_finish(const SynArgs& A, int g, int kb, int64_t np, doubl
       L[m * LP + tid] = v;
     }
     __syncthreads();
-    bool ok = true;
-    for (int j = 0; j < m; ++j) {
-      const double piv = L[j * LP + j];   // the same word for every thread: the branch is uniform
-      if (!(piv > 0.0)) {
-        ok = false;
-        break;
-      }
-      const double d = sqrt(piv);         // (nobody writes L[j][j] from here on)
-      if (tid == 0) dg[j] = d;
-      if (j + 1 + tid <= m) L[(j + 1 + tid) * LP + j] = L[(j + 1 + tid) * LP + j] / d;
-      __syncthreads();
-      for (int i = j + 1 + ty; i <= m; i += 16) {
-        const double lij = L[i * LP + j];
-        for (int k = j + 1 + tx; k <= i && k < m; k += 16) L[i * LP + k] -= lij * L[k * LP + j];
-      }
-      __syncthreads();
-    }
+    const bool ok = chol_extra_row<LP>(L, dg, m);
     if (tid == 0) {
       double ll = -INFINITY;
       if (ok) {
@@ -246,14 +226,7 @@ __global__ __launch_bounds__(256) void synlik_kernel(SynArgs A) {
         ++kb;
         nextp = kb < A.K ? A.prefixes[kb] : 0;
       }
-#pragma unroll
-      for (int i = 0; i < NT; ++i) {
-        const int q = wv + 4 * i;
-        if (q < T * T) {
-          const int ti = q / T, tj = q - ti * T;
-          chk[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(row[16 * ti], row[16 * tj], chk[i], 0, 0, 0);
-        }
-      }
+      gram_step<T>(chk, row, wv);
       if (tid < MP)
         for (int rr = 0; rr < 4; ++rr) s1chk += stage[(4 * s + rr) * SP + tid];
     }

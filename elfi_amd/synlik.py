@@ -5,16 +5,20 @@
     bsl = elfi_amd.HipBSL(model, n_sim_round=500)                             # the same with the device default
     elfi_amd.log_SL_stdev(model, theta, [100, 200, 500], ['S1', 'S2'], M=20)  # ONE device call for M x 3 evaluations
     elfi_amd.select_penalty(model, 500, theta, ['S1', 'S2'], shrinkage='warton')   # ONE call for M x 31 (the default penalties)
+    semi = elfi_amd.semiparametric_likelihood()                               # semiBSL: KDE marginals + Gaussian copula
+    elfi_amd.select_penalty(model, 500, theta, ['S1', 'S2'], likelihood=semi) # the same ONE call for the semiparametric form
 
 `syn_loglik` is the thin mirror of `elfihip_syn_loglik` (csrc/synlik.hip): G groups of n summary rows, K prefixes of
 every group and P Warton penalties in one launch.  The factories carry the reference's names and call signatures
 (elfi/methods/bsl/pdf_methods.py:19-74) and return callables with the reference's return types (`np.array([ll])`; a
 scalar for the robust one, a `functools.partial` with an `adjustment` keyword, which is how `BSL.__init__` detects
-misspecification, bsl.py:54).  `log_SL_stdev` / `select_penalty` (pre_sample_methods.py:102-143, 215-318) draw the same
+misspecification, bsl.py:54).  `semi_loglik` mirrors `elfihip_semi_loglik` (csrc/semibsl.hip) in the same way: the
+semiparametric likelihood of An, Nott & Drovandi (pdf_methods.py:46-59, 179-264) with the same (G, K, P) call shape.
+`log_SL_stdev` / `select_penalty` (pre_sample_methods.py:102-143, 215-318) draw the same
 child seeds through `model.generate` as the reference and stack the M matrices as M groups.
 
-Not on the device: graphical-lasso shrinkage, the semiparametric likelihood, estimate_whitening_matrix, the
-slice samplers for gamma.  They raise or stay the reference's; nothing falls back quietly.
+Not on the device: graphical-lasso shrinkage, the whitened semiparametric likelihood (wsemiBSL),
+estimate_whitening_matrix, the slice samplers for gamma.  They raise or stay the reference's; nothing falls back quietly.
 """
 import sys
 from functools import partial
@@ -24,6 +28,7 @@ import numpy as np
 from . import _lib
 
 MAX_FEATURES = 64
+MAX_SEMI_ROWS = 16384       # rows per group of the semiparametric likelihood: one column is held in LDS
 _VARIANTS = {'standard': 0, 'unbiased': 1, 'mean': 2, 'variance': 3}
 _CLASSES = {}
 
@@ -42,17 +47,8 @@ def _variant_code(variant, adjustment):
     return _VARIANTS[variant]
 
 
-def syn_loglik(ssx, ssy, n_groups=1, variant='standard', shrinkage=None, penalty=None, whitening=None, gamma=None,
-               adjustment=None, prefixes=None, penalties=None, return_moments=False, ctx=None):
-    """Gaussian synthetic log-likelihoods of `n_groups` groups of simulated summaries in one device call.
-
-    ssx: (n_groups * n, m), group g = rows g n ... g n + n - 1, or (n_groups, n, m); ssy: the m observed summaries.
-    variant: 'standard' | 'unbiased' | 'robust' (with adjustment 'mean' | 'variance' and gamma (m)).
-    shrinkage: None | 'warton' with `penalty` (one) or `penalties` (several, an axis of the result).
-    prefixes: row counts, ascending, the last == n: the likelihood of the first prefixes[k] rows of every group (an axis).
-    Returns an array (n_groups[, len(prefixes)][, len(penalties)]); a float for one group given as a 2-d array and
-    neither list.  With return_moments: (loglik, mean (G, m), cov (G, m, m)) of the full groups after whitening.
-    """
+def _groups(ssx, ssy, n_groups):
+    """(X (n_groups n, m), y (m), n_groups, n, m, keep_group_axis) of the two layouts ssx may have."""
     X = np.asarray(ssx, dtype=np.float64)
     keep_group_axis = X.ndim == 3 or n_groups != 1
     if X.ndim == 3:
@@ -76,34 +72,73 @@ def syn_loglik(ssx, ssy, n_groups=1, variant='standard', shrinkage=None, penalty
     y = np.ascontiguousarray(np.asarray(ssy, dtype=np.float64).reshape(-1))
     if y.shape != (m,):
         raise ValueError('ssy has %d entries, ssx has %d columns' % (y.size, m))
+    return X, y, n_groups, n, m, keep_group_axis
+
+
+def _penalty_list(shrinkage, penalty, penalties):
+    """The Warton penalties as an array, or None without shrinkage."""
+    if shrinkage == 'glasso':
+        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
+    if shrinkage not in (None, 'warton'):
+        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    if shrinkage is None:
+        if penalties is not None:
+            raise ValueError("penalties need shrinkage='warton'")
+        return None
+    if penalties is None and penalty is None:
+        raise ValueError("shrinkage='warton' needs penalty or penalties")
+    pen = np.ascontiguousarray(np.atleast_1d(np.asarray(penalty if penalties is None else penalties, dtype=np.float64)))
+    if pen.ndim != 1 or pen.size < 1:
+        raise ValueError('penalties must be a non-empty list')
+    if not np.all((pen >= 0) & (pen <= 1)):
+        raise ValueError('Gamma must be between 0 and 1')           # cov_warton.py:21-22
+    return pen
+
+
+def _prefix_list(prefixes, n):
+    if prefixes is None:
+        return None
+    pre = np.ascontiguousarray(np.atleast_1d(np.asarray(prefixes)).astype(np.int64))
+    if pre.ndim != 1 or pre.size < 1 or np.any(np.diff(pre) <= 0) or pre[0] < 2 or pre[-1] != n:
+        raise ValueError('prefixes must be ascending row counts >= 2 whose last entry is n=%d' % n)
+    return pre
+
+
+def _squeeze(ll, keep_group_axis, prefixes, penalties):
+    """(G, K, max(P, 1)) -> the axes the caller asked for; a float for one group given as a 2-d array and neither list."""
+    if penalties is None:
+        ll = ll[:, :, 0]
+    if prefixes is None:
+        ll = ll[:, 0]
+    if not keep_group_axis:
+        ll = ll[0]
+        if ll.ndim == 0:
+            ll = float(ll)
+    return ll
+
+
+def syn_loglik(ssx, ssy, n_groups=1, variant='standard', shrinkage=None, penalty=None, whitening=None, gamma=None,
+               adjustment=None, prefixes=None, penalties=None, return_moments=False, ctx=None):
+    """Gaussian synthetic log-likelihoods of `n_groups` groups of simulated summaries in one device call.
+
+    ssx: (n_groups * n, m), group g = rows g n ... g n + n - 1, or (n_groups, n, m); ssy: the m observed summaries.
+    variant: 'standard' | 'unbiased' | 'robust' (with adjustment 'mean' | 'variance' and gamma (m)).
+    shrinkage: None | 'warton' with `penalty` (one) or `penalties` (several, an axis of the result).
+    prefixes: row counts, ascending, the last == n: the likelihood of the first prefixes[k] rows of every group (an axis).
+    Returns an array (n_groups[, len(prefixes)][, len(penalties)]); a float for one group given as a 2-d array and
+    neither list.  With return_moments: (loglik, mean (G, m), cov (G, m, m)) of the full groups after whitening.
+    """
+    X, y, n_groups, n, m, keep_group_axis = _groups(ssx, ssy, n_groups)
     code = _variant_code(variant, adjustment)
     g = None
     if code >= 2:
         if gamma is None:
             raise ValueError('the robust likelihood needs gamma')
         g = np.ascontiguousarray(np.broadcast_to(np.asarray(gamma, dtype=np.float64).reshape(-1), (m,)))
-    if shrinkage == 'glasso':
-        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
-    if shrinkage not in (None, 'warton'):
-        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    pen = _penalty_list(shrinkage, penalty, penalties)
     if shrinkage is not None and code != 0:
         raise ValueError('shrinkage goes with the standard likelihood only (the unbiased and robust ones have none)')
-    pen = None
-    if shrinkage == 'warton':
-        if penalties is None and penalty is None:
-            raise ValueError("shrinkage='warton' needs penalty or penalties")
-        pen = np.ascontiguousarray(np.atleast_1d(np.asarray(penalty if penalties is None else penalties, dtype=np.float64)))
-        if pen.ndim != 1 or pen.size < 1:
-            raise ValueError('penalties must be a non-empty list')
-        if not np.all((pen >= 0) & (pen <= 1)):
-            raise ValueError('Gamma must be between 0 and 1')           # cov_warton.py:21-22
-    elif penalties is not None:
-        raise ValueError("penalties need shrinkage='warton'")
-    pre = None
-    if prefixes is not None:
-        pre = np.ascontiguousarray(np.atleast_1d(np.asarray(prefixes)).astype(np.int64))
-        if pre.ndim != 1 or pre.size < 1 or np.any(np.diff(pre) <= 0) or pre[0] < 2 or pre[-1] != n:
-            raise ValueError('prefixes must be ascending row counts >= 2 whose last entry is n=%d' % n)
+    pre = _prefix_list(prefixes, n)
     W = None
     if whitening is not None:
         W = np.ascontiguousarray(whitening, dtype=np.float64)
@@ -118,15 +153,38 @@ def syn_loglik(ssx, ssy, n_groups=1, variant='standard', shrinkage=None, penalty
     ctx = ctx or _lib.default_context()
     ctx.call("elfihip_syn_loglik", _lib.ptr(X), n_groups, n, m, m, _lib.ptr(y), _lib.ptr(W), code, _lib.ptr(g),
              _lib.ptr(pre), 0 if pre is None else K, _lib.ptr(pen), P, _lib.ptr(ll), _lib.ptr(mean), _lib.ptr(cov))
-    if penalties is None:
-        ll = ll[:, :, 0]
-    if prefixes is None:
-        ll = ll[:, 0]
-    if not keep_group_axis:
-        ll = ll[0]
-        if ll.ndim == 0:
-            ll = float(ll)
+    ll = _squeeze(ll, keep_group_axis, prefixes, penalties)
     return (ll, mean, cov) if return_moments else ll
+
+
+def semi_loglik(ssx, ssy, n_groups=1, shrinkage=None, penalty=None, prefixes=None, penalties=None, return_parts=False,
+                ctx=None):
+    """Semiparametric synthetic log-likelihoods (semiBSL: a kernel density estimate per summary, a Gaussian copula with
+    the Gaussian rank correlation) of `n_groups` groups of simulated summaries in one device call.
+
+    ssx, ssy, n_groups, shrinkage ('warton': rho -> (1 - penalty) rho + penalty I), penalty / penalties, prefixes and the
+    shape of the result: as syn_loglik.  A group has 2 to MAX_SEMI_ROWS rows.  -inf where ssy lies outside the reach of a
+    column's density estimate (its integral is 0 or 1), where a column has no spread or the correlation matrix no
+    Cholesky factor.  With return_parts: (loglik, u (G, m), rho (G, m, m), scores (G, n, m)) of the full groups -- the
+    integrals of the density estimates up to ssy, the rank correlation before shrinkage, the normal scores of the rows.
+    """
+    X, y, n_groups, n, m, keep_group_axis = _groups(ssx, ssy, n_groups)
+    if n > MAX_SEMI_ROWS:
+        raise ValueError('%d rows per group: the semiparametric kernel takes 2 to %d' % (n, MAX_SEMI_ROWS))
+    pen = _penalty_list(shrinkage, penalty, penalties)
+    pre = _prefix_list(prefixes, n)
+    X = np.ascontiguousarray(X)
+    K = 1 if pre is None else pre.size
+    P = 0 if pen is None else pen.size
+    ll = np.empty((n_groups, K, max(P, 1)), dtype=np.float64)
+    u = np.empty((n_groups, m), dtype=np.float64) if return_parts else None
+    rho = np.empty((n_groups, m, m), dtype=np.float64) if return_parts else None
+    scores = np.empty((n_groups, n, m), dtype=np.float64) if return_parts else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_semi_loglik", _lib.ptr(X), n_groups, n, m, m, _lib.ptr(y), _lib.ptr(pre), 0 if pre is None else K,
+             _lib.ptr(pen), P, _lib.ptr(ll), _lib.ptr(u), _lib.ptr(rho), _lib.ptr(scores))
+    ll = _squeeze(ll, keep_group_axis, prefixes, penalties)
+    return (ll, u, rho, scores) if return_parts else ll
 
 
 # ---- the reference's likelihood callables (pdf_methods.py:77-135, 138-176, 267-316) ----------------------------------
@@ -147,6 +205,15 @@ def syn_likelihood_misspec(ssx, ssy, gamma, adjustment):
     return syn_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, gamma=gamma, adjustment=adjustment)
 
 
+def semi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
+    """Semiparametric synthetic log-likelihood of one (n, m) summary matrix; np.array([ll]), the shape of the other
+    device callables (the reference's own return is a (1, 1, 1) array that BSL only adds to a scalar)."""
+    if whitening is not None:
+        raise NotImplementedError('the whitened semiparametric likelihood (wsemiBSL) is not on the device')
+    return np.array([semi_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, shrinkage=shrinkage,
+                                 penalty=penalty)])
+
+
 def standard_likelihood(shrinkage=None, penalty=None, whitening=None):
     """pdf_methods.standard_likelihood on the device (Warton shrinkage or none)."""
     if shrinkage == 'glasso':
@@ -154,6 +221,17 @@ def standard_likelihood(shrinkage=None, penalty=None, whitening=None):
     if shrinkage not in (None, 'warton'):
         raise ValueError('unknown shrinkage %r' % (shrinkage,))
     return partial(gaussian_syn_likelihood, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
+
+
+def semiparametric_likelihood(shrinkage=None, penalty=None, whitening=None):
+    """pdf_methods.semiparametric_likelihood on the device (Warton shrinkage of the correlation matrix or none)."""
+    if shrinkage == 'glasso':
+        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
+    if shrinkage not in (None, 'warton'):
+        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    if whitening is not None:
+        raise NotImplementedError('the whitened semiparametric likelihood (wsemiBSL) is not on the device')
+    return partial(semi_param_kernel_estimate, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
 
 
 def unbiased_likelihood():
@@ -169,7 +247,7 @@ def robust_likelihood(adjustment):
 
 
 def _likelihood_setup(likelihood, **override):
-    """syn_loglik keywords of one of the callables above (None: the standard one)."""
+    """syn_loglik keywords of one of the callables above (None: the standard one); with semi=True: semi_loglik's."""
     kw = {}
     fn = likelihood
     if isinstance(likelihood, partial):
@@ -177,10 +255,15 @@ def _likelihood_setup(likelihood, **override):
     if fn is None or fn is gaussian_syn_likelihood:
         kw.update({k: v for k, v in override.items()})
         return dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw.get('whitening'))
+    if fn is semi_param_kernel_estimate:
+        kw.update({k: v for k, v in override.items()})
+        if kw.get('whitening') is not None:
+            raise NotImplementedError('the whitened semiparametric likelihood (wsemiBSL) is not on the device')
+        return dict(semi=True, shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'))
     if fn is gaussian_syn_likelihood_ghurye_olkin and not override:
         return dict(variant='unbiased')
     raise TypeError('the batched evaluation takes the device likelihoods of elfi_amd (standard_likelihood(...), '
-                    'unbiased_likelihood()); got %r' % (likelihood,))
+                    'semiparametric_likelihood(...), unbiased_likelihood()); got %r' % (likelihood,))
 
 
 def _generate_groups(model, theta, max_sim, feature_names, M, seed):
@@ -215,7 +298,8 @@ def log_SL_stdev(model, theta, n_sim, feature_names, likelihood=None, M=20, seed
     setup = _likelihood_setup(likelihood)
     counts, uniq, where = _prefix_axis(n_sim)
     groups, observed = _generate_groups(model, theta, int(uniq[-1]), feature_names, M, seed)
-    ll = syn_loglik(groups, observed, prefixes=uniq, **setup)          # (M, len(uniq))
+    batched = semi_loglik if setup.pop('semi', False) else syn_loglik
+    ll = batched(groups, observed, prefixes=uniq, **setup)          # (M, len(uniq))
     return np.std(np.ascontiguousarray(ll[:, where].T), axis=1)     # (len(n_sim), M), the reference's layout
 
 
@@ -233,7 +317,8 @@ def select_penalty(model, n_sim, theta, feature_names, likelihood=None, lmdas=No
     counts, uniq, where = _prefix_axis(n_sim)
     groups, observed = _generate_groups(model, theta, int(uniq[-1]), feature_names, M, seed)
     setup.pop('penalty', None)
-    logliks = syn_loglik(groups, observed, prefixes=uniq, penalties=lmdas, **setup)     # (M, len(uniq), len(lmdas))
+    batched = semi_loglik if setup.pop('semi', False) else syn_loglik
+    logliks = batched(groups, observed, prefixes=uniq, penalties=lmdas, **setup)        # (M, len(uniq), len(lmdas))
     spread = logliks.std(axis=0)[where]                    # over the repeats: (len(n_sim), len(lmdas))
     pick = np.abs(spread - sigma).argmin(axis=1)           # ties go to the smaller penalty index, as argmin does
     if verbose:

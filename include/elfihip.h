@@ -340,6 +340,30 @@ int elfihip_syn_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_
                            const double* dW, int variant, const double* dgamma_adj, const int64_t* prefixes, int K,
                            const double* penalties, int P, double* dloglik, double* dmean, double* dcov);
 
+/* The semiparametric synthetic log-likelihood (semiBSL: a kernel density estimate per summary and a Gaussian copula with
+ * the Gaussian rank correlation; elfi/methods/bsl/pdf_methods.py:179-264, gaussian_rank_corr.py:30-52) of G groups of n
+ * rows in one call.  X, y, ldx, prefixes, penalties and loglik (G, K, max(P, 1)) as for elfihip_syn_loglik; m <= 64,
+ * 2 <= n <= 16384 (one column of a group is held in LDS).  Per column j of the first p rows: bandwidth
+ * h = (3 p / 4)^(-1/5) std (ddof 1), z_i = (y_j - x_ij) / h, logpdf_j = logsumexp_i(-z_i^2 / 2) - log p - log h -
+ * log(2 pi) / 2, u_j = min(1, sum_i Phi(z_i) / p), eta_j = Phi^-1(u_j); scores q_ij = Phi^-1(r_ij / (p + 1)) with r the
+ * 1-based rank within the column, ties at the average rank; rho_ab = sum_i q_ia q_ib / sum_i Phi^-1(i / (p + 1))^2,
+ * rho_aa = 1; penalty l: rho <- (1 - l) rho + l I (corr_warton: no eps);
+ * loglik = -(log|rho| + eta^T rho^-1 eta - eta^T eta) / 2 + sum_j logpdf_j.
+ * -inf with the status left at ELFIHIP_OK: a u_j of 0 or 1, a non-positive Cholesky pivot, a non-finite value; a column
+ * without spread (h = 0 -- the reference raises LinAlgError from scipy's gaussian_kde there); two rows and m > 1 (rho has
+ * rank one; the reference returns about -1e16 from rounding noise).
+ * u (G, m), rho (G, m, m), scores (G, n, m) or NULL: of the full groups, the integrals u_j, the rank correlation before
+ * shrinkage and the normal scores q.
+ * Host form: host pointers, synchronises.  _dev form: X, y, loglik, u, rho, scores are device pointers, no
+ * synchronisation; prefixes and penalties are host arrays in both forms (they are checked before any launch).
+ * Deterministic; a group's result does not depend on G, and prefix p has the bits of a group of p rows. */
+int elfihip_semi_loglik(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, int m, int64_t ldx, const double* y,
+                        const int64_t* prefixes, int K, const double* penalties, int P, double* loglik, double* u,
+                        double* rho, double* scores);
+int elfihip_semi_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx, const double* dy,
+                            const int64_t* prefixes, int K, const double* penalties, int P, double* dloglik, double* du,
+                            double* drho, double* dscores);
+
 /* ------------------------------------------------------------------ summaries
  * Row-wise summary statistics that ELFI's example models install as elfi.Summary operations, with
  * NumPy's exact (pairwise) summation order, i.e. bit-identical results:
