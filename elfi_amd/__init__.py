@@ -33,6 +33,8 @@ from . import chains, fused_models, multistart, priors  # noqa: F401
 from .maxvar_acquisition import HipExpIntVar, HipMaxVar, HipRandMaxVar  # noqa: F401
 from .synlik import (HipBSL, hip_bsl_class, log_SL_stdev, robust_likelihood, select_penalty,  # noqa: F401
                      semi_loglik, semiparametric_likelihood, standard_likelihood, syn_loglik, unbiased_likelihood)
+from .logratio import HipLogisticRegression, hip_logistic_regression_class, log_ratio  # noqa: F401
+from .bolfire import HipBOLFIRE, HipBOLFIREPosterior, hip_bolfire_class  # noqa: F401
 
 
 

@@ -364,6 +364,38 @@ int elfihip_semi_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64
                             const int64_t* prefixes, int K, const double* penalties, int P, double* dloglik, double* du,
                             double* drho, double* dscores);
 
+/* Logistic-regression ratio estimation (the classifier of BOLFIRE; elfi/methods/classifier.py:72-121: StandardScaler,
+ * then scikit-learn's LogisticRegression(penalty='l1', solver='liblinear'), then the log-odds) of G groups in one call.
+ * X (G n, m) row-major with pitch ldx: the likelihood rows, label +1, group g = rows g n ... g n + n - 1.  M (nm, m) with
+ * pitch ldm: the marginal rows, label -1, shared by every group.  Yobs (k, m) contiguous: where the log ratio is read.
+ * 1 <= m <= 64, n >= 1, nm >= 1, k >= 1; C > 0 (liblinear's default 1), 0 <= class_min < 1, tol >= 0, max_iter >= 0.
+ * Per group, N = n + nm: mean and population standard deviation (ddof 0) of the N stacked rows per column, scale 1 for a
+ * column StandardScaler treats as constant (var <= N eps var + (N mean eps)^2); x~ = (x - mean) / scale.  The fit
+ * minimises liblinear's L1R_LR objective with fit_intercept=True, intercept_scaling=1,
+ *     ||v||_1 + C sum_i log(1 + exp(-y_i v.z_i)),  z_i = (x~_i, 1),  v = (w, b)
+ * (the intercept is a penalised coordinate) by proximal Newton steps: coordinate descent with soft-thresholding on the
+ * quadratic model, then a backtracking line search on the objective; a coordinate ends exactly zero or not.  With
+ * g = C Z^T (-y o sigma(-y o Z v)) the optimality violation is the largest of |g_j + sign(v_j)| (v_j != 0) and
+ * max(|g_j| - 1, 0) (v_j == 0); the iteration stops when it is <= tol or after max_iter outer steps.
+ * logratio (G, k): t = w.x~_obs + b where expit(t) >= class_min, else log(class_min / (1 - class_min)).  That is the
+ * reference's log(p / (1 - p)), p = max(expit(t), class_min), without the rounding of 1 - p, and finite where the
+ * reference returns +-inf from an expit that under- or overflows.
+ * Each may be NULL: coef (G, m), intercept (G), mean (G, m), scale (G, m), n_iter (G) outer steps taken, status (G):
+ * 0 converged, 1 stopped at max_iter, 2 a non-finite value (in the group's rows, in M, or on the way), 4 no step lowers the
+ * objective any more (its rounding level is reached before tol).  A group with status 2 has NaN outputs.  None of these
+ * is an error return: the call gives ELFIHIP_OK.
+ * Host form: host pointers, synchronises.  _dev form: X, M, Yobs and every output are device pointers, no
+ * synchronisation; the scalars are host values in both forms.
+ * Deterministic; a group's result does not depend on G or on the other groups of the call. */
+int elfihip_log_ratio(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, int m, int64_t ldx, const double* M,
+                      int64_t nm, int64_t ldm, const double* Yobs, int64_t k, double C, double class_min, double tol,
+                      int max_iter, double* logratio, double* coef, double* intercept, double* mean, double* scale,
+                      int* n_iter, int* status);
+int elfihip_log_ratio_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx, const double* dM,
+                          int64_t nm, int64_t ldm, const double* dYobs, int64_t k, double C, double class_min, double tol,
+                          int max_iter, double* dlogratio, double* dcoef, double* dintercept, double* dmean,
+                          double* dscale, int* dn_iter, int* dstatus);
+
 /* ------------------------------------------------------------------ summaries
  * Row-wise summary statistics that ELFI's example models install as elfi.Summary operations, with
  * NumPy's exact (pairwise) summation order, i.e. bit-identical results:
