@@ -20,6 +20,7 @@
 
 #include <cmath>
 
+#include "np_sum.hpp"
 #include "philox.hpp"
 
 #pragma clang fp contract(off)
@@ -135,32 +136,6 @@ __device__ __forceinline__ double pairwise8(F f, int n, int j) {
   return r;
 }
 
-// the general length: one lane per row, NumPy's recursion (blocks of at most 128, halves rounded to multiples of 8)
-template <class F>
-__device__ double pairwise1(F f, int lo, int n) {
-  if (n < 8) {
-    double r = 0.0;
-    for (int i = 0; i < n; ++i) r += f(lo + i);
-    return r;
-  }
-  if (n <= 128) {
-    double r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = f(lo + j);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r[j] += f(lo + i + j);
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += f(lo + i);
-    return res;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return pairwise1(f, lo, n2) + pairwise1(f, lo + n2, n - n2);
-}
-
 struct GaussArgs {
   const double* Z;     // (n, ldz) standard normals, or NULL: drawn here
   int64_t ldz;
@@ -230,8 +205,8 @@ __global__ __launch_bounds__(128) void gauss_kernel(GaussArgs G) {
       }
     } else if (tid < rows) {
       const double* row = tile + (size_t)tid * G.Lp;
-      const double mean = pairwise1([&](int i) { return row[i]; }, 0, L) / (double)L;
-      const double var = pairwise1([&](int i) { const double d = row[i] - mean; return d * d; }, 0, L) / (double)L;
+      const double mean = np_pairwise_row([&](int i) { return row[i]; }, L) / (double)L;
+      const double var = np_pairwise_row([&](int i) { const double d = row[i] - mean; return d * d; }, L) / (double)L;
       const int64_t gi = row0 + tid;
       G.S1[gi] = mean;
       G.S2[gi] = var;

@@ -2,7 +2,9 @@
 //
 // np.add.reduce along a contiguous axis is a pairwise sum: fewer than 8 terms in order; 8 .. 128 terms by eight
 // interleaved accumulators over stride 8, combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the tail in order; more than
-// 128 terms split at n/2 - (n/2 mod 8) and both halves summed the same way.  With FMA contraction off the results are
+// 128 terms split at n/2 - (n/2 mod 8) and both halves summed the same way.  The reduction hands that sum at most one
+// buffer of its iterator at a time (np.getbufsize(), 8192 elements by default), so an axis longer than that is summed
+// piece by piece, the pieces added to the result in order (np_pairwise_row).  With FMA contraction off the results are
 // BIT-IDENTICAL to NumPy.
 #pragma once
 
@@ -38,6 +40,17 @@ __device__ double np_pairwise(F f, int lo, int n) {
   int n2 = n / 2;
   n2 -= n2 % 8;
   return np_pairwise(f, lo, n2) + np_pairwise(f, lo + n2, n - n2);
+}
+
+// np.add.reduce over a whole row of n terms: pieces of NumPy's default buffer size, each summed pairwise, added in order.
+constexpr int NP_BUFSIZE = 8192;
+
+template <class F>
+__device__ double np_pairwise_row(F f, int n) {
+#pragma clang fp contract(off)
+  double r = np_pairwise(f, 0, n < NP_BUFSIZE ? n : NP_BUFSIZE);
+  for (int lo = NP_BUFSIZE; lo < n; lo += NP_BUFSIZE) r += np_pairwise(f, lo, n - lo < NP_BUFSIZE ? n - lo : NP_BUFSIZE);
+  return r;
 }
 
 // The same sum with at most D splits, inlined (no call, no stack): exact for every n whose split tree is at most D deep

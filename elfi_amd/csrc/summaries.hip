@@ -172,20 +172,20 @@ __global__ __launch_bounds__(256) void row_summary_kernel(SumArgs S) {
       const double* row = tile + (size_t)tid * A.mp;
       const int64_t gi = row0 + tid;
       if constexpr (KIND == SUM_MEAN) {
-        S.out1[gi] = np_pairwise([&](int i) { return row[i]; }, 0, L) / (double)L;
+        S.out1[gi] = np_pairwise_row([&](int i) { return row[i]; }, L) / (double)L;
       } else if constexpr (KIND == SUM_VAR) {
-        const double mean = np_pairwise([&](int i) { return row[i]; }, 0, L) / (double)L;
-        S.out1[gi] = np_pairwise([&](int i) { const double d = row[i] - mean; return d * d; }, 0, L) / (double)L;
+        const double mean = np_pairwise_row([&](int i) { return row[i]; }, L) / (double)L;
+        S.out1[gi] = np_pairwise_row([&](int i) { const double d = row[i] - mean; return d * d; }, L) / (double)L;
       } else if constexpr (KIND == SUM_AUTOCOV) {
         const int lag = S.lag, cnt = L - lag;
-        S.out1[gi] = np_pairwise([&](int i) { return row[i + lag] * row[i]; }, 0, cnt) / (double)cnt;
+        S.out1[gi] = np_pairwise_row([&](int i) { return row[i + lag] * row[i]; }, cnt) / (double)cnt;
       } else {  // SUM_MA2: row holds w (L = n_obs + 2); x_i = (w[i+2] + t1 w[i+1]) + t2 w[i], in place
         const double a = S.t1[gi], b = S.t2[gi];
         const int nobs = L - 2;
         double* x = tile + (size_t)tid * A.mp;
         for (int i = 0; i < nobs; ++i) x[i] = (x[i + 2] + a * x[i + 1]) + b * x[i];
-        const double s1 = np_pairwise([&](int i) { return x[i + 1] * x[i]; }, 0, nobs - 1) / (double)(nobs - 1);
-        const double s2 = np_pairwise([&](int i) { return x[i + 2] * x[i]; }, 0, nobs - 2) / (double)(nobs - 2);
+        const double s1 = np_pairwise_row([&](int i) { return x[i + 1] * x[i]; }, nobs - 1) / (double)(nobs - 1);
+        const double s2 = np_pairwise_row([&](int i) { return x[i + 2] * x[i]; }, nobs - 2) / (double)(nobs - 2);
         S.out1[gi] = s1;
         S.out2[gi] = s2;
         const double d1 = s1 - S.obs1, d2 = s2 - S.obs2;   // cdist euclidean over the two summaries

@@ -402,7 +402,9 @@ int elfihip_log_ratio_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t
  *   ELFIHIP_SUM_MEAN     np.mean(y, axis=1)                           elfi/examples/gauss.py:142-156
  *   ELFIHIP_SUM_VAR      np.var(y, axis=1)                            elfi/examples/gauss.py:159-173
  *   ELFIHIP_SUM_AUTOCOV  np.mean(x[:, lag:] * x[:, :-lag], axis=1)    elfi/examples/ma2.py:40-59
- * X is row-major (n, L) with leading dimension ldx; out has n doubles; lag only for AUTOCOV. */
+ * X is row-major (n, L) with leading dimension ldx; out has n doubles; lag only for AUTOCOV.  A row takes one LDS tile:
+ * L <= 20479 ((L | 1) * 8 bytes <= 160 KiB), ELFIHIP_ERR_ARG beyond.  Rows longer than NumPy's reduction buffer (8192
+ * elements) are summed as NumPy sums them: pairwise inside pieces of 8192, the pieces added in order. */
 enum { ELFIHIP_SUM_MEAN = 0, ELFIHIP_SUM_VAR = 1, ELFIHIP_SUM_AUTOCOV = 2 };
 int elfihip_row_summary(elfihip_ctx* ctx, int kind, const double* X, int64_t n, int L, int64_t ldx, int lag,
                         double* out);
