@@ -665,16 +665,9 @@ int adaptive_pass_impl(elfihip_ctx* ctx, const double* dX, int64_t n, int m, int
   if (g < 1) g = 1;
   const int h = m / 2;
   const int nu = (ADA_T % h == 0 && A.R % (ADA_T / h) == 0) ? A.R / (ADA_T / h) : 0;   // loads per thread and tile when m / 2 divides the workgroup
-#define ELFIHIP_ADA_LAUNCH(NU) \
-  hipLaunchKernelGGL((adaptive_pass_kernel<NU>), dim3((unsigned)g), dim3(ADA_T), lds, ctx->stream, P)
-  switch (nu) {
-    case 8: ELFIHIP_ADA_LAUNCH(8); break;
-    case 4: ELFIHIP_ADA_LAUNCH(4); break;
-    case 2: ELFIHIP_ADA_LAUNCH(2); break;
-    case 1: ELFIHIP_ADA_LAUNCH(1); break;
-    default: ELFIHIP_ADA_LAUNCH(0); break;
-  }
-#undef ELFIHIP_ADA_LAUNCH
+  with_constant<8, 4, 2, 1, 0>(nu, [&](auto NU) {
+    hipLaunchKernelGGL((adaptive_pass_kernel<decltype(NU)::value>), dim3((unsigned)g), dim3(ADA_T), lds, ctx->stream, P);
+  });
   if (nparts && partial) *nparts = (int)g;
   return launch_status(ctx, "adaptive_pass_kernel");
 }

@@ -9,9 +9,11 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/elfihip.h"
+#include "group_args.hpp"
 
 namespace elfihip {
 
@@ -198,6 +200,50 @@ inline int launch_status(elfihip_ctx* ctx, const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess)
     return fail(ctx, ELFIHIP_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
+  return ELFIHIP_OK;
+}
+
+// Raises a kernel's dynamic-LDS limit when a launch asks for more than `above` bytes.
+template <class KernelT>
+static int set_lds(elfihip_ctx* ctx, KernelT k, size_t lds, size_t above = 64 * 1024) {
+  if (lds > above)
+    ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return ELFIHIP_OK;
+}
+
+// A run-time choice among a few template arguments: f(std::integral_constant<int, V>{}) for the V that equals v (else the last)
+template <int V0, int... Vs, class F>
+static inline void with_constant(int v, F f) {
+  if constexpr (sizeof...(Vs) > 0) {
+    if (v != V0) return with_constant<Vs...>(v, f);
+  }
+  f(std::integral_constant<int, V0>{});
+}
+
+// Launches the instance for T = group_tiles(m) tiles (1 to 4) of a kernel family, 256 threads per workgroup: kernel_of(T)
+// and lds_bytes_of(T) take a std::integral_constant.  The LDS limit is raised from 48 KiB on, not set_lds's 64: instances
+// in between (SynShape<3>, SemiShape<3>, LrShape<4>) have never been launched without it.
+template <class KernelOf, class LdsBytesOf, class Args>
+static inline int launch_by_tiles(elfihip_ctx* ctx, int m, unsigned grid, const char* name, KernelOf kernel_of,
+                                  LdsBytesOf lds_bytes_of, const Args& args) {
+  int rc = ELFIHIP_OK;
+  with_constant<1, 2, 3, 4>(group_tiles(m), [&](auto T) {
+    const size_t lds = lds_bytes_of(T);
+    if ((rc = set_lds(ctx, kernel_of(T), lds, 48 * 1024)) != ELFIHIP_OK) return;
+    hipLaunchKernelGGL(kernel_of(T), dim3(grid), dim3(256), lds, ctx->stream, args);
+  });
+  return rc != ELFIHIP_OK ? rc : launch_status(ctx, name);
+}
+
+// rows x m doubles from host memory at pitch ld (in doubles) to contiguous device memory, on the context's stream
+inline int upload_rows(elfihip_ctx* ctx, double* dst, const double* src, size_t rows, int m, int64_t ld) {
+  const size_t md = (size_t)m * sizeof(double);
+  if (ld == m)
+    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dst, src, rows * md, hipMemcpyHostToDevice, ctx->stream));
+  else
+    ELFIHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(dst, md, src, (size_t)ld * sizeof(double), md, rows, hipMemcpyHostToDevice,
+                                            ctx->stream));
   return ELFIHIP_OK;
 }
 

@@ -3,7 +3,6 @@
 #pragma once
 
 #include <algorithm>
-#include <type_traits>
 
 #include "common.hpp"
 #include "tile_stream.hpp"
@@ -36,23 +35,6 @@ static inline int grid_for(const elfihip_ctx* ctx, int64_t ntiles, size_t lds_by
   if (g > ntiles) g = ntiles;
   if (g < 1) g = 1;
   return (int)g;
-}
-
-template <class KernelT>
-static int set_lds(elfihip_ctx* ctx, KernelT k, size_t lds) {
-  if (lds > 64 * 1024)
-    ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return ELFIHIP_OK;
-}
-
-// A run-time choice among a few template arguments: f(std::integral_constant<int, V>{}) for the V that equals v (else the last)
-template <int V0, int... Vs, class F>
-static inline void with_constant(int v, F f) {
-  if constexpr (sizeof...(Vs) > 0) {
-    if (v != V0) return with_constant<Vs...>(v, f);
-  }
-  f(std::integral_constant<int, V0>{});
 }
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -140,13 +122,7 @@ static inline int stage_rows(elfihip_ctx* ctx, const double* X, int64_t n, int m
   ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((size_t)n * m * sizeof(double)));
   *dX = ctx->in.as<double>();
   if (n == 0) return ELFIHIP_OK;
-  if (ldx == m)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(*dX, X, (size_t)n * m * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  else
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(*dX, (size_t)m * sizeof(double), X, (size_t)ldx * sizeof(double),
-                                            (size_t)m * sizeof(double), (size_t)n, hipMemcpyHostToDevice,
-                                            ctx->stream));
-  return ELFIHIP_OK;
+  return upload_rows(ctx, *dX, X, (size_t)n, m, ldx);
 }
 
 // The row-major host entry points' preamble: y, aux (naux doubles, or NULL), the rows at pitch m, room for n x cols results

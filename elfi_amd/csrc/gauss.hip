@@ -250,9 +250,7 @@ static int gauss_dev_impl(elfihip_ctx* ctx, const double* dZ, int64_t ldz, uint6
   const int64_t ntiles = (n + rows - 1) / rows;
   const int64_t g = std::min<int64_t>(ntiles, (int64_t)ctx->cu_count * 8);
   if (wide) {
-    if (lds > 64 * 1024)
-      ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(gauss_kernel<true>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ELFIHIP_TRY(set_lds(ctx, gauss_kernel<true>, lds));
     hipLaunchKernelGGL(gauss_kernel<true>, dim3((unsigned)g), dim3(128), lds, ctx->stream, G);
   } else {
     hipLaunchKernelGGL(gauss_kernel<false>, dim3((unsigned)g), dim3(128), lds, ctx->stream, G);

@@ -64,6 +64,7 @@ struct LrShape : GramShape<T> {
   // staged rows (also the 4 x 64 x 2 partial sums of the scaler: 512 <= 32 SP), the Gram matrix with the intercept row,
   // mean, scale, v, v + d, trial point, gradient; per staged row: gradient coefficient, weight, loss; 8 scalars
   static constexpr int DOUBLES = SL_RC * SP + (MP + 1) * LP + 6 * LR_VP + 3 * SL_RC + 8;
+  static_assert(DOUBLES * sizeof(double) <= 160 * 1024);
 };
 
 // s + e is the running sum: TwoSum keeps what the addition rounds away
@@ -404,16 +405,6 @@ __global__ __launch_bounds__(256) void logratio_kernel(LrArgs A) {
   }
 }
 
-template <int T>
-static int logratio_launch(elfihip_ctx* ctx, const LrArgs& A, int G) {
-  const size_t bytes = (size_t)LrShape<T>::DOUBLES * sizeof(double);
-  if (bytes > 48 * 1024)
-    ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(logratio_kernel<T>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  hipLaunchKernelGGL(logratio_kernel<T>, dim3(G), dim3(256), bytes, ctx->stream, A);
-  return launch_status(ctx, "log-ratio kernel");
-}
-
 static int logratio_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, int m, int64_t ldx, const void* M,
                           int64_t nm, int64_t ldm, const void* Yobs, int64_t k, double C, double class_min, double tol,
                           int max_iter, const void* logratio) {
@@ -455,12 +446,9 @@ static int logratio_dev_impl(elfihip_ctx* ctx, const double* dX, int G, int64_t 
   A.scale = dscale;
   A.n_iter = dniter;
   A.status = dstatus;
-  switch ((m + 15) / 16) {
-    case 1: return logratio_launch<1>(ctx, A, G);
-    case 2: return logratio_launch<2>(ctx, A, G);
-    case 3: return logratio_launch<3>(ctx, A, G);
-    default: return logratio_launch<4>(ctx, A, G);
-  }
+  return launch_by_tiles(
+      ctx, m, (unsigned)G, "log-ratio kernel", [](auto T) { return logratio_kernel<decltype(T)::value>; },
+      [](auto T) { return (size_t)LrShape<decltype(T)::value>::DOUBLES * sizeof(double); }, A);
 }
 
 }  // namespace elfihip
@@ -502,14 +490,8 @@ int elfihip_log_ratio(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, i
   double* dicpt = dscale + Gs * m;
   int* dniter = reinterpret_cast<int*>(dicpt + Gs);
   int* dstatus = dniter + Gs;
-  if (ldx == m)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dX, X, rows * md, hipMemcpyHostToDevice, st));
-  else
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(dX, md, X, (size_t)ldx * sizeof(double), md, rows, hipMemcpyHostToDevice, st));
-  if (ldm == m)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dM, M, (size_t)nm * md, hipMemcpyHostToDevice, st));
-  else
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(dM, md, M, (size_t)ldm * sizeof(double), md, (size_t)nm, hipMemcpyHostToDevice, st));
+  ELFIHIP_TRY(upload_rows(ctx, dX, X, rows, m, ldx));
+  ELFIHIP_TRY(upload_rows(ctx, dM, M, (size_t)nm, m, ldm));
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dY, Yobs, (size_t)k * md, hipMemcpyHostToDevice, st));
   ELFIHIP_TRY(logratio_dev_impl(ctx, dX, (int)G, n, m, m, dM, nm, m, dY, (int)k, C, class_min, tol, max_iter, dlr,
                                 coef ? dcoef : nullptr, intercept ? dicpt : nullptr, mean ? dmean : nullptr,

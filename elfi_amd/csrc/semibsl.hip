@@ -174,6 +174,7 @@ struct SemiShape : GramShape<T> {
   using GramShape<T>::SP;
   using GramShape<T>::LP;
   static constexpr int DOUBLES = SL_RC * SP + MP * LP + (MP + 1) * LP + 3 * MP;
+  static_assert(DOUBLES * sizeof(double) <= 160 * 1024);
 };
 
 template <int T>
@@ -265,16 +266,6 @@ __global__ __launch_bounds__(256) void semibsl_finish_kernel(SemiArgs A) {
   }
 }
 
-template <int T>
-static int semibsl_finish_launch(elfihip_ctx* ctx, const SemiArgs& A, int64_t GK) {
-  const size_t bytes = (size_t)SemiShape<T>::DOUBLES * sizeof(double);
-  if (bytes > 48 * 1024)
-    ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(semibsl_finish_kernel<T>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  hipLaunchKernelGGL(semibsl_finish_kernel<T>, dim3((unsigned)GK), dim3(256), bytes, ctx->stream, A);
-  return launch_status(ctx, "semiparametric likelihood finish kernel");
-}
-
 static int semibsl_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, int m, int64_t ldx, const void* y,
                          const int64_t* prefixes, int K, const double* penalties, int P, const void* loglik) {
   ELFIHIP_REQUIRE(ctx, m >= 1 && m <= SL_MAX_M, "semiparametric likelihood: %d summaries; 1 to %d are supported", m,
@@ -284,18 +275,10 @@ static int semibsl_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, 
   ELFIHIP_REQUIRE(ctx, G >= 1 && ldx >= m, "bad shape G=%lld n=%lld m=%d ldx=%lld", (long long)G, (long long)n, m,
                   (long long)ldx);
   ELFIHIP_REQUIRE(ctx, X && y && loglik, "NULL data pointer");
-  ELFIHIP_REQUIRE(ctx, (prefixes && K >= 1) || (!prefixes && K <= 1), "prefixes and K do not agree (K=%d)", K);
-  ELFIHIP_REQUIRE(ctx, (penalties && P >= 1) || (!penalties && P == 0), "penalties and P do not agree (P=%d)", P);
   ELFIHIP_REQUIRE(ctx, G * (int64_t)(prefixes ? K : 1) * m <= 0x7fffffff, "G K m = %lld x %d x %d workgroups are too many",
                   (long long)G, prefixes ? K : 1, m);
-  if (prefixes) {
-    for (int k = 0; k < K; ++k)
-      ELFIHIP_REQUIRE(ctx, prefixes[k] >= 2 && (k == 0 || prefixes[k] > prefixes[k - 1]),
-                      "prefixes must be ascending and at least 2 (entry %d)", k);
-    ELFIHIP_REQUIRE(ctx, prefixes[K - 1] == n, "the last prefix must be n");
-  }
-  for (int p = 0; p < P; ++p)
-    ELFIHIP_REQUIRE(ctx, penalties[p] >= 0.0 && penalties[p] <= 1.0, "penalty %d is outside [0, 1]", p);
+  const std::string bad = group_lists_error(prefixes, K, penalties, P, n);
+  ELFIHIP_REQUIRE(ctx, bad.empty(), "%s", bad.c_str());
   return ELFIHIP_OK;
 }
 
@@ -304,18 +287,15 @@ static int semibsl_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64
                             const int64_t* prefixes, int K, const double* penalties, int P, double* dll, double* du,
                             double* drho, double* dscores) {
   hipStream_t st = ctx->stream;
-  const int Ke = prefixes ? K : 1;
-  const int64_t GK = G * Ke;
-  const int MP = 16 * ((m + 15) / 16);
   // parameter block: [prefixes Ke][penalties P]
-  std::vector<double> host((size_t)Ke + P);
-  int64_t* hp = reinterpret_cast<int64_t*>(host.data());
-  for (int k = 0; k < Ke; ++k) hp[k] = prefixes ? prefixes[k] : n;
-  for (int p = 0; p < P; ++p) host[Ke + p] = penalties[p];
-  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve(host.size() * sizeof(double)));
+  const GroupParams B = group_params(prefixes, K, n, nullptr, penalties, P);
+  const int Ke = B.Ke;
+  const int64_t GK = G * Ke;
+  const int MP = 16 * group_tiles(m);
+  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve(B.words.size() * sizeof(double)));
   double* dpar = ctx->par.as<double>();
-  // the parameter block is pageable host memory: the copy has left it before hipMemcpyAsync returns
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  // pageable host memory: the copy has left it before hipMemcpyAsync returns
+  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, B.words.data(), B.words.size() * sizeof(double), hipMemcpyHostToDevice, st));
   const size_t qd = (size_t)GK * (size_t)n * MP;
   ELFIHIP_CHECK_HIP(ctx, ctx->scratch.reserve((qd + (size_t)GK * SEMI_STATS) * sizeof(double)));
   SemiArgs A;
@@ -328,7 +308,7 @@ static int semibsl_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64
   A.MP = MP;
   A.y = dy;
   A.prefixes = reinterpret_cast<const int64_t*>(dpar);
-  A.penalties = P > 0 ? dpar + Ke : nullptr;
+  A.penalties = P > 0 ? dpar + B.pen : nullptr;
   A.Q = ctx->scratch.as<double>();
   A.stats = A.Q + qd;
   A.loglik = dll;
@@ -336,17 +316,13 @@ static int semibsl_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64
   A.rho = drho;
   A.scores = dscores;
   const size_t bytes = (size_t)(SEMI_RED + ((n + 3) & ~(int64_t)3)) * sizeof(double);
-  if (bytes > 48 * 1024)
-    ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(semibsl_column_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  ELFIHIP_TRY(set_lds(ctx, semibsl_column_kernel, bytes, 48 * 1024));
   hipLaunchKernelGGL(semibsl_column_kernel, dim3((unsigned)(GK * m)), dim3(256), bytes, st, A);
   ELFIHIP_TRY(launch_status(ctx, "semiparametric likelihood column kernel"));
-  switch (MP / 16) {
-    case 1: return semibsl_finish_launch<1>(ctx, A, GK);
-    case 2: return semibsl_finish_launch<2>(ctx, A, GK);
-    case 3: return semibsl_finish_launch<3>(ctx, A, GK);
-    default: return semibsl_finish_launch<4>(ctx, A, GK);
-  }
+  return launch_by_tiles(
+      ctx, m, (unsigned)GK, "semiparametric likelihood finish kernel",
+      [](auto T) { return semibsl_finish_kernel<decltype(T)::value>; },
+      [](auto T) { return (size_t)SemiShape<decltype(T)::value>::DOUBLES * sizeof(double); }, A);
 }
 
 }  // namespace elfihip
@@ -382,10 +358,7 @@ int elfihip_semi_loglik(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n,
   double* du = dll + nll;
   double* drho = du + (size_t)G * m;
   double* dsc = drho + (size_t)G * m * m;
-  if (ldx == m)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dX, X, rows * md, hipMemcpyHostToDevice, st));
-  else
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(dX, md, X, (size_t)ldx * sizeof(double), md, rows, hipMemcpyHostToDevice, st));
+  ELFIHIP_TRY(upload_rows(ctx, dX, X, rows, m, ldx));
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dy, y, md, hipMemcpyHostToDevice, st));
   ELFIHIP_TRY(semibsl_dev_impl(ctx, dX, G, n, m, m, dy, prefixes, K, penalties, P, dll, u ? du : nullptr,
                                rho ? drho : nullptr, scores ? dsc : nullptr));

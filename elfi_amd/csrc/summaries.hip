@@ -231,15 +231,11 @@ static int launch_summary(elfihip_ctx* ctx, SumArgs S) {
   if (g > ntiles) g = ntiles;
   if (pipe) {
     auto k = row_summary_kernel<KIND, U, true>;
-    if (lds > 64 * 1024)
-      ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ELFIHIP_TRY(set_lds(ctx, k, lds));
     hipLaunchKernelGGL(k, dim3((unsigned)g), dim3(T), lds, ctx->stream, S);
   } else {
     auto k = row_summary_kernel<KIND, 1, false>;
-    if (lds > 64 * 1024)
-      ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ELFIHIP_TRY(set_lds(ctx, k, lds));
     hipLaunchKernelGGL(k, dim3((unsigned)g), dim3(T), lds, ctx->stream, S);
   }
   return launch_status(ctx, "row_summary_kernel");

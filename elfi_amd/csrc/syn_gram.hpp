@@ -1,7 +1,12 @@
-// What the two synthetic-likelihood kernels share (synlik.hip: the Gaussian forms; semibsl.hip: the semiparametric one):
-// the shape of the LDS buffers, the MFMA step of the m x m sum of outer products and the Cholesky factorisation with an
-// extra row.  Both kernels stage rows 32 at a time, sum every chunk from zero and add it to the running total
-// (two-level summation), so a matrix entry is the same sequence of operations whatever else the launch holds.
+// What the group-statistic kernels share on the device (synlik.hip, semibsl.hip: the two synthetic likelihoods;
+// logratio.hip: BOLFIRE's weighted Gram matrix): the shape of the LDS buffers, the MFMA step of the m x m sum of outer
+// products and, for the likelihoods, the Cholesky factorisation with an extra row.  All stage rows 32 at a time, sum every
+// chunk from zero and add it to the running total (two-level summation), so a matrix entry is the same sequence of
+// operations whatever else the launch holds.  The chunk loops stay written out in each kernel: as a __forceinline__ helper
+// here (zero chk, the gram_step loop, tot += chk) the loop changed all four instruction streams of semibsl_finish_kernel
+// and its VGPR counts (T = 3: 64 -> 124 or 118, T = 4: 96 -> 132 or 156, by the helper's spelling), and a shared
+// tile-to-LDS store changed all four as well (811 -> 812, 837 -> 825, 928 reordered, 1064 -> 1062 instructions); what that
+// costs is not measured.  The host side these files share is in group_args.hpp and common.hpp.
 #pragma once
 
 #include "mfma_f64.hpp"

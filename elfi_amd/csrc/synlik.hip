@@ -22,7 +22,8 @@
 //              quadratic form.  A non-positive pivot or a non-finite value gives -inf.
 // Whitening (rows -> rows W^T, y -> W y) is a launch of its own in front.
 // Determinism: no atomics, fixed order everywhere; a group's result does not depend on G.
-// The shape of the LDS buffers, the MFMA step and the factorisation are shared with semibsl.hip (syn_gram.hpp).
+// The shape of the LDS buffers, the MFMA step and the factorisation are shared with semibsl.hip and logratio.hip
+// (syn_gram.hpp); the check of the lists and their parameter block with semibsl.hip (group_args.hpp).
 #include "common.hpp"
 #include "syn_gram.hpp"
 
@@ -54,6 +55,7 @@ struct SynShape : GramShape<T> {
   using GramShape<T>::SP;
   using GramShape<T>::LP;
   static constexpr int DOUBLES = SL_RC * SP + MP * LP + (MP + 1) * LP + 6 * MP;
+  static_assert(DOUBLES * sizeof(double) <= 160 * 1024);
 };
 
 // rows -> rows W^T (sequential k), one output element per thread and step
@@ -247,16 +249,6 @@ static double unbiased_const(int d, int64_t n) {
   return (double)a;
 }
 
-template <int T>
-static int synlik_launch(elfihip_ctx* ctx, const SynArgs& A, int G) {
-  const size_t bytes = (size_t)SynShape<T>::DOUBLES * sizeof(double);
-  if (bytes > 48 * 1024)
-    ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(synlik_kernel<T>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  hipLaunchKernelGGL(synlik_kernel<T>, dim3(G), dim3(256), bytes, ctx->stream, A);
-  return launch_status(ctx, "synthetic likelihood kernel");
-}
-
 static int synlik_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, int m, int64_t ldx, const void* y,
                         int variant, const void* gamma_adj, const int64_t* prefixes, int K, const double* penalties, int P,
                         const void* loglik) {
@@ -266,17 +258,10 @@ static int synlik_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, i
   ELFIHIP_REQUIRE(ctx, X && y && loglik, "NULL data pointer");
   ELFIHIP_REQUIRE(ctx, variant >= 0 && variant <= 3, "unknown variant %d", variant);
   ELFIHIP_REQUIRE(ctx, variant < 2 || gamma_adj, "variant %d needs gamma_adj", variant);
-  ELFIHIP_REQUIRE(ctx, (prefixes && K >= 1) || (!prefixes && K <= 1), "prefixes and K do not agree (K=%d)", K);
-  ELFIHIP_REQUIRE(ctx, (penalties && P >= 1) || (!penalties && P == 0), "penalties and P do not agree (P=%d)", P);
-  ELFIHIP_REQUIRE(ctx, P == 0 || variant == 0, "penalties go with the standard variant only (variant %d)", variant);
-  if (prefixes) {
-    for (int k = 0; k < K; ++k)
-      ELFIHIP_REQUIRE(ctx, prefixes[k] >= 2 && (k == 0 || prefixes[k] > prefixes[k - 1]),
-                      "prefixes must be ascending and at least 2 (entry %d)", k);
-    ELFIHIP_REQUIRE(ctx, prefixes[K - 1] == n, "the last prefix must be n");
-  }
-  for (int p = 0; p < P; ++p)
-    ELFIHIP_REQUIRE(ctx, penalties[p] >= 0.0 && penalties[p] <= 1.0, "penalty %d is outside [0, 1]", p);
+  ELFIHIP_REQUIRE(ctx, !(penalties && P >= 1) || variant == 0, "penalties go with the standard variant only (variant %d)",
+                  variant);
+  const std::string bad = group_lists_error(prefixes, K, penalties, P, n);
+  ELFIHIP_REQUIRE(ctx, bad.empty(), "%s", bad.c_str());
   return ELFIHIP_OK;
 }
 
@@ -286,17 +271,14 @@ static int synlik_dev_impl(elfihip_ctx* ctx, const double* dX, int G, int64_t n,
                            const double* penalties, int P, double* dll, double* dmean, double* dcov) {
   hipStream_t st = ctx->stream;
   const int Ke = prefixes ? K : 1;
-  // parameter block: [prefixes Ke][konst Ke][penalties P][yw m]
-  std::vector<double> host((size_t)2 * Ke + P);
-  int64_t* hp = reinterpret_cast<int64_t*>(host.data());
-  for (int k = 0; k < Ke; ++k) {
-    hp[k] = prefixes ? prefixes[k] : n;
-    host[Ke + k] = variant == 1 ? unbiased_const(m, hp[k]) : 0.0;
-  }
-  for (int p = 0; p < P; ++p) host[2 * Ke + p] = penalties[p];
-  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve((host.size() + m) * sizeof(double)));
+  std::vector<double> konst(Ke);
+  for (int k = 0; k < Ke; ++k) konst[k] = variant == 1 ? unbiased_const(m, prefixes ? prefixes[k] : n) : 0.0;
+  // parameter block: [prefixes Ke][konst Ke][penalties P], and behind it on the device [yw m]
+  const GroupParams B = group_params(prefixes, K, n, konst.data(), penalties, P);
+  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve((B.words.size() + m) * sizeof(double)));
   double* dpar = ctx->par.as<double>();
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  // pageable host memory: the copy has left it before hipMemcpyAsync returns
+  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, B.words.data(), B.words.size() * sizeof(double), hipMemcpyHostToDevice, st));
   SynArgs A;
   A.X = dX;
   A.n = n;
@@ -306,8 +288,8 @@ static int synlik_dev_impl(elfihip_ctx* ctx, const double* dX, int G, int64_t n,
   A.y = dy;
   A.gamma = dgamma;
   A.prefixes = reinterpret_cast<const int64_t*>(dpar);
-  A.konst = dpar + Ke;
-  A.penalties = P > 0 ? dpar + 2 * Ke : nullptr;
+  A.konst = dpar + B.konst;
+  A.penalties = P > 0 ? dpar + B.pen : nullptr;
   A.K = Ke;
   A.P = P;
   A.loglik = dll;
@@ -317,7 +299,7 @@ static int synlik_dev_impl(elfihip_ctx* ctx, const double* dX, int G, int64_t n,
     const int64_t rows = (int64_t)G * n;
     ELFIHIP_CHECK_HIP(ctx, ctx->scratch.reserve((size_t)rows * m * sizeof(double)));
     double* dXw = ctx->scratch.as<double>();
-    double* dyw = dpar + host.size();
+    double* dyw = dpar + B.words.size();
     const int64_t want = (rows * m + 255) / 256;
     const int grid = (int)std::min<int64_t>(std::max<int64_t>(want, 1), (int64_t)ctx->cu_count * 8);
     hipLaunchKernelGGL(synlik_whiten_kernel, dim3(grid), dim3(256), 0, st, dX, rows, m, ldx, dW, dy, dXw, dyw);
@@ -326,13 +308,9 @@ static int synlik_dev_impl(elfihip_ctx* ctx, const double* dX, int G, int64_t n,
     A.ldx = m;
     A.y = dyw;
   }
-  // the parameter block is pageable host memory: the copy above has left it before hipMemcpyAsync returned
-  switch ((m + 15) / 16) {
-    case 1: return synlik_launch<1>(ctx, A, G);
-    case 2: return synlik_launch<2>(ctx, A, G);
-    case 3: return synlik_launch<3>(ctx, A, G);
-    default: return synlik_launch<4>(ctx, A, G);
-  }
+  return launch_by_tiles(
+      ctx, m, (unsigned)G, "synthetic likelihood kernel", [](auto T) { return synlik_kernel<decltype(T)::value>; },
+      [](auto T) { return (size_t)SynShape<decltype(T)::value>::DOUBLES * sizeof(double); }, A);
 }
 
 }  // namespace elfihip
@@ -370,10 +348,7 @@ int elfihip_syn_loglik(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, 
   double* dll = ctx->out.as<double>();
   double* dmean = dll + nll;
   double* dcov = dmean + (size_t)G * m;
-  if (ldx == m)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dX, X, rows * md, hipMemcpyHostToDevice, st));
-  else
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(dX, md, X, (size_t)ldx * sizeof(double), md, rows, hipMemcpyHostToDevice, st));
+  ELFIHIP_TRY(upload_rows(ctx, dX, X, rows, m, ldx));
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dy, y, md, hipMemcpyHostToDevice, st));
   if (gamma_adj) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dgam, gamma_adj, md, hipMemcpyHostToDevice, st));
   if (W) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dW, W, (size_t)m * md, hipMemcpyHostToDevice, st));

@@ -221,12 +221,7 @@ int elfihip_welford_update(elfihip_ctx* ctx, const double* X, int64_t n, int m, 
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dstate, st.data(), ns * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((size_t)n * m * sizeof(double)));
   double* dX = ctx->in.as<double>();
-  if (ldx == m)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dX, X, (size_t)n * m * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  else
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(dX, (size_t)m * sizeof(double), X, (size_t)ldx * sizeof(double),
-                                            (size_t)m * sizeof(double), (size_t)n, hipMemcpyHostToDevice,
-                                            ctx->stream));
+  ELFIHIP_TRY(upload_rows(ctx, dX, X, (size_t)n, m, ldx));
   ELFIHIP_TRY(welford_dev_impl(ctx, dX, n, m, m, dstate));
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(st.data(), dstate, ns * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -147,11 +147,7 @@ int elfihip_weighted_var(elfihip_ctx* ctx, const double* X, int64_t n, int m, in
   ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((size_t)m * sizeof(double)));
   double* dX = ctx->in.as<double>();
   double* dw = w ? dX + (size_t)n * m : nullptr;
-  if (ldx == m)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dX, X, xb, hipMemcpyHostToDevice, st));
-  else
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(dX, (size_t)m * sizeof(double), X, (size_t)ldx * sizeof(double),
-                                            (size_t)m * sizeof(double), (size_t)n, hipMemcpyHostToDevice, st));
+  ELFIHIP_TRY(upload_rows(ctx, dX, X, (size_t)n, m, ldx));
   if (w) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dw, w, wb, hipMemcpyHostToDevice, st));
   ELFIHIP_TRY(wvar_dev_impl(ctx, dX, n, m, m, dw, ctx->out.as<double>()));
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(s2, ctx->out.as<double>(), (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));

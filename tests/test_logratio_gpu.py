@@ -84,9 +84,9 @@ def test_parity_with_truth(hip_ctx, gold, ci):
 
 
 # 2 ---------------------------------------------------------------------------------------------------------------
-def test_groups_in_one_call_equal_single_calls(hip_ctx):
+def _groups_in_one_call_equal_single_calls(m):
     import elfi_amd
-    X, M, obs = _five_groups()
+    X, M, obs = _five_groups(m=m)
     lr, p = elfi_amd.log_ratio(X, M, obs, return_parts=True)
     assert lr.shape == (5, 3) and np.all(p['status'] == 0) and len(set(lr[:, 0])) == 5
     for g in range(5):
@@ -96,6 +96,14 @@ def test_groups_in_one_call_equal_single_calls(hip_ctx):
             assert np.array_equal(q[k][0], p[k][g]), (g, k)
     flat = elfi_amd.log_ratio(X.reshape(-1, X.shape[2]), M, obs, n_groups=5)
     assert np.array_equal(flat, lr)
+
+
+def test_groups_in_one_call_equal_single_calls(hip_ctx):
+    _groups_in_one_call_equal_single_calls(6)
+
+
+def test_groups_in_one_call_equal_single_calls_at_three_tiles(hip_ctx):
+    _groups_in_one_call_equal_single_calls(40)     # 33 <= m <= 48: the three-tile instance of the kernel
 
 
 def _dev_call(ctx, X, M, obs, layout_x, layout_m, G, C=1.0, class_min=0.0, max_iter=100):
@@ -122,15 +130,37 @@ def _dev_call(ctx, X, M, obs, layout_x, layout_m, G, C=1.0, class_min=0.0, max_i
     return outs['lr'].check().reshape(G, k), parts
 
 
-@pytest.mark.parametrize('m', [6, 7])
+@pytest.mark.parametrize('m', [6, 7, 40])      # (40: the three-tile instance of the kernel)
 def test_dev_form_at_every_layout_equals_host_form(hip_ctx, m):
     import elfi_amd
     X, M, obs = _five_groups(m=m)
     X2 = X.reshape(-1, m)
     host = elfi_amd.log_ratio(X2, M, obs, n_groups=5, return_parts=True)
+    assert np.all(host[1]['status'] == 0)
     for lx, lm in zip(DL.LAYOUTS, DL.LAYOUTS[::-1]):
         got = _dev_call(hip_ctx, X2, M, obs, lx, lm, 5)
         assert _same(got, host), (lx, lm)
+
+
+def test_c_entry_point_refuses_bad_arguments(hip_ctx):
+    """ELFIHIP_ERR_ARG before any launch: the output keeps its sentinel."""
+    from elfi_amd import _lib
+    from elfi_amd.logratio import DEFAULT_TOL
+    SENTINEL = -12345.5
+    X, M, obs = np.zeros((8, 3)), np.ones((6, 3)), np.zeros((1, 3))
+    lr = np.full(2, SENTINEL)
+    inf, nan = float('inf'), float('nan')
+
+    def call(G=1, n=8, m=3, ldx=3, nm=6, ldm=3, k=1, C=1.0, class_min=0.0, tol=DEFAULT_TOL, max_iter=100, out=lr):
+        hip_ctx.call("elfihip_log_ratio", _lib.ptr(X), G, n, m, ldx, _lib.ptr(M), nm, ldm, _lib.ptr(obs), k, C, class_min, tol,
+                     max_iter, _lib.ptr(out), None, None, None, None, None, None)
+    for kw in (dict(m=65), dict(n=0), dict(nm=0), dict(ldx=2), dict(ldm=2), dict(k=0), dict(C=0.0), dict(C=inf), dict(C=nan),
+               dict(class_min=1.0), dict(class_min=-0.1), dict(tol=-1.0), dict(max_iter=-1), dict(out=None)):
+        with pytest.raises(ValueError):
+            call(**kw)
+        assert np.all(lr == SENTINEL), kw
+    call()                                   # the call itself is sound: good arguments go through
+    assert lr[0] != SENTINEL and lr[1] == SENTINEL
 
 
 # 3 ---------------------------------------------------------------------------------------------------------------

@@ -158,7 +158,42 @@ def test_device_pointer_form_and_pitched_rows_equal_the_host_form(hip_ctx):
         assert np.array_equal(dmean.cpu().numpy(), wmean) and np.array_equal(dcov.cpu().numpy(), wcov)
 
 
-# 4 ---------------------------------------------------------------------------------------------------------------
+def test_c_entry_point_refuses_bad_arguments(hip_ctx):
+    """ELFIHIP_ERR_ARG before any launch: the output keeps its sentinel.  The lists are refused in the words
+    elfihip_semi_loglik uses for the same lists (one check serves both: csrc/group_args.hpp)."""
+    from elfi_amd import _lib
+    SENTINEL = -12345.5
+    X, y, gam = np.zeros((8, 3)), np.zeros(3), np.zeros(3)
+    ll = np.full(4, SENTINEL)
+    pre, pens = np.array([4, 8], dtype=np.int64), np.array([0.5, 1.5])
+
+    def call(G=1, n=8, m=3, ldx=3, variant=0, gamma=None, pre=None, K=0, pens=None, P=0):
+        hip_ctx.call("elfihip_syn_loglik", _lib.ptr(X), G, n, m, ldx, _lib.ptr(y), None, variant, _lib.ptr(gamma),
+                     _lib.ptr(pre), K, _lib.ptr(pens), P, _lib.ptr(ll), None, None)
+
+    def semi_text(pre=None, K=0, pens=None, P=0):
+        with pytest.raises(ValueError) as exc:
+            hip_ctx.call("elfihip_semi_loglik", _lib.ptr(X), 1, 8, 3, 3, _lib.ptr(y), _lib.ptr(pre), K, _lib.ptr(pens), P,
+                         _lib.ptr(ll), None, None, None)
+        return str(exc.value)
+
+    reversed_pre, bad_pens = dict(pre=pre[::-1].copy(), K=2), dict(pens=pens, P=2)
+    for kw in (dict(m=65), dict(n=1), dict(ldx=2), dict(G=0), dict(variant=4), dict(variant=2), reversed_pre,
+               dict(pre=pre[:1].copy(), K=1), dict(pre=np.array([1, 8], dtype=np.int64), K=2), bad_pens,
+               dict(variant=1, pens=np.array([0.5]), P=1)):
+        with pytest.raises(ValueError) as exc:
+            call(**kw)
+        assert np.all(ll == SENTINEL), kw
+        if kw is reversed_pre or kw is bad_pens:
+            assert str(exc.value) == semi_text(**kw)
+            assert np.all(ll == SENTINEL), kw
+    assert semi_text(**reversed_pre) == 'prefixes must be ascending and at least 2 (entry 1)'
+    assert semi_text(**bad_pens) == 'penalty 1 is outside [0, 1]'
+    call(variant=2, gamma=gam, pre=pre, K=2)     # the call itself is sound: good arguments go through
+    assert not np.any(ll[:2] == SENTINEL) and np.all(ll[2:] == SENTINEL)
+
+
+# 4---------------------------------------------------------------------------------------------------------------
 def test_singular_and_non_finite_groups_give_minus_infinity(hip_ctx):
     import elfi_amd
     X, y, W, gamma = R.make_case(*R.CASES[1])
