@@ -35,6 +35,8 @@ from .synlik import (HipBSL, hip_bsl_class, log_SL_stdev, robust_likelihood, sel
                      semi_loglik, semiparametric_likelihood, standard_likelihood, syn_loglik, unbiased_likelihood)
 from .logratio import HipLogisticRegression, hip_logistic_regression_class, log_ratio  # noqa: F401
 from .bolfire import HipBOLFIRE, HipBOLFIREPosterior, hip_bolfire_class  # noqa: F401
+from .twostage import (HipTwoStageSelection, hip_two_stage_selection_class, knn_entropy, mrsse,  # noqa: F401
+                       subset_best)
 
 
 

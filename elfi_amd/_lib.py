@@ -161,6 +161,18 @@ PROTOTYPES = {
                                         C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double,
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "elfihip_knn_entropy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int,
+                                      C.c_void_p, C.c_void_p]),
+    "elfihip_knn_entropy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int,
+                                          C.c_void_p, C.c_void_p]),
+    "elfihip_mrsse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64,
+                                C.c_int64, C.c_void_p]),
+    "elfihip_mrsse_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_void_p,
+                                    C.c_int64, C.c_int64, C.c_void_p]),
+    "elfihip_subset_best": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "elfihip_subset_best_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "elfihip_row_summary": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int,
                                       C.c_void_p]),
     "elfihip_row_summary_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int,

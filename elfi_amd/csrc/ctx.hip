@@ -164,6 +164,7 @@ int elfihip_ctx_destroy(elfihip_ctx* ctx) {
     ctx->par.release();
     ctx->scratch.release();
     ctx->stat.release();
+    ctx->sel.release();
     ctx->keep.release();
     ctx->rows.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

@@ -396,6 +396,47 @@ int elfihip_log_ratio_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t
                           int max_iter, double* dlogratio, double* dcoef, double* dintercept, double* dmean,
                           double* dscale, int* dn_iter, int* dstatus);
 
+/* ------------------------------------------------------------------ summary-statistic selection
+ * The data-parallel steps of TwoStageSelection (Nunes & Balding 2010; elfi/methods/diagnostics.py:15-289), each for all
+ * candidate combinations in one call (csrc/twostage.hip).  Deterministic: fixed-order sums, no atomics; a group's result
+ * does not depend on G.  Every argument is checked before anything is launched; on ELFIHIP_ERR_ARG no output is touched.
+ *
+ * elfihip_knn_entropy (diagnostics.py:214-253): T holds G groups of n points in q dimensions, row-major with pitch ldt,
+ * group g = rows g n ... g n + n - 1.  entropy (G):
+ *   E = log(pi^(q/2) / Gamma(q/2 + 1)) - psi(k) + log n + (q / n) sum_i log R_ik,
+ * R_ik = the euclidean distance from point i to its k-th nearest neighbour where the point itself is the first, at
+ * distance 0 (cKDTree.query(theta_i, k)[0][-1]): k = 4 is the third other point; k = 1, or k coincident points, give -inf;
+ * k > n gives +inf (the tree pads with inf).  kth (G, n) or NULL: the R_ik.  A squared distance is summed left to right over
+ * the dimensions.  1 <= q <= 32, 1 <= k <= 16, n >= 1 (at most 65535 * 256 points per group).
+ *
+ * elfihip_mrsse (:255-289): mrsse (G) = (1 / J) sum_j sqrt(sum_{i,d} (T[g][i][d] - closest[j][d])^2) with closest (J, q) at
+ * pitch ldc, J <= 65535, the mean over j taken in index order.
+ *
+ * elfihip_subset_best: what one elfi.Rejection per combination selects (:172-212) from ONE pool of simulations.  X (n, m)
+ * with pitch ldx are the summaries, y (m) the observed ones, masks (C, m) hold 0.0 / 1.0 (any other entry and an all-zero
+ * mask are argument errors).  vals (C, min(k, n)) and rows (C, min(k, n)): the k smallest euclidean distances of every
+ * combination over its selected columns, with their row numbers, ascending by (distance, row), NaN last.  The distances
+ * are elfihip_dist_multiw's with the masks as weights, bit for bit, so a non-finite value in an UNSELECTED column makes
+ * the row's distance 0 * inf = NaN and ranks it last.  Composed on the device from elfihip_dist_multiw_dev (blocks of at
+ * most 64 combinations and 1 GiB), elfihip_topk_smallest_dev per column and a sort of the survivors; no (n, C) matrix
+ * reaches the host.
+ *
+ * Host forms: host pointers, synchronise.  _dev forms: device pointers and the context's stream; masks is a HOST array in
+ * both forms (it is checked before the launch).  elfihip_knn_entropy_dev and elfihip_mrsse_dev do not synchronise;
+ * elfihip_subset_best_dev synchronises once per block of combinations (it reads the selection's time-out flags). */
+int elfihip_knn_entropy(elfihip_ctx* ctx, const double* T, int64_t G, int64_t n, int q, int64_t ldt, int k,
+                        double* entropy, double* kth);
+int elfihip_knn_entropy_dev(elfihip_ctx* ctx, const double* dT, int64_t G, int64_t n, int q, int64_t ldt, int k,
+                            double* dentropy, double* dkth);
+int elfihip_mrsse(elfihip_ctx* ctx, const double* T, int64_t G, int64_t n, int q, int64_t ldt, const double* closest,
+                  int64_t J, int64_t ldc, double* mrsse);
+int elfihip_mrsse_dev(elfihip_ctx* ctx, const double* dT, int64_t G, int64_t n, int q, int64_t ldt,
+                      const double* dclosest, int64_t J, int64_t ldc, double* dmrsse);
+int elfihip_subset_best(elfihip_ctx* ctx, const double* X, int64_t n, int m, int64_t ldx, const double* y,
+                        const double* masks, int64_t C, int64_t k, double* vals, int64_t* rows);
+int elfihip_subset_best_dev(elfihip_ctx* ctx, const double* dX, int64_t n, int m, int64_t ldx, const double* dy,
+                            const double* masks, int64_t C, int64_t k, double* dvals, int64_t* drows);
+
 /* ------------------------------------------------------------------ summaries
  * Row-wise summary statistics that ELFI's example models install as elfi.Summary operations, with
  * NumPy's exact (pairwise) summation order, i.e. bit-identical results:
