@@ -37,6 +37,7 @@ from .logratio import HipLogisticRegression, hip_logistic_regression_class, log_
 from .bolfire import HipBOLFIRE, HipBOLFIREPosterior, hip_bolfire_class  # noqa: F401
 from .twostage import (HipTwoStageSelection, hip_two_stage_selection_class, knn_entropy, mrsse,  # noqa: F401
                        subset_best)
+from .adjust import HipLinearAdjustment, adjust_posterior, hip_linear_adjustment_class, linear_adjust  # noqa: F401
 
 
 

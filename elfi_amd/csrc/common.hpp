@@ -79,6 +79,7 @@ struct elfihip_ctx {
   elfihip::DevBuf in, out, par, scratch;
   elfihip::DevBuf stat;   // workgroup partials of the fused adaptive-distance pass (adaptive.hip; topk.hip owns `scratch`)
   elfihip::DevBuf sel;    // twostage.hip: a block of subset distances and its survivors; the partial sums of the entropy
+                          // adjust.hip: the tile factors, the tile sums, the jobs' means and coefficients
   // the distances the last host-form distance call returned, kept on the device for the sampler state
   // (elfihip_kept_distances / elfihip_reject_push_kept): (keep_n, keep_cols) row-major; the epoch names the call
   elfihip::DevBuf keep;

@@ -437,6 +437,37 @@ int elfihip_subset_best(elfihip_ctx* ctx, const double* X, int64_t n, int m, int
 int elfihip_subset_best_dev(elfihip_ctx* ctx, const double* dX, int64_t n, int m, int64_t ldx, const double* dy,
                             const double* masks, int64_t C, int64_t k, double* dvals, int64_t* drows);
 
+/* ------------------------------------------------------------------ regression adjustment
+ * elfi.LinearAdjustment / elfi.adjust_posterior (elfi/methods/post_processing.py:195-253) for G groups of n accepted rows
+ * and K nested prefixes of every group in one call (csrc/adjust.hip).  X (G n, m) row-major with pitch ldx: the summaries
+ * minus the observed summaries; Y (G n, q) with pitch ldy: the parameters, one column each; group g = rows g n ...
+ * g n + n - 1 of both.  1 <= m <= 64, 1 <= q <= 16, n >= 2.  prefixes (K) as for elfihip_syn_loglik: ascending, >= 2, the
+ * last == n; NULL = {n} (Ke = 1, else Ke = K).  A job is one (g, k): the first p_k rows of group g.  Per job and response:
+ *     b = argmin || (y - ybar) - (X - xbar) b ||_2,   intercept = ybar - xbar.b,   rss = the minimum (a sum of squares),
+ *     adjusted_i = y_i - x_i.b   with the UNCENTRED x_i, summed left to right (what LinearAdjustment._adjust computes)
+ * by a Householder QR of the centred [X | Y] in float64: tiles of 256 rows (128 when m + q > 40), the tile factors folded
+ * pairwise in a fixed binary tree; no Gram matrix is formed, so the result does not depend on the columns' scales (the
+ * reference's SVD does).  rss is the squared norm of the response's column of R22.
+ * adjusted (G, Ke, n, q), required: rows at or beyond p_k are NaN.  Each may be NULL: coef (G, Ke, q, m), intercept
+ * (G, Ke, q), rss (G, Ke, q), status (G, Ke), per job:
+ *   0 ok;
+ *   2 a non-finite value in the job's rows;
+ *   3 rank-deficient: p_k - 1 < m, a constant column (minimum == maximum), or a column j with
+ *     |R_jj| <= max(p_k, m) eps ||centred column j||_2 (scale-invariant).  The reference returns the minimum-norm
+ *     solution there; the device does not.
+ * A job with status 2 or 3 has NaN outputs.  None of these is an error return: the call gives ELFIHIP_OK.
+ * Every argument is checked before anything is launched; on ELFIHIP_ERR_ARG no output is touched.
+ * Host form: host pointers, synchronises.  _dev form: X, Y and every output are device pointers on the context's stream,
+ * no synchronisation; prefixes is a host array in both forms.
+ * Deterministic: fixed-order sums, no atomics; a job's result does not depend on G or on the other jobs, and prefix p has
+ * the bits of a group of p rows. */
+int elfihip_linear_adjust(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, int m, int64_t ldx, const double* Y,
+                          int q, int64_t ldy, const int64_t* prefixes, int K, double* adjusted, double* coef,
+                          double* intercept, double* rss, int* status);
+int elfihip_linear_adjust_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx,
+                              const double* dY, int q, int64_t ldy, const int64_t* prefixes, int K, double* dadjusted,
+                              double* dcoef, double* dintercept, double* drss, int* dstatus);
+
 /* ------------------------------------------------------------------ summaries
  * Row-wise summary statistics that ELFI's example models install as elfi.Summary operations, with
  * NumPy's exact (pairwise) summation order, i.e. bit-identical results:
