@@ -1,7 +1,9 @@
-"""ELFI's two example models with the whole simulation on the GPU: same priors, same node names, same inference calls.
+"""ELFI's example models with the whole simulation on the GPU: same priors, same node names, same inference calls.
 
     m = elfi_amd.fused_models.ma2_model(n_obs=100, seed_obs=4)        # elfi.examples.ma2.get_model(...)
     m = elfi_amd.fused_models.gauss_model(n_obs=50, seed_obs=4)       # elfi.examples.gauss.get_model(...)
+    m = elfi_amd.fused_models.arch_model(n_obs=100, seed_obs=4)       # elfi.examples.arch.get_model(...)
+    m = elfi_amd.fused_models.mg1_model(n_obs=50, seed_obs=4)         # elfi.examples.mg1.get_model(...)
     elfi_amd.HipRejection(m['d'], batch_size=10**6, seed=1).sample(1000, n_sim=10**8)
 
 The reference's Simulator node draws the series on the host (MA2: random_state.randn(batch, n_obs + 2),
@@ -14,18 +16,27 @@ Summary nodes pick their column and the Distance node is elfi.Distance over elfi
 generated exactly as the reference's get_model does (its own simulator on the host with RandomState(seed_obs)) and
 reduced to the observed summaries once, at model construction.
 
+arch_model / mg1_model are the reference's time-series examples (elfi/examples/arch.py, mg1.py) built the same way on
+csrc/series.hip: each simulation has a serial recurrence (a chain of dependent square roots; two running sums and a
+maximum), which one lane walks while the draws and the reductions keep the wavefront busy.  Their Simulator node returns
+all summaries of a simulation -- ARCH: the (batch, 2 + L + L (L - 1) / 2) columns MU, VAR, AC_1 .., PW_1_2 ..; M/G/1:
+(batch, n_obs + n_quantiles) = [log inter-departure times | quantiles] -- and the Summary nodes slice columns; M/G/1's
+log_identity is what HipBSL / syn_loglik take.  On given draws series, summaries and quantiles are the reference's bit
+for bit, the logarithms within 4 ulp (tests/test_series_models_gpu.py).
+
 The draws are the device generator's, not MT19937's: a run of this model is a different (equally valid) random
 realisation than a run of elfi.examples.*.get_model with the same seed; the arithmetic on given draws is bit-identical
 to the reference's (tests/test_summaries_gpu.py, tests/test_gauss_gpu.py).
 """
 import sys
 from functools import partial
+from itertools import combinations
 
 import numpy as np
 
 from .distance import HipDistance, randn_rows
 from .priors import SIMULATOR_STREAM_BASE
-from .summaries import gauss_distance, ma2_draw_distance
+from .summaries import arch_summaries, gauss_distance, ma2_draw_distance, mg1_summaries
 
 
 def _elfi():
@@ -105,6 +116,88 @@ def gauss_model(n_obs=50, true_params=None, seed_obs=None, device_priors=True):
     elfi.Summary(first_column, m['gauss'], name='ss_mean')
     elfi.Summary(second_column, m['gauss'], name='ss_var')
     elfi.Distance(HipDistance('euclidean'), m['ss_mean'], m['ss_var'], name='d')
+    return m
+
+
+def column(y, j=0):
+    return np.asarray(y)[:, j]
+
+
+def columns(y, start=0, stop=None):
+    return np.asarray(y)[:, start:stop]
+
+
+def _per_simulation(batch_size, *params):
+    """Parameters fixed to one value (model.generate(..., with_values=...)) are repeated over the batch."""
+    params = [np.asarray(p, dtype=np.float64).reshape(-1) for p in params]
+    n = max([int(batch_size)] + [p.shape[0] for p in params])
+    return [np.repeat(p, n) if p.shape[0] == 1 and n > 1 else p for p in params]
+
+
+def arch_summary_rows(t1, t2, n_obs=100, n_lags=5, batch_size=1, random_state=None):
+    """Simulator operation: (batch, 2 + L + L (L - 1) / 2) summaries MU, VAR, AC_1 .., PW_1_2 .. of ARCH(1) series drawn,
+    run and reduced on the device."""
+    t1, t2 = _per_simulation(batch_size, t1, t2)
+    return arch_summaries(t1, t2, n_obs=n_obs, n_lags=n_lags, seed=_seed_of(random_state), stream=SIMULATOR_STREAM_BASE)
+
+
+def arch_names(n_lags=5):
+    lags = range(1, n_lags + 1)
+    return ['MU', 'VAR'] + ['AC_%d' % i for i in lags] + ['PW_%d_%d' % ij for ij in combinations(lags, 2)]
+
+
+def arch_model(n_obs=100, true_params=None, seed_obs=None, n_lags=5, device_priors=True):
+    """elfi.examples.arch.get_model(n_obs, true_params, seed_obs, n_lags) with the simulation on the device; nodes t1,
+    t2, Y, MU, VAR, AC_i, PW_i_j, d.  The node Y returns the (batch, m) summaries, the Summary nodes pick their column.
+    device_priors: the two uniform priors draw on the device as well (elfi_amd.priors.uniform; False: SciPy's)."""
+    elfi = _elfi()
+    from elfi.examples import arch
+    if true_params is None:
+        true_params = [0.3, 0.7]
+    y = arch.arch(*true_params, n_obs=n_obs, random_state=np.random.RandomState(seed_obs))
+    lags = range(1, n_lags + 1)
+    obs = np.column_stack([arch.sample_mean(y), arch.sample_variance(y)] + [arch.autocorr(y, i) for i in lags] +
+                          [arch.pairwise_autocorr(y, i, j) for i, j in combinations(lags, 2)])
+    m = elfi.ElfiModel()
+    from . import priors
+    uniform = priors.uniform if device_priors else 'uniform'
+    elfi.Prior(uniform, -1, 2, model=m, name='t1')
+    elfi.Prior(uniform, 0, 1, model=m, name='t2')
+    elfi.Simulator(partial(arch_summary_rows, n_obs=n_obs, n_lags=n_lags), m['t1'], m['t2'], observed=obs, name='Y')
+    ss = [elfi.Summary(partial(column, j=k), m['Y'], name=name) for k, name in enumerate(arch_names(n_lags))]
+    elfi.Distance(HipDistance('euclidean'), *ss, name='d')
+    return m
+
+
+def mg1_summary_rows(t1, t2, t3, n_obs=50, q=None, batch_size=1, random_state=None):
+    """Simulator operation: (batch, n_obs + nq) = [log inter-departure times | quantiles] of M/G/1 series drawn, run,
+    sorted and reduced on the device."""
+    t1, t2, t3 = _per_simulation(batch_size, t1, t2, t3)
+    logy, quant = mg1_summaries(t1, t2, t3, n_obs=n_obs, q=q, seed=_seed_of(random_state), stream=SIMULATOR_STREAM_BASE)
+    return np.hstack((logy, quant))
+
+
+def mg1_model(n_obs=50, true_params=None, seed_obs=None, n_quantiles=10, device_priors=True):
+    """elfi.examples.mg1.get_model(n_obs, true_params, seed_obs, n_quantiles) with the simulation on the device; nodes t1,
+    t2, t3, MG1, log_identity, quantiles, d.  The node MG1 returns [log y | quantiles] per simulation, the two Summary
+    nodes slice it.  device_priors: t1 and t3 draw on the device (t2, whose location is the node t1, stays SciPy's)."""
+    elfi = _elfi()
+    from elfi.examples import mg1
+    if true_params is None:
+        true_params = [1., 5., 0.2]
+    y = mg1.MG1(*true_params, n_obs=n_obs, random_state=np.random.RandomState(seed_obs))
+    q = np.linspace(0, 1, n_quantiles)
+    obs = np.hstack((mg1.log_identity(y), mg1.quantiles(y, q)))
+    m = elfi.ElfiModel()
+    from . import priors
+    uniform = priors.uniform if device_priors else 'uniform'
+    elfi.Prior(uniform, 0, 10, model=m, name='t1')
+    elfi.Prior('uniform', m['t1'], 10, model=m, name='t2')   # t2 - t1 ~ U(0, 10)
+    elfi.Prior(uniform, 0, 0.5, model=m, name='t3')
+    elfi.Simulator(partial(mg1_summary_rows, n_obs=n_obs, q=q), m['t1'], m['t2'], m['t3'], observed=obs, name='MG1')
+    elfi.Summary(partial(columns, stop=n_obs), m['MG1'], name='log_identity')
+    elfi.Summary(partial(columns, start=n_obs), m['MG1'], name='quantiles')
+    elfi.Distance(HipDistance('euclidean', w=(1 / 100) ** q), m['quantiles'], name='d')
     return m
 
 

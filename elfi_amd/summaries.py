@@ -8,6 +8,8 @@ leading dimension of 1 -- elfi/model/elfi_model.py:915-943, elfi/compiler.py:94-
     ss_mean(y)           elfi/examples/gauss.py:142-156
     ss_var(y)            elfi/examples/gauss.py:159-173
     ma2_distance(...)    the fused MA2 path: simulator arithmetic + both summaries + distance
+    arch_summaries(...)  the fused ARCH(1) example: series + 17 summaries [+ distance]     elfi/examples/arch.py
+    mg1_summaries(...)   the fused M/G/1 example: series, its logarithm, quantiles [+ distance]  elfi/examples/mg1.py
 
     S1 = elfi.Summary(elfi_amd.autocov, Y);  S2 = elfi.Summary(elfi_amd.autocov, Y, 2)
 
@@ -131,3 +133,140 @@ def gauss_distance(mu, sigma, observed, n_obs=50, z=None, seed=0, stream=0, retu
              _lib.ptr(D))
     _lib.remember_kept(D, ctx)
     return (S1, S2, D, Y) if return_y else (S1, S2, D)
+
+
+# ---- the time-series example models (csrc/series.hip) ---------------------------------------------------------------
+SERIES_MAX_OBS = 2048       # include/elfihip.h: ELFIHIP_SERIES_MAX_OBS (a simulation keeps its series in LDS)
+ARCH_MAX_LAGS = 8
+MG1_MAX_QUANTILES = 64
+
+
+def _params(n, *ts):
+    out = []
+    for t in ts:
+        t = np.asarray(t, dtype=np.float64).reshape(-1)
+        if t.shape[0] not in (1, n):
+            raise ValueError('parameters must be scalars or hold one value per simulation (%d)' % n)
+        out.append(np.ascontiguousarray(np.broadcast_to(t, (n,))))
+    return out
+
+
+def _batch_of(*ts):
+    return max(np.asarray(t).reshape(-1).shape[0] for t in ts)
+
+
+def arch_n_summaries(n_lags=5):
+    return 2 + n_lags + n_lags * (n_lags - 1) // 2
+
+
+def arch_summaries(t1, t2, n_obs=100, n_lags=5, noise=None, seed=0, stream=0, observed=None, return_series=False,
+                   ctx=None):
+    """The ARCH(1) example (elfi/examples/arch.py) as ONE device operation: the series e_i = xi_i sqrt(0.2 + t2 e_{i-1}^2),
+    y_i = t1 y_{i-1} + e_i and its 2 + L + L (L - 1) / 2 summaries -- sample_mean, sample_variance, autocorr at lags 1 .. L =
+    n_lags, pairwise_autocorr(i, j), i < j -- in the reference's column order MU, VAR, AC_1 .., PW_1_2 ...
+
+    t1, t2: (batch,) or scalars.  noise: (batch, n_obs + 2) standard normals (for the n_obs given; any other shape is a
+    ValueError), columns 0 .. n_obs what the reference draws
+    as `normal(size=(batch, n_obs + 1))` and the last column its `normal(size=batch)` -- results bit-identical to the
+    reference's NumPy; noise=None draws on the device (Philox4x32-10 keyed by `seed`, counter stream `stream`).
+    observed: the observed summaries; with them the euclidean distance is returned too.
+    Returns S (batch, m) [, series (batch, n_obs)] [, d (batch,)]."""
+    n_obs, n_lags = int(n_obs), int(n_lags)
+    if not 1 <= n_lags <= ARCH_MAX_LAGS:
+        raise ValueError('n_lags must be in [1, %d]' % ARCH_MAX_LAGS)
+    if noise is not None:
+        noise = np.asarray(noise)
+        if noise.ndim != 2 or noise.shape[1] != n_obs + 2:
+            raise ValueError('noise must be (batch, n_obs + 2) = (batch, %d)' % (n_obs + 2))
+    if n_obs < n_lags + 2:
+        raise ValueError('need n_obs >= n_lags + 2')
+    if n_obs > SERIES_MAX_OBS:
+        raise ValueError('series of at most %d observations' % SERIES_MAX_OBS)
+    n = noise.shape[0] if noise is not None else _batch_of(t1, t2)
+    t1, t2 = _params(n, t1, t2)
+    m = arch_n_summaries(n_lags)
+    obs = None
+    if observed is not None:
+        obs = np.ascontiguousarray(np.asarray(observed, dtype=np.float64).reshape(-1))
+        if obs.shape[0] != m:
+            raise ValueError('observed must hold the %d observed summaries' % m)
+    if noise is not None:
+        noise = np.ascontiguousarray(noise, dtype=np.float64)
+    S = np.empty((n, m))
+    Y = np.empty((n, n_obs)) if return_series else None
+    D = np.empty(n) if obs is not None else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_arch_summaries", _lib.ptr(noise), C.c_uint64(int(seed)), C.c_uint64(int(stream)), n, n_obs, n_lags,
+             _lib.ptr(t1), _lib.ptr(t2), _lib.ptr(obs), _lib.ptr(S), _lib.ptr(Y), _lib.ptr(D))
+    return tuple(a for a in (S, Y, D) if a is not None) if (return_series or obs is not None) else S
+
+
+def quantile_positions(q, n):
+    """np.quantile(method='linear') on n sorted values, as positions: (lo, hi, t) -- the two neighbours of the virtual index
+    (n - 1) q and the interpolation weight (NumPy's _get_indexes / _get_gamma: at the upper end both neighbours are the last
+    element, which NumPy names -1, and the weight is measured from that name)."""
+    q = np.asarray(q, dtype=np.float64).reshape(-1)
+    virt = (n - 1) * q
+    prev = np.floor(virt)
+    nxt = prev + 1
+    above = virt >= n - 1
+    prev[above], nxt[above] = -1, -1
+    below = virt < 0
+    prev[below], nxt[below] = 0, 0
+    t = virt - prev
+    return (prev.astype(np.int64) % n).astype(np.int32), (nxt.astype(np.int64) % n).astype(np.int32), t
+
+
+def mg1_summaries(t1, t2, t3, n_obs=50, q=None, draws=None, seed=0, stream=0, observed=None, w=None, return_series=False,
+                  return_draws=False, ctx=None):
+    """The M/G/1 queue example (elfi/examples/mg1.py) as ONE device operation: inter-departure times y_i = U_i + max(0,
+    sum_w - sum_x) from arrivals every (1 / t3) E and service times t1 + (t2 - t1) V, their logarithm (log_identity) and
+    the quantiles np.quantile(y, q, axis=1).T (default q: 10 equidistant in [0, 1], the example's).
+
+    draws: (E, V), each (batch, n_obs) -- standard exponentials and uniforms in [0, 1), what the reference consumes as
+    standard_exponential((n_obs, batch)).T and random_sample((n_obs, batch)).T: series and quantiles bit-identical to the
+    reference's NumPy; draws=None draws on the device (`seed`; counter streams `stream` and `stream + 1`).
+    observed: the observed quantiles, w: weights; with `observed` the (weighted) euclidean distance is returned too.
+    Returns log_y (batch, n_obs), quantiles (batch, nq) [, y] [, E, V] [, d]."""
+    n_obs = int(n_obs)
+    q = np.linspace(0, 1, 10) if q is None else np.asarray(q, dtype=np.float64).reshape(-1)
+    if not 1 <= q.shape[0] <= MG1_MAX_QUANTILES:
+        raise ValueError('1 to %d quantiles' % MG1_MAX_QUANTILES)
+    if not np.all((q >= 0) & (q <= 1)):
+        raise ValueError('Quantiles must be in the range [0, 1]')
+    E = V = None
+    if draws is not None:
+        E, V = [np.asarray(a) for a in draws]
+        if E.ndim != 2 or E.shape != V.shape or E.shape[1] != n_obs:
+            raise ValueError('draws must be two (batch, n_obs) = (batch, %d) arrays: exponentials and uniforms' % n_obs)
+    if n_obs < 2:
+        raise ValueError('need n_obs >= 2')
+    if n_obs > SERIES_MAX_OBS:
+        raise ValueError('series of at most %d observations' % SERIES_MAX_OBS)
+    if w is not None and observed is None:
+        raise ValueError('weights need the observed quantiles')
+    nq = q.shape[0]
+    obs = None
+    if observed is not None:
+        obs = np.ascontiguousarray(np.asarray(observed, dtype=np.float64).reshape(-1))
+        if obs.shape[0] != nq:
+            raise ValueError('observed must hold the %d observed quantiles' % nq)
+    if w is not None:
+        w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(-1))
+        if w.shape[0] != nq:
+            raise ValueError('w must hold one weight per quantile (%d)' % nq)
+    n = E.shape[0] if E is not None else _batch_of(t1, t2, t3)
+    t1, t2, t3 = _params(n, t1, t2, t3)
+    if E is not None:
+        E, V = np.ascontiguousarray(E, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64)
+    lo, hi, t = [np.ascontiguousarray(a) for a in quantile_positions(q, n_obs)]
+    logY, Q = np.empty((n, n_obs)), np.empty((n, nq))
+    Y = np.empty((n, n_obs)) if return_series else None
+    Eo = np.empty((n, n_obs)) if return_draws else None
+    Vo = np.empty((n, n_obs)) if return_draws else None
+    D = np.empty(n) if obs is not None else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_mg1_summaries", _lib.ptr(E), _lib.ptr(V), C.c_uint64(int(seed)), C.c_uint64(int(stream)), n, n_obs,
+             _lib.ptr(t1), _lib.ptr(t2), _lib.ptr(t3), nq, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(t), _lib.ptr(obs),
+             _lib.ptr(w), _lib.ptr(logY), _lib.ptr(Q), _lib.ptr(Y), _lib.ptr(Eo), _lib.ptr(Vo), _lib.ptr(D))
+    return tuple(a for a in (logY, Q, Y, Eo, Vo, D) if a is not None)

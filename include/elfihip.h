@@ -545,6 +545,47 @@ int elfihip_prior_draw(elfihip_ctx* ctx, int kind, uint64_t seed, uint64_t strea
 int elfihip_prior_draw_dev(elfihip_ctx* ctx, int kind, uint64_t seed, uint64_t stream, int64_t n, const double* a,
                            const double* dcond, double* dout);
 
+/* The time-series example models, fused: draws, the serial recurrence of every simulation, summaries and distance in one
+ * pass; series, summaries and quantiles bit-identical to the reference's NumPy on the same draws.  Series of at most
+ * ELFIHIP_SERIES_MAX_OBS observations (a simulation keeps its series in LDS).  Draw matrices given as NULL are drawn
+ * in the kernel from the stream (seed, stream) of elfihip_randn_dev.  Optional outputs may be NULL.  obs, w and the
+ * quantile positions are HOST arrays in both forms; in the _dev forms every other pointer is a device pointer and every
+ * matrix comes with the caller's leading dimension (in doubles); no synchronisation.  The host forms synchronise.
+ *
+ * ARCH(1) (elfi/examples/arch.py): W (n, n_obs + 2) standard normals -- columns 0 .. n_obs the reference's xi =
+ * normal((batch, n_obs + 1)), column n_obs + 1 its e[:, 0] = normal(batch); W == NULL: element e of the row-major matrix
+ * is normal number e of (seed, stream).  e_i = xi_i sqrt(0.2 + t2 e_{i-1}^2), y_0 = 0, y_i = t1 y_{i-1} + e_i, i = 1 ..
+ * n_obs.  S (n, m), m = 2 + L + L (L - 1) / 2 for L = n_lags in 1 .. ELFIHIP_ARCH_MAX_LAGS, n_obs >= L + 2: sample_mean,
+ * sample_variance, autocorr(lag 1 .. L), pairwise_autocorr(i, j) for i < j in itertools.combinations order.  Y (n, n_obs):
+ * the series.  D (n): euclidean distance of the row of S to obs (m values), bit-identical to elfihip_dist_rows on S. */
+#define ELFIHIP_SERIES_MAX_OBS 2048
+#define ELFIHIP_ARCH_MAX_LAGS 8
+int elfihip_arch_summaries(elfihip_ctx* ctx, const double* W, uint64_t seed, uint64_t stream, int64_t n, int n_obs, int n_lags,
+                           const double* t1, const double* t2, const double* obs, double* S, double* Y, double* D);
+int elfihip_arch_summaries_dev(elfihip_ctx* ctx, const double* dW, int64_t ldw, uint64_t seed, uint64_t stream, int64_t n,
+                               int n_obs, int n_lags, const double* dt1, const double* dt2, const double* obs, double* dS,
+                               int64_t lds, double* dY, int64_t ldy, double* dD);
+/* M/G/1 (elfi/examples/mg1.py): E (n, n_obs) standard exponentials and V (n, n_obs) uniforms in [0, 1) -- the reference's
+ * standard_exponential((n_obs, batch)) and random_sample((n_obs, batch)), transposed; both NULL: E_e = -log u with u the
+ * 53-bit uniform in (0, 1] made of word e of (seed, stream) (the word + 1, as the normals' radius takes it), V_e = word e of
+ * (seed, stream + 1) as elfihip_prior_draw forms its uniforms.  W = (1 / t3) E, U = t1 + (t2 - t1) V, sum_w += W_i,
+ * y_i = U_i + max(0, sum_w - sum_x), sum_x += y_i.  logY (n, n_obs) = log y (the device logarithm: within a few ulp of
+ * np.log).  Q (n, nq), 1 <= nq <= ELFIHIP_MG1_MAX_QUANTILES: np.quantile(y, q, axis=1, method='linear') from the positions
+ * the host computed by NumPy's virtual-index rule -- for quantile k the sorted neighbours a = s[lo[k]], b = s[hi[k]] and the
+ * weight t[k]: a + (b - a) t[k] if t[k] < 0.5, else b - (b - a) (1 - t[k]).  Y: the series; Eo, Vo: the draws used.
+ * D (n): euclidean distance of the row of Q to obs (nq values), weighted by w (nq values) when w is given; bit-identical
+ * to elfihip_dist_rows on Q. */
+#define ELFIHIP_MG1_MAX_QUANTILES 64
+int elfihip_mg1_summaries(elfihip_ctx* ctx, const double* E, const double* V, uint64_t seed, uint64_t stream, int64_t n,
+                          int n_obs, const double* t1, const double* t2, const double* t3, int nq, const int* lo, const int* hi,
+                          const double* t, const double* obs, const double* w, double* logY, double* Q, double* Y, double* Eo,
+                          double* Vo, double* D);
+int elfihip_mg1_summaries_dev(elfihip_ctx* ctx, const double* dE, int64_t lde, const double* dV, int64_t ldv, uint64_t seed,
+                              uint64_t stream, int64_t n, int n_obs, const double* dt1, const double* dt2, const double* dt3,
+                              int nq, const int* lo, const int* hi, const double* t, const double* obs, const double* w,
+                              double* dLogY, int64_t ldl, double* dQ, int64_t ldq, double* dY, int64_t ldy, double* dEo,
+                              int64_t ldeo, double* dVo, int64_t ldvo, double* dD);
+
 /* ------------------------------------------------------------------- GP surrogate
  * Replaces the GPy model behind elfi.methods.bo.gpy_regression.GPyRegression
  * (elfi/methods/bo/gpy_regression.py:15-364): kernel RBF(variance, lengthscale) + Bias
