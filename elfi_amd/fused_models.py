@@ -4,6 +4,7 @@
     m = elfi_amd.fused_models.gauss_model(n_obs=50, seed_obs=4)       # elfi.examples.gauss.get_model(...)
     m = elfi_amd.fused_models.arch_model(n_obs=100, seed_obs=4)       # elfi.examples.arch.get_model(...)
     m = elfi_amd.fused_models.mg1_model(n_obs=50, seed_obs=4)         # elfi.examples.mg1.get_model(...)
+    m = elfi_amd.fused_models.lorenz_model(seed_obs=4)                # elfi.examples.lorenz.get_model(...)
     elfi_amd.HipRejection(m['d'], batch_size=10**6, seed=1).sample(1000, n_sim=10**8)
 
 The reference's Simulator node draws the series on the host (MA2: random_state.randn(batch, n_obs + 2),
@@ -24,6 +25,11 @@ all summaries of a simulation -- ARCH: the (batch, 2 + L + L (L - 1) / 2) column
 log_identity is what HipBSL / syn_loglik take.  On given draws series, summaries and quantiles are the reference's bit
 for bit, the logarithms within 4 ulp (tests/test_series_models_gpu.py).
 
+lorenz_model is the stochastic Lorenz-96 forecast example (elfi/examples/lorenz.py: 40 coupled variables, 160 rows, a
+fourth-order Runge-Kutta step and an AR(1) forcing per row, six summaries) on csrc/lorenz.hip: a simulation is one
+wavefront, a variable one lane; its Simulator node returns the (batch, 6) columns Mean, Var, Autocov, Cov, CrosscovPrev,
+CrosscovNext.  On given draws series and summaries are the reference's bit for bit (tests/test_lorenz_gpu.py).
+
 The draws are the device generator's, not MT19937's: a run of this model is a different (equally valid) random
 realisation than a run of elfi.examples.*.get_model with the same seed; the arithmetic on given draws is bit-identical
 to the reference's (tests/test_summaries_gpu.py, tests/test_gauss_gpu.py).
@@ -36,7 +42,7 @@ import numpy as np
 
 from .distance import HipDistance, randn_rows
 from .priors import SIMULATOR_STREAM_BASE
-from .summaries import arch_summaries, gauss_distance, ma2_draw_distance, mg1_summaries
+from .summaries import LORENZ_NAMES, arch_summaries, gauss_distance, lorenz_summaries, ma2_draw_distance, mg1_summaries
 
 
 def _elfi():
@@ -198,6 +204,61 @@ def mg1_model(n_obs=50, true_params=None, seed_obs=None, n_quantiles=10, device_
     elfi.Summary(partial(columns, stop=n_obs), m['MG1'], name='log_identity')
     elfi.Summary(partial(columns, start=n_obs), m['MG1'], name='quantiles')
     elfi.Distance(HipDistance('euclidean', w=(1 / 100) ** q), m['quantiles'], name='d')
+    return m
+
+
+class _InitialState(np.ndarray):
+    """An initial state the reference's simulator accepts: forecast_lorenz tests `if not initial_state` (lorenz.py:128),
+    which an array of more than one element refuses to answer."""
+
+    def __bool__(self):
+        return True
+
+
+def lorenz_summary_rows(theta1, theta2, initial_state=None, f=10., phi=0.984, n_obs=40, n_timestep=160, total_duration=4,
+                        batch_size=1, random_state=None):
+    """Simulator operation: (batch, 6) summaries Mean, Var, Autocov, Cov, CrosscovPrev, CrosscovNext of stochastic Lorenz-96
+    series drawn, integrated and reduced on the device."""
+    theta1, theta2 = _per_simulation(batch_size, theta1, theta2)
+    return lorenz_summaries(theta1, theta2, initial_state, f=f, phi=phi, n_obs=n_obs, n_timestep=n_timestep,
+                            total_duration=total_duration, seed=_seed_of(random_state), stream=SIMULATOR_STREAM_BASE)
+
+
+def lorenz_model(true_params=None, seed_obs=None, initial_state=None, n_obs=40, f=10., phi=0.984, total_duration=4,
+                 device_priors=True):
+    """elfi.examples.lorenz.get_model(true_params, seed_obs, initial_state, n_obs, f, phi, total_duration) with the
+    simulation on the device; nodes theta1, theta2, Lorenz, Mean, Var, Autocov, Cov, CrosscovPrev, CrosscovNext, d.  The
+    node Lorenz returns the (batch, 6) summaries, the Summary nodes pick their column.  The observed series is the
+    reference's own forecast_lorenz with RandomState(seed_obs), reduced once with its summary functions; its default
+    initial state (n_obs = 40) is asked of that simulator, whose row 0 it is.  device_priors: the two uniform priors draw
+    on the device as well (elfi_amd.priors.uniform; False: SciPy's)."""
+    elfi = _elfi()
+    from elfi.examples import lorenz
+    if true_params is None:
+        true_params = [2.0, 0.1]
+    if initial_state is None:
+        y0 = np.array(lorenz.forecast_lorenz(0, 0, n_obs=n_obs, n_timestep=1, batch_size=1)[0, 0], dtype=np.float64)
+        given = None
+    else:
+        y0 = np.array(initial_state, dtype=np.float64).reshape(-1)
+        if y0.shape[0] != n_obs:
+            raise ValueError('initial_state must hold the n_obs = %d initial values' % n_obs)
+        given = y0.reshape(1, n_obs).view(_InitialState)
+    y = lorenz.forecast_lorenz(*true_params, f=f, phi=phi, n_obs=n_obs, initial_state=given, total_duration=total_duration,
+                               random_state=np.random.RandomState(seed_obs))
+    y = np.asarray(y)
+    n_timestep = y.shape[1]
+    obs = np.column_stack([lorenz.mean(y), lorenz.var(y), lorenz.autocov(y), lorenz.cov(y), lorenz.xcov(y, True),
+                           lorenz.xcov(y, False)])
+    m = elfi.ElfiModel()
+    from . import priors
+    uniform = priors.uniform if device_priors else 'uniform'
+    elfi.Prior(uniform, 0.5, 3., model=m, name='theta1')
+    elfi.Prior(uniform, 0, 0.3, model=m, name='theta2')
+    elfi.Simulator(partial(lorenz_summary_rows, initial_state=y0, f=f, phi=phi, n_obs=n_obs, n_timestep=n_timestep,
+                           total_duration=total_duration), m['theta1'], m['theta2'], observed=obs, name='Lorenz')
+    ss = [elfi.Summary(partial(column, j=k), m['Lorenz'], name=name) for k, name in enumerate(LORENZ_NAMES)]
+    elfi.Distance(HipDistance('euclidean'), *ss, name='d')
     return m
 
 

@@ -10,11 +10,13 @@ leading dimension of 1 -- elfi/model/elfi_model.py:915-943, elfi/compiler.py:94-
     ma2_distance(...)    the fused MA2 path: simulator arithmetic + both summaries + distance
     arch_summaries(...)  the fused ARCH(1) example: series + 17 summaries [+ distance]     elfi/examples/arch.py
     mg1_summaries(...)   the fused M/G/1 example: series, its logarithm, quantiles [+ distance]  elfi/examples/mg1.py
+    lorenz_summaries(...)  the fused stochastic Lorenz-96 example: series + 6 summaries [+ distance]   elfi/examples/lorenz.py
 
     S1 = elfi.Summary(elfi_amd.autocov, Y);  S2 = elfi.Summary(elfi_amd.autocov, Y, 2)
 
 Module-level functions (picklable), plain data in, NumPy arrays out; the arithmetic runs in
-libelfihip.so (csrc/summaries.hip) with NumPy's pairwise summation order.  No CPU fallback.
+libelfihip.so (csrc/summaries.hip, csrc/series.hip, csrc/lorenz.hip) with NumPy's pairwise summation order.  No CPU
+fallback.
 """
 import ctypes as C
 
@@ -270,3 +272,62 @@ def mg1_summaries(t1, t2, t3, n_obs=50, q=None, draws=None, seed=0, stream=0, ob
              _lib.ptr(t1), _lib.ptr(t2), _lib.ptr(t3), nq, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(t), _lib.ptr(obs),
              _lib.ptr(w), _lib.ptr(logY), _lib.ptr(Q), _lib.ptr(Y), _lib.ptr(Eo), _lib.ptr(Vo), _lib.ptr(D))
     return tuple(a for a in (logY, Q, Y, Eo, Vo, D) if a is not None)
+
+
+# ---- the stochastic Lorenz-96 example model (csrc/lorenz.hip) -------------------------------------------------------
+LORENZ_MAX_VARS = 64        # include/elfihip.h: ELFIHIP_LORENZ_MAX_VARS (a variable per lane)
+LORENZ_MAX_TERMS = 8192     # ELFIHIP_LORENZ_MAX_TERMS (n_timestep * n_obs: NumPy's reduction buffer)
+LORENZ_NAMES = ('Mean', 'Var', 'Autocov', 'Cov', 'CrosscovPrev', 'CrosscovNext')
+
+
+def lorenz_summaries(theta1, theta2, initial_state, f=10., phi=0.984, n_obs=40, n_timestep=160, total_duration=4,
+                     noise=None, seed=0, stream=0, observed=None, return_series=False, ctx=None):
+    """The stochastic Lorenz-96 forecast example (elfi/examples/lorenz.py) as ONE device operation: n_obs cyclically coupled
+    variables stepped n_timestep - 1 times by fourth-order Runge-Kutta under an AR(1) forcing eta = phi eta + e sqrt(1 -
+    phi^2), and the six summaries of the (n_timestep, n_obs) series in the reference's order Mean, Var, Autocov, Cov,
+    CrosscovPrev, CrosscovNext.
+
+    theta1, theta2: (batch,) or scalars.  initial_state: (n_obs,) shared by all simulations, or (batch, n_obs).
+    noise: (batch, n_timestep - 1, n_obs) standard normals, what the reference draws as `normal(0, 1, (batch, n_obs))` once
+    per step, stacked along axis 1 -- series and summaries bit-identical to the reference's NumPy; noise=None draws on the
+    device (Philox4x32-10 keyed by `seed`, counter stream `stream`).  4 <= n_obs <= 64, n_timestep >= 2, n_timestep * n_obs
+    <= 8192.  observed: the six observed summaries; with them the euclidean distance is returned too.
+    Returns S (batch, 6) [, series (batch, n_timestep, n_obs)] [, d (batch,)]."""
+    n_obs, n_timestep = int(n_obs), int(n_timestep)
+    if not 4 <= n_obs <= LORENZ_MAX_VARS:
+        raise ValueError('n_obs must be in [4, %d]' % LORENZ_MAX_VARS)
+    if n_timestep < 2:
+        raise ValueError('need n_timestep >= 2')
+    if n_timestep * n_obs > LORENZ_MAX_TERMS:
+        raise ValueError('n_timestep * n_obs must be at most %d' % LORENZ_MAX_TERMS)
+    if not abs(float(phi)) <= 1.0:
+        raise ValueError('phi must be in [-1, 1]')
+    if noise is not None:
+        noise = np.asarray(noise)
+        if noise.ndim != 3 or noise.shape[1:] != (n_timestep - 1, n_obs):
+            raise ValueError('noise must be (batch, n_timestep - 1, n_obs) = (batch, %d, %d)' % (n_timestep - 1, n_obs))
+    y0 = np.asarray(initial_state, dtype=np.float64)
+    if y0.ndim not in (1, 2) or y0.shape[-1] != n_obs:
+        raise ValueError('initial_state must be (n_obs,) or (batch, n_obs) with n_obs = %d' % n_obs)
+    n = noise.shape[0] if noise is not None else (y0.shape[0] if y0.ndim == 2 else _batch_of(theta1, theta2))
+    if y0.ndim == 2 and y0.shape[0] != n:
+        raise ValueError('initial_state must hold one row per simulation (%d)' % n)
+    theta1, theta2 = _params(n, theta1, theta2)
+    obs = None
+    if observed is not None:
+        obs = np.ascontiguousarray(np.asarray(observed, dtype=np.float64).reshape(-1))
+        if obs.shape[0] != 6:
+            raise ValueError('observed must hold the 6 observed summaries')
+    y0 = np.ascontiguousarray(y0)
+    if noise is not None:
+        noise = np.ascontiguousarray(noise, dtype=np.float64)
+    c = float(np.sqrt(1 - pow(phi, 2)))          # lorenz.py:157, as Python computes it
+    h = total_duration / n_timestep              # lorenz.py:148
+    S = np.empty((n, 6))
+    Y = np.empty((n, n_timestep, n_obs)) if return_series else None
+    D = np.empty(n) if obs is not None else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_lorenz_summaries", _lib.ptr(noise), C.c_uint64(int(seed)), C.c_uint64(int(stream)), n, n_obs, n_timestep,
+             _lib.ptr(theta1), _lib.ptr(theta2), C.c_double(f), C.c_double(c), C.c_double(phi), C.c_double(h), _lib.ptr(y0),
+             int(y0.ndim == 2), _lib.ptr(obs), _lib.ptr(S), _lib.ptr(Y), _lib.ptr(D))
+    return tuple(a for a in (S, Y, D) if a is not None) if (return_series or obs is not None) else S

@@ -586,6 +586,31 @@ int elfihip_mg1_summaries_dev(elfihip_ctx* ctx, const double* dE, int64_t lde, c
                               double* dLogY, int64_t ldl, double* dQ, int64_t ldq, double* dY, int64_t ldy, double* dEo,
                               int64_t ldeo, double* dVo, int64_t ldvo, double* dD);
 
+/* The stochastic Lorenz-96 forecast model (elfi/examples/lorenz.py), fused the same way: draws, the Runge-Kutta recurrence,
+ * the six summaries and the distance in one pass; series and summaries bit-identical to the reference's NumPy on the same
+ * draws.  K = n_obs variables in 4 .. ELFIHIP_LORENZ_MAX_VARS, T = n_timestep >= 2 rows, T K <= ELFIHIP_LORENZ_MAX_TERMS
+ * (NumPy's reduction buffer: beyond it its summation order changes); anything else is ELFIHIP_ERR_ARG.
+ * E (n, T - 1, K) standard normals -- the reference's normal(0, 1, (batch, K)) of steps 1 .. T - 1, stacked along axis 1;
+ * E == NULL: element e of that row-major array is normal number e of (seed, stream), as elfihip_randn_dev writes them.
+ * Row 0 of a series is y0 -- one row of K values shared by all simulations or (n, K).  For i = 1 .. T - 1, with c =
+ * sqrt(1 - phi^2) and h = total_duration / T as the host computes them:
+ *     eta  = phi eta + E_i c                                                    (eta starts as 0)
+ *     dy_k = ((((-y[k-2] y[k-1] + y[k-1] y[k+1]) - y[k]) + f) - (theta1 + y[k] theta2)) + eta[k]       (indices cyclic)
+ *     k1 = h dy(y), k2 = h dy(y + k1 / 2), k3 = h dy(y + k2 / 2), k4 = h dy(y + k3), y = y + (((k1 + 2 k2) + 2 k3) + k4) / 6
+ * S (n, 6): Mean, Var, Autocov, Cov, CrosscovPrev, CrosscovNext (lorenz.py: mean, var, autocov, cov, xcov(prev), xcov(next)).
+ * Y (n, T K): the series, (T, K) row-major per simulation.  D (n): euclidean distance of the row of S to obs (6 values),
+ * bit-identical to elfihip_dist_rows on S.  Host form: y0_per_simulation 0 = y0 is (K), else (n, K).  _dev form: ldE, lds,
+ * ldy are the pitches between simulations, ldy0 == 0 says one shared row, else the pitch of the (n, K) rows. */
+#define ELFIHIP_LORENZ_MAX_VARS 64
+#define ELFIHIP_LORENZ_MAX_TERMS 8192
+int elfihip_lorenz_summaries(elfihip_ctx* ctx, const double* E, uint64_t seed, uint64_t stream, int64_t n, int n_obs,
+                             int n_timestep, const double* t1, const double* t2, double f, double c, double phi, double h,
+                             const double* y0, int y0_per_simulation, const double* obs, double* S, double* Y, double* D);
+int elfihip_lorenz_summaries_dev(elfihip_ctx* ctx, const double* dE, int64_t ldE, uint64_t seed, uint64_t stream, int64_t n,
+                                 int n_obs, int n_timestep, const double* dt1, const double* dt2, double f, double c, double phi,
+                                 double h, const double* dy0, int64_t ldy0, const double* obs, double* dS, int64_t lds,
+                                 double* dY, int64_t ldy, double* dD);
+
 /* ------------------------------------------------------------------- GP surrogate
  * Replaces the GPy model behind elfi.methods.bo.gpy_regression.GPyRegression
  * (elfi/methods/bo/gpy_regression.py:15-364): kernel RBF(variance, lengthscale) + Bias
