@@ -5,6 +5,8 @@
     m = elfi_amd.fused_models.arch_model(n_obs=100, seed_obs=4)       # elfi.examples.arch.get_model(...)
     m = elfi_amd.fused_models.mg1_model(n_obs=50, seed_obs=4)         # elfi.examples.mg1.get_model(...)
     m = elfi_amd.fused_models.lorenz_model(seed_obs=4)                # elfi.examples.lorenz.get_model(...)
+    m = elfi_amd.fused_models.gnk_model(n_obs=50, seed=4)             # elfi.examples.gnk.get_model(...)
+    m = elfi_amd.fused_models.bignk_model(n_obs=150, seed=4)          # elfi.examples.bignk.get_model(...)
     elfi_amd.HipRejection(m['d'], batch_size=10**6, seed=1).sample(1000, n_sim=10**8)
 
 The reference's Simulator node draws the series on the host (MA2: random_state.randn(batch, n_obs + 2),
@@ -30,6 +32,16 @@ fourth-order Runge-Kutta step and an AR(1) forcing per row, six summaries) on cs
 wavefront, a variable one lane; its Simulator node returns the (batch, 6) columns Mean, Var, Autocov, Cov, CrosscovPrev,
 CrosscovNext.  On given draws series and summaries are the reference's bit for bit (tests/test_lorenz_gpu.py).
 
+gnk_model / bignk_model are the g-and-k quantile-distribution examples (elfi/examples/gnk.py, bignk.py) on csrc/gnk.hip.
+Nothing in them is a recurrence: the wavefront's lanes take single elements for the exp and pow of the quantile function
+and whole columns for the sort that the octiles need.  The Simulator node returns the (batch, m) rows of the ONE summary
+the model was built with (gnk: 'order', the reference's default; bignk: 'robust'), the Summary node ss_<summary> gives them
+the reference's (batch, m, 1) shape, and d is an elfi.Discrepancy that flattens them for HipDistance('euclidean') -- the
+reference's euclidean_multiss up to the order of its sum.  The series goes through the device's exp and pow: within a few
+eps (|A| + |y - A|) of the reference's on given draws, and every summary NumPy's bit for bit on that series
+(tests/test_gnk_gpu.py).  The bivariate model's correlated normals are z0 = e0, z1 = rho e0 + sqrt(1 - rho^2) e1 of the
+device generator: the distribution of the reference's multivariate_normal.rvs draws, not their bits.
+
 The draws are the device generator's, not MT19937's: a run of this model is a different (equally valid) random
 realisation than a run of elfi.examples.*.get_model with the same seed; the arithmetic on given draws is bit-identical
 to the reference's (tests/test_summaries_gpu.py, tests/test_gauss_gpu.py).
@@ -43,6 +55,7 @@ import numpy as np
 from .distance import HipDistance, randn_rows
 from .priors import SIMULATOR_STREAM_BASE
 from .summaries import LORENZ_NAMES, arch_summaries, gauss_distance, lorenz_summaries, ma2_draw_distance, mg1_summaries
+from .summaries import GNK_SUMMARIES, bignk_summaries, gnk_summaries
 
 
 def _elfi():
@@ -259,6 +272,87 @@ def lorenz_model(true_params=None, seed_obs=None, initial_state=None, n_obs=40, 
                            total_duration=total_duration), m['theta1'], m['theta2'], observed=obs, name='Lorenz')
     ss = [elfi.Summary(partial(column, j=k), m['Lorenz'], name=name) for k, name in enumerate(LORENZ_NAMES)]
     elfi.Distance(HipDistance('euclidean'), *ss, name='d')
+    return m
+
+
+def rows_as_points(y):
+    """Summary operation of the g-and-k models: the (batch, m) rows in the reference's (batch, m, 1) shape."""
+    return np.asarray(y)[:, :, np.newaxis]
+
+
+def euclidean_rows(*simulated, observed):
+    """Discrepancy operation of the g-and-k models (the reference's euclidean_multiss, gnk.py:115-142, on one summary of
+    shape (batch, m, 1)): flattened and handed to HipDistance('euclidean')."""
+    sim = np.asarray(simulated[0])
+    return HipDistance('euclidean')(sim.reshape(sim.shape[0], -1), np.asarray(observed[0]).reshape(1, -1))
+
+
+def gnk_summary_rows(*params, dim=1, c=0.8, n_obs=50, summary='order', batch_size=1, random_state=None):
+    """Simulator operation: the (batch, m) rows of one summary of g-and-k series (dim = 1) or bivariate g-and-k series
+    (dim = 2) drawn, transformed, sorted and read on the device."""
+    params = _per_simulation(batch_size, *params)
+    fn = gnk_summaries if dim == 1 else bignk_summaries
+    return fn(*params, c=c, n_obs=n_obs, summary=summary, seed=_seed_of(random_state), stream=SIMULATOR_STREAM_BASE)
+
+
+def _observed_rows(module, y_obs, summary):
+    """The observed series through the reference's own summary function, as the (1, m) row the Simulator node holds."""
+    if summary == 'sorted':      # not a reference summary: what ss_order was meant to be
+        s = np.sort(np.asarray(y_obs), axis=1)
+    else:
+        s = getattr(module, 'ss_' + summary)(y_obs)
+    return np.asarray(s, dtype=np.float64).reshape(1, -1)
+
+
+def gnk_model(n_obs=50, true_params=None, seed=None, summary='order', device_priors=True):
+    """elfi.examples.gnk.get_model(n_obs, true_params, seed) with the simulation on the device; nodes A, B, g, k, GNK,
+    ss_<summary>, d.  summary: 'order' (the reference's default: the series as it is), 'octile', 'robust' or 'sorted'
+    (true order statistics; not a reference summary).  The node GNK returns the (batch, m) rows of that summary, the
+    Summary node gives them the reference's (batch, m, 1) shape and d is an elfi.Discrepancy over HipDistance('euclidean').
+    The observed series is the reference's own GNK with RandomState(seed), reduced by its own summary function.
+    device_priors: the four uniform priors draw on the device as well (elfi_amd.priors.uniform; False: SciPy's)."""
+    elfi = _elfi()
+    from elfi.examples import gnk
+    if summary not in GNK_SUMMARIES:
+        raise ValueError('summary must be one of %s' % (GNK_SUMMARIES,))
+    if true_params is None:
+        true_params = [3, 1, 2, .5]
+    m = elfi.new_model()
+    from . import priors
+    uniform = priors.uniform if device_priors else 'uniform'
+    nodes = [elfi.Prior(uniform, 0, 10, model=m, name=name) for name in ('A', 'B', 'g', 'k')]
+    y_obs = gnk.GNK(*true_params, n_obs=n_obs, random_state=np.random.RandomState(seed))
+    elfi.Simulator(partial(gnk_summary_rows, dim=1, n_obs=n_obs, summary=summary), *nodes,
+                   observed=_observed_rows(gnk, y_obs, summary), name='GNK')
+    ss = elfi.Summary(rows_as_points, m['GNK'], name='ss_' + summary)
+    elfi.Discrepancy(euclidean_rows, ss, name='d')
+    return m
+
+
+def bignk_model(n_obs=150, true_params=None, seed=None, summary='robust', device_priors=True):
+    """elfi.examples.bignk.get_model(n_obs, true_params, seed) with the simulation on the device; nodes a1, a2, b1, b2,
+    g1, g2, k1, k2, rho, BiGNK, ss_<summary>, d.  summary: 'robust' (the reference's default), 'octile' or 'sorted'; 'order'
+    is refused here, because the reference's ss_order would sort each (y0, y1) pair, which is no summary of either
+    dimension.  Built as gnk_model is; the observed series is the reference's own BiGNK with RandomState(seed).  The device's
+    correlated normals have the distribution of the reference's, not their bits."""
+    elfi = _elfi()
+    from elfi.examples import bignk, gnk
+    if summary not in GNK_SUMMARIES or summary == 'order':
+        raise ValueError("summary must be one of 'robust', 'octile', 'sorted'")
+    if true_params is None:
+        true_params = [3, 4, 1, 0.5, 1, 2, .5, .4, 0.6]
+    m = elfi.new_model()
+    from . import priors
+    uniform = priors.uniform if device_priors else 'uniform'
+    eps = np.finfo(float).eps
+    ranges = [('a1', 0, 5), ('a2', 0, 5), ('b1', 0, 5), ('b2', 0, 5), ('g1', -5, 10), ('g2', -5, 10), ('k1', -.5, 5.5),
+              ('k2', -.5, 5.5), ('rho', -1 + eps, 2 - 2 * eps)]
+    nodes = [elfi.Prior(uniform, loc, scale, model=m, name=name) for name, loc, scale in ranges]
+    y_obs = bignk.BiGNK(*true_params, n_obs=n_obs, random_state=np.random.RandomState(seed))
+    elfi.Simulator(partial(gnk_summary_rows, dim=2, n_obs=n_obs, summary=summary), *nodes,
+                   observed=_observed_rows(gnk, y_obs, summary), name='BiGNK')
+    ss = elfi.Summary(rows_as_points, m['BiGNK'], name='ss_' + summary)
+    elfi.Discrepancy(euclidean_rows, ss, name='d')
     return m
 
 

@@ -11,11 +11,13 @@ leading dimension of 1 -- elfi/model/elfi_model.py:915-943, elfi/compiler.py:94-
     arch_summaries(...)  the fused ARCH(1) example: series + 17 summaries [+ distance]     elfi/examples/arch.py
     mg1_summaries(...)   the fused M/G/1 example: series, its logarithm, quantiles [+ distance]  elfi/examples/mg1.py
     lorenz_summaries(...)  the fused stochastic Lorenz-96 example: series + 6 summaries [+ distance]   elfi/examples/lorenz.py
+    gnk_summaries(...), bignk_summaries(...)  the fused g-and-k examples: series, order statistics, octiles, robust
+                         statistics [+ distance]                                      elfi/examples/gnk.py, bignk.py
 
     S1 = elfi.Summary(elfi_amd.autocov, Y);  S2 = elfi.Summary(elfi_amd.autocov, Y, 2)
 
 Module-level functions (picklable), plain data in, NumPy arrays out; the arithmetic runs in
-libelfihip.so (csrc/summaries.hip, csrc/series.hip, csrc/lorenz.hip) with NumPy's pairwise summation order.  No CPU
+libelfihip.so (csrc/summaries.hip, csrc/series.hip, csrc/lorenz.hip, csrc/gnk.hip) with NumPy's pairwise summation order.  No CPU
 fallback.
 """
 import ctypes as C
@@ -331,3 +333,96 @@ def lorenz_summaries(theta1, theta2, initial_state, f=10., phi=0.984, n_obs=40, 
              _lib.ptr(theta1), _lib.ptr(theta2), C.c_double(f), C.c_double(c), C.c_double(phi), C.c_double(h), _lib.ptr(y0),
              int(y0.ndim == 2), _lib.ptr(obs), _lib.ptr(S), _lib.ptr(Y), _lib.ptr(D))
     return tuple(a for a in (S, Y, D) if a is not None) if (return_series or obs is not None) else S
+
+
+# ---- the g-and-k example models (csrc/gnk.hip) ----------------------------------------------------------------------
+GNK_SUMMARIES = ('order', 'sorted', 'octile', 'robust')     # include/elfihip.h: ELFIHIP_GNK_ORDER, _SORTED, _OCTILE, _ROBUST
+GNK_OCTILES = np.linspace(12.5, 87.5, 7)                    # gnk.py:207
+
+
+def gnk_summary_length(name, n_obs, dim=1):
+    """Values per simulation of the summary `name`."""
+    return {'order': n_obs * dim, 'sorted': n_obs * dim, 'octile': 7 * dim, 'robust': 4 * dim}[name]
+
+
+def _gnk_call(params, dim, c, n_obs, z, seed, stream, summary, observed, return_series, return_draws, ctx):
+    n_obs = int(n_obs)
+    single = isinstance(summary, str)
+    names = (summary,) if single else (tuple(summary) if isinstance(summary, (tuple, list)) else ())
+    if not names or any(not isinstance(s, str) or s not in GNK_SUMMARIES for s in names):
+        raise ValueError('summary must be one of %s, or a tuple of them' % (GNK_SUMMARIES,))
+    shape = (n_obs,) if dim == 1 else (n_obs, 2)
+    if z is not None:
+        z = np.asarray(z)
+        if z.ndim != 1 + len(shape) or z.shape[1:] != shape:
+            raise ValueError('z must be (batch,%s)' % ''.join(' %d,' % s for s in shape)[:-1])
+    if n_obs < 2:
+        raise ValueError('need n_obs >= 2')
+    if n_obs * dim > SERIES_MAX_OBS:
+        raise ValueError('series of at most %d values (n_obs * %d)' % (SERIES_MAX_OBS, dim))
+    n = z.shape[0] if z is not None else _batch_of(*params)
+    P = np.ascontiguousarray(np.column_stack(_params(n, *params)))
+    if dim == 2 and not np.all(np.abs(P[:, 8]) <= 1.0):
+        raise ValueError('rho must be in [-1, 1]')
+    obs = None
+    if observed is not None:
+        m = gnk_summary_length(names[0], n_obs, dim)
+        obs = np.ascontiguousarray(np.asarray(observed, dtype=np.float64).reshape(-1))
+        if obs.shape[0] != m:
+            raise ValueError('observed must hold the %d values of the summary %r' % (m, names[0]))
+    if z is not None:
+        z = np.ascontiguousarray(z, dtype=np.float64)
+    lo, hi, t = [np.ascontiguousarray(a) for a in quantile_positions(np.true_divide(GNK_OCTILES, 100), n_obs)]
+    L = n_obs * dim
+    Y = np.empty((n, L)) if (return_series or 'order' in names) else None
+    Zo = np.empty((n,) + shape) if return_draws else None
+    Ys = np.empty((n, L)) if 'sorted' in names else None
+    O = np.empty((n, 7 * dim)) if 'octile' in names else None
+    R = np.empty((n, 4 * dim)) if 'robust' in names else None
+    D = np.empty(n) if obs is not None else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_gnk_summaries", _lib.ptr(z), C.c_uint64(int(seed)), C.c_uint64(int(stream)), n, n_obs, dim,
+             _lib.ptr(P), C.c_double(c), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(t), _lib.ptr(obs),
+             GNK_SUMMARIES.index(names[0]), _lib.ptr(Y), _lib.ptr(Zo), _lib.ptr(Ys), _lib.ptr(O), _lib.ptr(R), _lib.ptr(D))
+    by_name = dict(order=Y, sorted=Ys, octile=O, robust=R)
+    out = [by_name[s] for s in names]
+    if return_series:
+        out.append(Y.reshape((n,) + shape))
+    if return_draws:
+        out.append(Zo)
+    if D is not None:
+        out.append(D)
+    return out[0] if (single and len(out) == 1) else tuple(out)
+
+
+def gnk_summaries(A, B, g, k, c=0.8, n_obs=50, z=None, seed=0, stream=0, summary='robust', observed=None,
+                  return_series=False, return_draws=False, ctx=None):
+    """The univariate g-and-k example (elfi/examples/gnk.py) as ONE device operation: the series y = A + B (1 + c (1 -
+    exp(-g z)) / (1 + exp(-g z))) (1 + z^2)^k z in the reference's order of operations, and its summaries.
+
+    A, B, g, k: (batch,) or scalars.  z: (batch, n_obs) standard normals, what the reference draws as
+    ss.norm.rvs(size=(batch, n_obs)); z=None draws on the device (Philox4x32-10 keyed by `seed`, counter stream `stream`:
+    element e is normal number e of that stream).  The series passes through the device's exp and pow and is within a few
+    units eps (|A| + |y - A|) of the reference's; every summary is NumPy's bit for bit on the device's series.
+    summary: 'order' (the series as it is: the reference's ss_order, whose np.sort runs along the last axis), 'sorted'
+    (np.sort(y, axis=1): true order statistics, not a reference summary), 'octile' (ss_octile, 7 values), 'robust'
+    (ss_robust, 4 values), or a tuple of them.  observed: the observed values of the FIRST summary named; with them the
+    euclidean distance on that summary is returned too (HipDistance's bits; euclidean_multiss up to its order of summation).
+    Returns the summaries in the order asked, each (batch, m) [, series (batch, n_obs)] [, draws (batch, n_obs)] [, d
+    (batch,)] -- the bare array when `summary` is one name and nothing else is asked for, else a tuple."""
+    return _gnk_call((A, B, g, k), 1, float(c), n_obs, z, seed, stream, summary, observed, return_series, return_draws, ctx)
+
+
+def bignk_summaries(A1, A2, B1, B2, g1, g2, k1, k2, rho, c=0.8, n_obs=150, z=None, seed=0, stream=0, summary='robust',
+                    observed=None, return_series=False, return_draws=False, ctx=None):
+    """The bivariate g-and-k example (elfi/examples/bignk.py) as ONE device operation: per simulation n_obs pairs of
+    normals with correlation rho, the g-and-k quantile function per dimension, and the summaries of gnk_summaries per
+    dimension, stacked as the reference stacks them: 'octile' (batch, 14) = [E1_d0, E1_d1, E2_d0, ...], 'robust' (batch, 8)
+    = [A_d0, A_d1, B_d0, ...]; 'order' and 'sorted' (batch, 2 n_obs) are (n_obs, 2) row-major per simulation.
+
+    z: (batch, n_obs, 2) ALREADY correlated normals, as the reference holds them (multivariate_normal.rvs(cov=[[1, rho],
+    [rho, 1]], size=n_obs) per simulation); z=None draws on the device: the pair (e0, e1) of an observation -- normals 2 j
+    and 2 j + 1 of (seed, stream) -- becomes z0 = e0, z1 = rho e0 + sqrt(1 - rho^2) e1, the distribution of the reference's
+    draws, not their bits.  |rho| <= 1.  Series and draws come back as (batch, n_obs, 2).  Otherwise as gnk_summaries."""
+    return _gnk_call((A1, A2, B1, B2, g1, g2, k1, k2, rho), 2, float(c), n_obs, z, seed, stream, summary, observed,
+                     return_series, return_draws, ctx)

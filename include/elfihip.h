@@ -611,6 +611,46 @@ int elfihip_lorenz_summaries_dev(elfihip_ctx* ctx, const double* dE, int64_t ldE
                                  double h, const double* dy0, int64_t ldy0, const double* obs, double* dS, int64_t lds,
                                  double* dY, int64_t ldy, double* dD);
 
+/* The g-and-k quantile-distribution models (elfi/examples/gnk.py, bignk.py), fused the same way: draws, the quantile
+ * function, a sort of every (simulation, dimension) column, the octiles, the robust statistics and the distance in one
+ * pass.  dim = 1 (GNK) or 2 (BiGNK), n_obs >= 2, n_obs dim <= ELFIHIP_SERIES_MAX_OBS; anything else is ELFIHIP_ERR_ARG.
+ * P (n, 4) = A, B, g, k at dim = 1, (n, 9) = A1, A2, B1, B2, g1, g2, k1, k2, rho at dim = 2 (the reference's argument
+ * order); c a host scalar.  Z (n, n_obs dim): the normals, (n_obs, dim) row-major per simulation and at dim = 2 ALREADY
+ * correlated (what multivariate_normal.rvs returns); Z == NULL: element e of the row-major (n, n_obs, dim) array is normal
+ * number e of (seed, stream), as elfihip_randn_dev writes them, and at dim = 2 the pair (e0, e1) of an observation becomes
+ * z0 = e0, z1 = (rho e0) + (sqrt(1 - rho rho) e1) -- the distribution of the reference's draws, not their bits.
+ * Per element, with the parameters of its dimension and the device's exp and pow:
+ *     y = A + ((B (1 + c ((1 - exp(-(g z))) / (1 + exp(-(g z)))))) pow(1 + z z, k)) z
+ * -- the reference's order of operations; exp(-(g z)) = inf gives NaN as there.  The series is within a few units
+ * eps (|A| + |y - A|) of NumPy's (the two exp / pow differ in the last place and the bracket amplifies that);
+ * everything after it is exact arithmetic on the series and bit-identical to NumPy:
+ * Y (n, n_obs dim): the series, (n_obs, dim) row-major per simulation -- the reference's ss_order, whose np.sort runs
+ * along the last axis.  Zo, same shape: the normals used.  Ys, same shape: every column sorted, np.sort(y, axis=1), NaNs
+ * last.  O (n, 7 dim) = [E1_d0, E1_d1, E2_d0, ...]: ss_octile = np.percentile(y, linspace(12.5, 87.5, 7), axis=1) from the
+ * positions the host computed by NumPy's virtual-index rule -- sorted neighbours a = s[lo[k]], b = s[hi[k]], weight t[k]:
+ * a + (b - a) t[k] if t[k] < 0.5, else b - (b - a) (1 - t[k]); a column that holds a NaN gives NaN throughout.
+ * R (n, 4 dim) = [A_d0, A_d1, B_d0, ...]: ss_robust, ss_A = E4, ss_B = E6 - E2 (an exactly zero ss_B becomes 0 + DBL_EPSILON),
+ * ss_g = ((E6 + E2) - 2 E4) / ss_B, ss_k = (((E7 - E5) + E3) - E1) / ss_B.
+ * D (n): euclidean distance of ONE of these rows, named by `which`, to obs (n_obs dim, 7 dim or 4 dim values); bit-identical
+ * to elfihip_dist_rows 'euclidean' on that row (whose order of summation changes at 300 values, here as there), and equal to
+ * the reference's euclidean_multiss up to the order of its sum.  The row need not be among the outputs.  The columns are
+ * sorted only when Ys, O, R or a distance on one of them is asked for.  Every output may be NULL.
+ * lo, hi, t (7 each, needed for O, R and their distances) and obs are HOST arrays in both forms; an obs of more than 64
+ * values is copied to the device on the context's stream.  _dev form: device pointers, every matrix with the caller's
+ * leading dimension (in doubles), no synchronisation.  The host form takes contiguous arrays and synchronises. */
+#define ELFIHIP_GNK_ORDER 0
+#define ELFIHIP_GNK_SORTED 1
+#define ELFIHIP_GNK_OCTILE 2
+#define ELFIHIP_GNK_ROBUST 3
+int elfihip_gnk_summaries(elfihip_ctx* ctx, const double* Z, uint64_t seed, uint64_t stream, int64_t n, int n_obs, int dim,
+                          const double* P, double c, const int* lo, const int* hi, const double* t, const double* obs,
+                          int which, double* Y, double* Zo, double* Ys, double* O, double* R, double* D);
+int elfihip_gnk_summaries_dev(elfihip_ctx* ctx, const double* dZ, int64_t ldz, uint64_t seed, uint64_t stream, int64_t n,
+                              int n_obs, int dim, const double* dP, int64_t ldp, double c, const int* lo, const int* hi,
+                              const double* t, const double* obs, int which, double* dY, int64_t ldy, double* dZo,
+                              int64_t ldzo, double* dYs, int64_t ldys, double* dO, int64_t ldo, double* dR, int64_t ldr,
+                              double* dD);
+
 /* ------------------------------------------------------------------- GP surrogate
  * Replaces the GPy model behind elfi.methods.bo.gpy_regression.GPyRegression
  * (elfi/methods/bo/gpy_regression.py:15-364): kernel RBF(variance, lengthscale) + Bias
