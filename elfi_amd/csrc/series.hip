@@ -1,5 +1,5 @@
-// ELFI's time-series example models on gfx950: ARCH(1) and the M/G/1 queue -- draws, the serial recurrence of every
-// simulation, the summaries and the distance in one pass each.
+// ELFI's time-series example models on gfx950: ARCH(1), the M/G/1 queue and the Ricker model -- draws, the serial
+// recurrence of every simulation, the summaries and the distance in one pass each.
 //
 // Replaces, for elfi/examples/arch.py:
 //     E(t2):   xi = normal((batch, n_obs + 1)); e[:, 0] = normal(batch)
@@ -10,10 +10,14 @@
 // and for elfi/examples/mg1.py:
 //     W = exponential(1 / t3), U = uniform(t1, t2), sum_w += W[i]; y[i] = U[i] + max(0, sum_w - sum_x); sum_x += y[i]
 //     log_identity = np.log(y), quantiles = np.quantile(y, q, axis=1)                                 mg1.py:40-64
+// and for elfi/examples/ricker.py:
+//     stock = stock_prev * np.exp(log_rate - stock_prev + std * randn(batch)); stock_obs[:, ii] = poisson(scale * stock)
+//     np.mean, np.var, num_zeros, chi_squared -- 2 n_obs small NumPy calls per batch                  ricker.py:11-167
 //
-// Both simulators have a recurrence along the series (ARCH: a chain of dependent square roots; M/G/1: two running sums and
-// a maximum), so a simulation belongs to ONE lane from its first step to its distance.  A workgroup is one wavefront and a
-// tile is 64 simulations (fewer only when 64 rows do not fit the LDS): the 64 lanes first fill the tile's draws together
+// All three simulators have a recurrence along the series (ARCH: a chain of dependent square roots; M/G/1: two running sums
+// and a maximum; Ricker: a chain of dependent exponentials), so a simulation belongs to ONE lane from its first step to
+// its distance.  A workgroup is one wavefront and a tile is 64 simulations (fewer when 64 rows do not fit the LDS, and 32
+// for the stochastic Ricker model, see its launch): the 64 lanes first fill the tile's draws together
 // -- coalesced loads of the caller's draws, or Philox4x32-10 pairs, every lane drawing -- then each lane runs its row's
 // recurrence in place in LDS, and stays with the row for the reductions: NumPy's pairwise sums (np_sum.hpp) with their
 // eight independent accumulators per lane, FMA contraction off, so that series, summaries and quantiles are BIT-IDENTICAL to
@@ -26,7 +30,8 @@
 // the normals elfihip_randn_dev writes for (seed, stream) -- columns 0 .. n_obs are the reference's xi (column 0 drawn and
 // unused, as there), column n_obs + 1 its e[:, 0]; M/G/1 takes element e of its (n, n_obs) standard exponentials as -log u,
 // u the 53-bit uniform in (0, 1] of word e of `stream` (the word + 1, as normal_pair forms its u1), and element e of its
-// uniforms in [0, 1) as word e of `stream + 1` (gauss.hip: uniform_pair).
+// uniforms in [0, 1) as word e of `stream + 1` (gauss.hip: uniform_pair); Ricker's (n, n_obs) normals are the normals of
+// (seed, stream) again and its Poisson count e is poisson_draw(.., seed, stream + 1, e) (poisson.hpp).
 #include "common.hpp"
 
 #include <algorithm>
@@ -35,6 +40,7 @@
 #include "dist_metrics.hpp"
 #include "np_sum.hpp"
 #include "philox.hpp"
+#include "poisson.hpp"
 
 #pragma clang fp contract(off)
 
@@ -291,6 +297,130 @@ __global__ __launch_bounds__(SERIES_THREADS) void mg1_kernel(Mg1Args A) {
   }
 }
 
+// ---- Ricker ---------------------------------------------------------------------------------------------------------
+// The stock recurrence s_i = s_{i-1} exp((log_rate - s_{i-1}) + sd z_i) is serial, one lane per simulation as in ARCH; the
+// stock takes the place of the normal it has consumed.  The Poisson observation of step i does not feed step i + 1, so
+// it is made AFTER the recurrence, element by element over the tile's rows, as the normals were drawn: all 64 lanes draw
+// whatever the number of rows in the tile, stock and counts leave in whole rows, and neighbouring lanes hold neighbouring
+// steps of one simulation (the same scale, stocks of one trajectory) -- which the sampler's branches (poisson.hpp) turn
+// out to care little about: 4 % between that order and unrelated simulations side by side.  The counts
+// replace the stock in LDS and the lane of the row reduces them.
+struct RickerArgs {
+  const double* Z;      // (n, ldz) normals, or NULL: drawn here
+  int64_t ldz;
+  uint64_t seed, stream;
+  const double* t1;     // (n) log_rate
+  const double* t2;     // (n) sd, NULL with t3: the deterministic form
+  const double* t3;     // (n) scale
+  double stock_init;
+  int64_t n;
+  int n_obs;
+  int Lp, rows;         // LDS row pitch (odd), rows per tile
+  double* S;            // (n, lds): Mean, Var, #0
+  double* Y;            // optional (n, ldy): counts (deterministic form: the stock)
+  double* St;           // optional (n, ldst): the latent stock
+  double* Zo;           // optional (n, ldzo): the normals used
+  double* D;            // optional (n)
+  int64_t lds, ldy, ldst, ldzo;
+  int which;
+  double obs[3];
+};
+
+template <bool WIDE>
+__global__ __launch_bounds__(SERIES_THREADS) void ricker_kernel(RickerArgs A) {
+  extern __shared__ __align__(16) double tile[];
+  const int tid = threadIdx.x, nobs = A.n_obs, Lp = A.Lp, Rt = A.rows;
+  const bool stochastic = A.t2 != nullptr;
+  double* sc = tile + (size_t)Rt * Lp;      // the tile's scales, for the element pass
+  const int64_t ntiles = (A.n + Rt - 1) / Rt;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t row0 = t * Rt;
+    const int rows = (int)((A.n - row0) < Rt ? (A.n - row0) : Rt);
+    __syncthreads();
+    if (stochastic) {
+      if (A.Z) {
+        for (int e = tid; e < rows * nobs; e += SERIES_THREADS) {
+          const int r = e / nobs, i = e - r * nobs;
+          const double z = A.Z[(row0 + r) * A.ldz + i];
+          tile[r * Lp + i] = z;
+          if (A.Zo) A.Zo[(row0 + r) * A.ldzo + i] = z;
+        }
+      } else {
+        // elements [e0, e1) of the row-major (n, n_obs) matrix; a pair that straddles the tile's end is drawn by both tiles
+        const int64_t e0 = row0 * nobs, e1 = e0 + (int64_t)rows * nobs;
+        for (int64_t p = e0 / 2 + tid; 2 * p < e1; p += SERIES_THREADS) {
+          double z[2];
+          normal_pair(A.seed, A.stream, (uint64_t)p, z[0], z[1]);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int64_t e = 2 * p + h;
+            if (e >= e0 && e < e1) {
+              const int off = (int)(e - e0), r = off / nobs, i = off - r * nobs;
+              tile[r * Lp + i] = z[h];
+              if (A.Zo) A.Zo[(row0 + r) * A.ldzo + i] = z[h];
+            }
+          }
+        }
+      }
+      if (tid < rows) sc[tid] = A.t3[row0 + tid];
+      __syncthreads();
+    }
+    double* w = tile + (size_t)(tid < rows ? tid : 0) * Lp;
+    const int64_t gi = row0 + tid;
+    if (tid < rows) {
+      const double a = A.t1[gi];
+      double s = A.stock_init;
+      if (stochastic) {
+        const double b = A.t2[gi];
+        for (int i = 0; i < nobs; ++i) {
+          s = s * exp((a - s) + b * w[i]);
+          w[i] = s;
+        }
+      } else {
+        w[0] = s;
+        for (int i = 1; i < nobs; ++i) {
+          s = s * exp((a - s));
+          w[i] = s;
+        }
+      }
+    }
+    if (stochastic || A.Y || A.St) {   // (uniform) the element pass: stock out, the Poisson draw, counts out, whole rows
+      __syncthreads();
+      for (int e = tid; e < rows * nobs; e += SERIES_THREADS) {
+        const int r = e / nobs, i = e - r * nobs;
+        double v = tile[r * Lp + i];
+        if (A.St) A.St[(row0 + r) * A.ldst + i] = v;
+        if (stochastic) {
+          v = poisson_draw(sc[r] * v, A.seed, A.stream + 1, (uint64_t)((row0 + r) * nobs + i));
+          tile[r * Lp + i] = v;
+        }
+        if (A.Y) A.Y[(row0 + r) * A.ldy + i] = v;
+      }
+      __syncthreads();
+    }
+    if (tid < rows) {
+      const double mean = row_sum<WIDE>([&](int i) { return w[i]; }, nobs) / (double)nobs;
+      const double var = row_sum<WIDE>([&](int i) { const double d = w[i] - mean; return d * d; }, nobs) / (double)nobs;
+      int zeros = 0;
+      for (int i = 0; i < nobs; ++i) zeros += w[i] == 0.0;
+      double* s = A.S + gi * A.lds;
+      const double nz = (double)zeros;
+      s[0] = mean;
+      s[1] = var;
+      s[2] = nz;
+      if (A.D) {
+        if (A.which == ELFIHIP_RICKER_CHI2) {
+          const double d0 = mean - A.obs[0], d1 = var - A.obs[1], d2 = nz - A.obs[2];
+          A.D[gi] = (((d0 * d0) / A.obs[0]) + ((d1 * d1) / A.obs[1])) + ((d2 * d2) / A.obs[2]);
+        } else {
+          using Euclid = Op<ELFIHIP_EUCLIDEAN, false>;
+          A.D[gi] = Euclid::finish(Euclid::step(Euclid::init(), mean, A.obs[0], 1.0, 2.0), 0.5);
+        }
+      }
+    }
+  }
+}
+
 // ---- launches ---------------------------------------------------------------------------------------------------------
 // rows per tile: one per lane, fewer only where 64 rows of `row_bytes` exceed the LDS; 0: not even one row fits
 static int tile_rows(size_t row_bytes) {
@@ -411,6 +541,61 @@ static int mg1_dev_impl(elfihip_ctx* ctx, const double* dE, int64_t lde, const d
   return launch_status(ctx, "mg1_kernel");
 }
 
+static int ricker_dev_impl(elfihip_ctx* ctx, const double* dZ, int64_t ldz, uint64_t seed, uint64_t stream, int64_t n, int n_obs,
+                           const double* dt1, const double* dt2, const double* dt3, double stock_init, const double* obs,
+                           int which, double* dS, int64_t lds, double* dY, int64_t ldy, double* dSt, int64_t ldst, double* dZo,
+                           int64_t ldzo, double* dD) {
+  ELFIHIP_REQUIRE(ctx, n >= 1 && n_obs >= 1, "bad shape n=%lld n_obs=%d (at least 1 each)", (long long)n, n_obs);
+  ELFIHIP_REQUIRE(ctx, n_obs <= ELFIHIP_SERIES_MAX_OBS, "series of %d observations: at most %d", n_obs, ELFIHIP_SERIES_MAX_OBS);
+  ELFIHIP_REQUIRE(ctx, (dt2 == nullptr) == (dt3 == nullptr), "std and scale are given together or not at all");
+  ELFIHIP_REQUIRE(ctx, dt2 || (!dZ && !dZo), "the deterministic form takes and returns no normals");
+  ELFIHIP_REQUIRE(ctx, which == ELFIHIP_RICKER_CHI2 || which == ELFIHIP_RICKER_EUCLID_MEAN, "unknown distance %d", which);
+  ELFIHIP_REQUIRE(ctx, (!dZ || ldz >= n_obs) && lds >= 3 && (!dY || ldy >= n_obs) && (!dSt || ldst >= n_obs) &&
+                           (!dZo || ldzo >= n_obs),
+                  "leading dimension below the row length");
+  ELFIHIP_REQUIRE(ctx, !dD || obs, "a distance needs the observed summaries");
+  ELFIHIP_REQUIRE(ctx, dt1 && dS, "NULL data pointer");
+  RickerArgs A;
+  A.Z = dZ;
+  A.ldz = ldz;
+  A.seed = seed;
+  A.stream = stream;
+  A.t1 = dt1;
+  A.t2 = dt2;
+  A.t3 = dt3;
+  A.stock_init = stock_init;
+  A.n = n;
+  A.n_obs = n_obs;
+  A.Lp = n_obs | 1;
+  A.S = dS;
+  A.Y = dY;
+  A.St = dSt;
+  A.Zo = dZo;
+  A.D = dD;
+  A.lds = lds;
+  A.ldy = ldy;
+  A.ldst = ldst;
+  A.ldzo = ldzo;
+  A.which = which;
+  for (int j = 0; j < 3; ++j) A.obs[j] = obs ? obs[j] : 0.0;
+  const size_t row_bytes = ((size_t)A.Lp + 1) * sizeof(double);   // the series and the row's scale
+  // the stochastic form spends its time in the Poisson pass, which wants wavefronts more than full ones: at 238 VGPRs a CU
+  // runs eight, and eight 64-row tiles of a short series do not fit its LDS, eight 32-row tiles do (n_obs 50, batch 10^6:
+  // 3.68 -> 2.82 ms; the recurrence then runs with half its lanes, which the deterministic form would only lose by)
+  A.rows = dt2 ? std::min(tile_rows(row_bytes), 32) : tile_rows(row_bytes);
+  ELFIHIP_REQUIRE(ctx, A.rows >= 1, "series of %d observations do not fit the LDS tile", n_obs);
+  const size_t bytes = (size_t)A.rows * row_bytes;
+  const unsigned grid = series_grid(ctx, n, A.rows, bytes);
+  if (n_obs > 128) {
+    ELFIHIP_TRY(set_lds(ctx, ricker_kernel<true>, bytes));
+    hipLaunchKernelGGL(ricker_kernel<true>, dim3(grid), dim3(SERIES_THREADS), bytes, ctx->stream, A);
+  } else {
+    ELFIHIP_TRY(set_lds(ctx, ricker_kernel<false>, bytes));
+    hipLaunchKernelGGL(ricker_kernel<false>, dim3(grid), dim3(SERIES_THREADS), bytes, ctx->stream, A);
+  }
+  return launch_status(ctx, "ricker_kernel");
+}
+
 }  // namespace elfihip
 
 using namespace elfihip;
@@ -510,6 +695,57 @@ int elfihip_mg1_summaries(elfihip_ctx* ctx, const double* E, const double* V, ui
   if (Y) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Y, dY, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (Eo) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Eo, dEo, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (Vo) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Vo, dVo, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ELFIHIP_OK;
+}
+
+int elfihip_ricker_summaries_dev(elfihip_ctx* ctx, const double* dZ, int64_t ldz, uint64_t seed, uint64_t stream, int64_t n,
+                                 int n_obs, const double* dlog_rate, const double* dsd, const double* dscale,
+                                 double stock_init, const double* obs, int which, double* dS, int64_t lds, double* dY,
+                                 int64_t ldy, double* dSt, int64_t ldst, double* dZo, int64_t ldzo, double* dD) {
+  if (!ctx) return fail(nullptr, ELFIHIP_ERR_ARG, "ctx is NULL");
+  DeviceGuard g(ctx->device);
+  return ricker_dev_impl(ctx, dZ, ldz, seed, stream, n, n_obs, dlog_rate, dsd, dscale, stock_init, obs, which, dS, lds, dY, ldy,
+                         dSt, ldst, dZo, ldzo, dD);
+}
+
+int elfihip_ricker_summaries(elfihip_ctx* ctx, const double* Z, uint64_t seed, uint64_t stream, int64_t n, int n_obs,
+                             const double* log_rate, const double* sd, const double* scale, double stock_init,
+                             const double* obs, int which, double* S, double* Y, double* St, double* Zo, double* D) {
+  if (!ctx) return fail(nullptr, ELFIHIP_ERR_ARG, "ctx is NULL");
+  ELFIHIP_REQUIRE(ctx, n >= 1 && n_obs >= 1 && n_obs <= ELFIHIP_SERIES_MAX_OBS, "bad shape n=%lld n_obs=%d", (long long)n, n_obs);
+  ELFIHIP_REQUIRE(ctx, (sd == nullptr) == (scale == nullptr), "std and scale are given together or not at all");
+  ELFIHIP_REQUIRE(ctx, sd || (!Z && !Zo), "the deterministic form takes and returns no normals");
+  ELFIHIP_REQUIRE(ctx, log_rate && S, "NULL data pointer");
+  ELFIHIP_REQUIRE(ctx, !D || obs, "a distance needs the observed summaries");
+  DeviceGuard g(ctx->device);
+  const size_t nn = (size_t)n * n_obs, nz = Z ? nn : 0, np_ = sd ? 3 * (size_t)n : (size_t)n;
+  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((nz + np_) * sizeof(double)));
+  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((4 * (size_t)n + (Y ? nn : 0) + (St ? nn : 0) + (Zo ? nn : 0)) * sizeof(double)));
+  double* dZ = ctx->in.as<double>();
+  double* dt1 = dZ + nz;
+  double* dt2 = dt1 + n;
+  double* dt3 = dt2 + n;
+  double* dS = ctx->out.as<double>();
+  double* dD = dS + 3 * (size_t)n;
+  double* dY = dD + n;
+  double* dSt = dY + (Y ? nn : 0);
+  double* dZo = dSt + (St ? nn : 0);
+  const size_t pb = (size_t)n * sizeof(double);
+  if (Z) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dZ, Z, nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt1, log_rate, pb, hipMemcpyHostToDevice, ctx->stream));
+  if (sd) {
+    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt2, sd, pb, hipMemcpyHostToDevice, ctx->stream));
+    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt3, scale, pb, hipMemcpyHostToDevice, ctx->stream));
+  }
+  ELFIHIP_TRY(ricker_dev_impl(ctx, Z ? dZ : nullptr, n_obs, seed, stream, n, n_obs, dt1, sd ? dt2 : nullptr, sd ? dt3 : nullptr,
+                              stock_init, obs, which, dS, 3, Y ? dY : nullptr, n_obs, St ? dSt : nullptr, n_obs,
+                              Zo ? dZo : nullptr, n_obs, D ? dD : nullptr));
+  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(S, dS, 3 * pb, hipMemcpyDeviceToHost, ctx->stream));
+  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, pb, hipMemcpyDeviceToHost, ctx->stream));
+  if (Y) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Y, dY, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (St) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(St, dSt, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (Zo) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Zo, dZo, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ELFIHIP_OK;
 }

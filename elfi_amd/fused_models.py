@@ -7,6 +7,7 @@
     m = elfi_amd.fused_models.lorenz_model(seed_obs=4)                # elfi.examples.lorenz.get_model(...)
     m = elfi_amd.fused_models.gnk_model(n_obs=50, seed=4)             # elfi.examples.gnk.get_model(...)
     m = elfi_amd.fused_models.bignk_model(n_obs=150, seed=4)          # elfi.examples.bignk.get_model(...)
+    m = elfi_amd.fused_models.ricker_model(n_obs=50, seed_obs=4)      # elfi.examples.ricker.get_model(...)
     elfi_amd.HipRejection(m['d'], batch_size=10**6, seed=1).sample(1000, n_sim=10**8)
 
 The reference's Simulator node draws the series on the host (MA2: random_state.randn(batch, n_obs + 2),
@@ -42,6 +43,16 @@ eps (|A| + |y - A|) of the reference's on given draws, and every summary NumPy's
 (tests/test_gnk_gpu.py).  The bivariate model's correlated normals are z0 = e0, z1 = rho e0 + sqrt(1 - rho^2) e1 of the
 device generator: the distribution of the reference's multivariate_normal.rvs draws, not their bits.
 
+ricker_model is the Ricker example (elfi/examples/ricker.py: a chaotic stock recurrence observed through a Poisson count;
+the deterministic variant without noise and observation layer) on csrc/series.hip, built like arch_model: a lane walks the
+stock of its simulation, then the wavefront draws the tile's Poisson counts element by element with the library's
+counter-based sampler (csrc/poisson.hpp: inversion below an intensity of 10, transformed rejection from there on).  Its
+Simulator node returns the (batch, 3) columns Mean, Var, #0; d is an elfi.Discrepancy over the reference's chi_squared
+stated in NumPy (deterministic: elfi.Distance over HipDistance('euclidean') on Mean).  Each step of the stock is within 4
+ulp of NumPy's on the same previous stock, the counts are the NumPy statement's of the sampler and the summaries NumPy's bit
+for bit on the device's counts (tests/test_ricker_gpu.py).  An overflowed stock is observed as NaN, where the reference
+raises ValueError for the whole batch.
+
 The draws are the device generator's, not MT19937's: a run of this model is a different (equally valid) random
 realisation than a run of elfi.examples.*.get_model with the same seed; the arithmetic on given draws is bit-identical
 to the reference's (tests/test_summaries_gpu.py, tests/test_gauss_gpu.py).
@@ -56,6 +67,7 @@ from .distance import HipDistance, randn_rows
 from .priors import SIMULATOR_STREAM_BASE
 from .summaries import LORENZ_NAMES, arch_summaries, gauss_distance, lorenz_summaries, ma2_draw_distance, mg1_summaries
 from .summaries import GNK_SUMMARIES, bignk_summaries, gnk_summaries
+from .summaries import RICKER_NAMES, ricker_summaries
 
 
 def _elfi():
@@ -353,6 +365,57 @@ def bignk_model(n_obs=150, true_params=None, seed=None, summary='robust', device
                    observed=_observed_rows(gnk, y_obs, summary), name='BiGNK')
     ss = elfi.Summary(rows_as_points, m['BiGNK'], name='ss_' + summary)
     elfi.Discrepancy(euclidean_rows, ss, name='d')
+    return m
+
+
+def ricker_summary_rows(log_rate, std=None, scale=None, stock_init=1., n_obs=50, batch_size=1, random_state=None):
+    """Simulator operation: (batch, 3) summaries Mean, Var, #0 of Ricker series drawn, run, observed and reduced on the
+    device (std = scale = None: the deterministic model)."""
+    if std is None:
+        log_rate, = _per_simulation(batch_size, log_rate)
+    else:
+        log_rate, std, scale = _per_simulation(batch_size, log_rate, std, scale)
+    return ricker_summaries(log_rate, std, scale, stock_init=stock_init, n_obs=n_obs, seed=_seed_of(random_state),
+                            stream=SIMULATOR_STREAM_BASE)
+
+
+def chi_squared(*simulated, observed):
+    """Discrepancy operation of the Ricker model: the reference's chi_squared (ricker.py:147-161)."""
+    simulated = np.column_stack(simulated)
+    observed = np.column_stack(observed)
+    with np.errstate(all='ignore'):
+        return np.sum((simulated - observed) ** 2. / observed, axis=1)
+
+
+def ricker_model(n_obs=50, true_params=None, seed_obs=None, stochastic=True, device_priors=True):
+    """elfi.examples.ricker.get_model(n_obs, true_params, seed_obs, stochastic) with the simulation on the device; nodes t1,
+    t2, t3, Ricker, Mean, Var, #0, d (stochastic=False: t1, Ricker, Mean, d).  The node Ricker returns the (batch, 3)
+    summaries, the Summary nodes pick their column; d is an elfi.Discrepancy over chi_squared (deterministic: elfi.Distance
+    over HipDistance('euclidean')).  The observed series is the reference's own simulator with RandomState(seed_obs), reduced
+    once with NumPy.  device_priors: t3's uniform prior draws on the device (elfi_amd.priors.uniform); the expon and
+    truncnorm priors stay SciPy's."""
+    elfi = _elfi()
+    from elfi.examples import ricker
+    import scipy.stats as ss
+    simulator = ricker.stochastic_ricker if stochastic else ricker.ricker
+    if true_params is None:
+        true_params = [3.8, 0.3, 10.] if stochastic else [3.8]
+    y = simulator(*true_params, n_obs=n_obs, random_state=np.random.RandomState(seed_obs))
+    obs = np.column_stack([np.mean(y, axis=1), np.var(y, axis=1), ricker.num_zeros(y)]).astype(np.float64)
+    m = elfi.ElfiModel()
+    from . import priors
+    if stochastic:
+        elfi.Prior(ss.expon, np.e, 2, model=m, name='t1')
+        elfi.Prior(ss.truncnorm, 0, 5, model=m, name='t2')
+        elfi.Prior(priors.uniform if device_priors else ss.uniform, 0, 100, model=m, name='t3')
+        elfi.Simulator(partial(ricker_summary_rows, n_obs=n_obs), m['t1'], m['t2'], m['t3'], observed=obs, name='Ricker')
+        sumstats = [elfi.Summary(partial(column, j=k), m['Ricker'], name=name) for k, name in enumerate(RICKER_NAMES)]
+        elfi.Discrepancy(chi_squared, *sumstats, name='d')
+    else:
+        elfi.Prior(ss.expon, np.e, model=m, name='t1')
+        elfi.Simulator(partial(ricker_summary_rows, n_obs=n_obs), m['t1'], observed=obs, name='Ricker')
+        mean = elfi.Summary(partial(column, j=0), m['Ricker'], name='Mean')
+        elfi.Distance(HipDistance('euclidean'), mean, name='d')
     return m
 
 

@@ -13,6 +13,8 @@ leading dimension of 1 -- elfi/model/elfi_model.py:915-943, elfi/compiler.py:94-
     lorenz_summaries(...)  the fused stochastic Lorenz-96 example: series + 6 summaries [+ distance]   elfi/examples/lorenz.py
     gnk_summaries(...), bignk_summaries(...)  the fused g-and-k examples: series, order statistics, octiles, robust
                          statistics [+ distance]                                      elfi/examples/gnk.py, bignk.py
+    ricker_summaries(...)  the fused Ricker example: stock, Poisson counts, Mean / Var / #0 [+ distance]  elfi/examples/ricker.py
+    poisson(lam, ...)    Poisson variates from the library's counter-based generator (csrc/poisson.hpp)
 
     S1 = elfi.Summary(elfi_amd.autocov, Y);  S2 = elfi.Summary(elfi_amd.autocov, Y, 2)
 
@@ -426,3 +428,83 @@ def bignk_summaries(A1, A2, B1, B2, g1, g2, k1, k2, rho, c=0.8, n_obs=150, z=Non
     draws, not their bits.  |rho| <= 1.  Series and draws come back as (batch, n_obs, 2).  Otherwise as gnk_summaries."""
     return _gnk_call((A1, A2, B1, B2, g1, g2, k1, k2, rho), 2, float(c), n_obs, z, seed, stream, summary, observed,
                      return_series, return_draws, ctx)
+
+
+# ---- Poisson variates and the Ricker example model (csrc/poisson.hpp, csrc/series.hip) ------------------------------
+RICKER_DISTANCES = ('chi_squared', 'euclidean_mean')     # include/elfihip.h: ELFIHIP_RICKER_CHI2, _EUCLID_MEAN
+RICKER_NAMES = ('Mean', 'Var', '#0')
+
+
+def poisson(lam, seed=0, stream=0, ctx=None):
+    """Poisson variates with intensities `lam` from the library's counter-based generator, in the shape of `lam`, as
+    float64: element e of the flattened array is a fixed function of lam[e] and of Philox counter e of the streams (seed,
+    stream), (seed, stream + 1), ... -- inversion below 10, Hoermann's transformed rejection (NumPy's legacy algorithm) from
+    10 on, one stream per attempt; a fused kernel that draws element e itself gets the same number.  lam == 0 gives 0.
+    A NaN, negative or above-2^53 intensity gives NaN for that element (RandomState.poisson raises ValueError for the
+    whole batch instead)."""
+    lam = np.asarray(lam, dtype=np.float64)
+    flat = np.ascontiguousarray(lam.reshape(-1))
+    out = np.empty(flat.shape[0])
+    if flat.shape[0] == 0:
+        return out.reshape(lam.shape)
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_poisson", C.c_uint64(int(seed)), C.c_uint64(int(stream)), flat.shape[0], _lib.ptr(flat), _lib.ptr(out))
+    return out.reshape(lam.shape)
+
+
+def ricker_summaries(log_rate, std=None, scale=None, stock_init=1., n_obs=50, noise=None, seed=0, stream=0, observed=None,
+                     distance='chi_squared', return_series=False, return_stock=False, return_draws=False, ctx=None):
+    """The Ricker example (elfi/examples/ricker.py) as ONE device operation: the stock s_i = s_{i-1} exp(log_rate - s_{i-1} +
+    std z_i), s_0 = stock_init, its Poisson observation y_i ~ Poisson(scale s_i) and the summaries Mean = np.mean(y, axis=1),
+    Var = np.var(y, axis=1), #0 = the number of zero observations.  std = scale = None is the deterministic model: y_0 =
+    stock_init, y_i = y_{i-1} exp(log_rate - y_{i-1}), no draws (both are given or both None).
+
+    log_rate, std, scale: (batch,) or scalars; stock_init a scalar.  noise: (batch, n_obs) standard normals, the
+    reference's randn(batch) of step i in column i - 1 (any other shape is a ValueError); noise=None draws on the device
+    (Philox4x32-10 keyed by `seed`, counter stream `stream`).  The Poisson counts are always the device's: element e =
+    row * n_obs + i - 1 is elfi_amd.poisson's element e on the streams from `stream + 1` on.  A stock that has underflowed
+    to 0 is observed as 0, one that has overflowed as NaN (the reference raises ValueError for the whole batch).
+    observed: the 3 observed summaries; with them the distance is returned too -- 'chi_squared' (the reference's: sum((S -
+    obs)^2 / obs)) or 'euclidean_mean' (euclidean on the Mean column alone, the deterministic model's d).
+    Returns S (batch, 3) [, series (batch, n_obs)] [, stock (batch, n_obs)] [, normals (batch, n_obs)] [, d (batch,)] -- the
+    bare array when nothing else is asked for."""
+    n_obs = int(n_obs)
+    if (std is None) != (scale is None):
+        raise ValueError('std and scale are given together (the stochastic model) or not at all (the deterministic one)')
+    stochastic = std is not None
+    if distance not in RICKER_DISTANCES:
+        raise ValueError('distance must be one of %s' % (RICKER_DISTANCES,))
+    if not 1 <= n_obs <= SERIES_MAX_OBS:
+        raise ValueError('n_obs must be in [1, %d]' % SERIES_MAX_OBS)
+    if noise is not None:
+        if not stochastic:
+            raise ValueError('the deterministic model takes no noise')
+        noise = np.asarray(noise)
+        if noise.ndim != 2 or noise.shape[1] != n_obs:
+            raise ValueError('noise must be (batch, n_obs) = (batch, %d)' % n_obs)
+    if return_draws and not stochastic:
+        raise ValueError('the deterministic model makes no draws')
+    params = (log_rate, std, scale) if stochastic else (log_rate,)
+    n = noise.shape[0] if noise is not None else _batch_of(*params)
+    if n < 1:
+        raise ValueError('need at least one simulation')
+    params = _params(n, *params)
+    obs = None
+    if observed is not None:
+        obs = np.ascontiguousarray(np.asarray(observed, dtype=np.float64).reshape(-1))
+        if obs.shape[0] != 3:
+            raise ValueError('observed must hold the 3 observed summaries Mean, Var, #0')
+    if noise is not None:
+        noise = np.ascontiguousarray(noise, dtype=np.float64)
+    S = np.empty((n, 3))
+    Y = np.empty((n, n_obs)) if return_series else None
+    St = np.empty((n, n_obs)) if return_stock else None
+    Zo = np.empty((n, n_obs)) if return_draws else None
+    D = np.empty(n) if obs is not None else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_ricker_summaries", _lib.ptr(noise), C.c_uint64(int(seed)), C.c_uint64(int(stream)), n, n_obs,
+             _lib.ptr(params[0]), _lib.ptr(params[1]) if stochastic else None, _lib.ptr(params[2]) if stochastic else None,
+             C.c_double(float(stock_init)), _lib.ptr(obs), RICKER_DISTANCES.index(distance), _lib.ptr(S), _lib.ptr(Y),
+             _lib.ptr(St), _lib.ptr(Zo), _lib.ptr(D))
+    out = tuple(a for a in (S, Y, St, Zo, D) if a is not None)
+    return out if len(out) > 1 else S

@@ -586,6 +586,63 @@ int elfihip_mg1_summaries_dev(elfihip_ctx* ctx, const double* dE, int64_t lde, c
                               double* dLogY, int64_t ldl, double* dQ, int64_t ldq, double* dY, int64_t ldy, double* dEo,
                               int64_t ldeo, double* dVo, int64_t ldvo, double* dD);
 
+/* Counter-based Poisson variates: out[e] = poisson_draw(lam[e], seed, stream, e), e < n, a deterministic function of lam[e]
+ * and the generator's words, so element e does not depend on n or on where it is drawn (csrc/poisson.hpp; the NumPy
+ * statement is tests/ricker_ref.py: poisson_ref).  Attempt j = 0, 1, .. of element e reads Philox counter e of stream
+ * (seed, stream + j): u1 = ((r0 << 21) | (r1 >> 11)) 2^-53, u2 the same of words 2, 3, both in [0, 1).  The result is a double:
+ *   lam NaN, lam < 0 or lam > 2^53: NaN.  (RandomState.poisson raises ValueError for the whole batch; here the element
+ *     is marked and the batch goes on.)
+ *   lam == 0: 0, no draw.
+ *   0 < lam < 10: inversion on u1 of attempt 0 -- p = F = exp(-lam), k = 0; while u1 > F and k < ELFIHIP_POISSON_MAX_K:
+ *     k += 1, p = p (lam / k), F = F + p; the result is k.
+ *   lam >= 10: Hoermann's PTRS, the algorithm of NumPy's legacy poisson.  slam = sqrt(lam), loglam = log(lam), b = 0.931 +
+ *     2.53 slam, a = -0.059 + 0.02483 b, invalpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2).  Per
+ *     attempt: U = u1 - 0.5, V = u2, us = 0.5 - |U|, k = floor((2 a / us + b) U + lam + 0.43); accept k if us >= 0.07 and
+ *     V <= vr; else reject if k < 0 or (us < 0.013 and V > us); else accept iff log(V) + log(invalpha) - log(a / (us us) + b)
+ *     <= -lam + k loglam - lgamma(k + 1).  After ELFIHIP_POISSON_MAX_ATTEMPTS rejections (an attempt rejects with
+ *     probability 0.25 at lam = 10, below 0.14 at large lam: probability below 1e-38; the bound only makes the loop finite)
+ *     the result is floor(lam).
+ * The device's exp, log and lgamma differ from the host's in the last places, so a draw whose u1 lies within 2^-44 of a
+ * cumulative probability, or whose PTRS test is decided in the last bits, may differ from the NumPy statement by one
+ * acceptance decision; above lam = 10^6 only the distribution is claimed.  Host form: host pointers, synchronises; _dev
+ * form: device pointers, no synchronisation. */
+#define ELFIHIP_POISSON_MAX_K 128
+#define ELFIHIP_POISSON_MAX_ATTEMPTS 64
+int elfihip_poisson(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t n, const double* lam, double* out);
+int elfihip_poisson_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t n, const double* dlam, double* dout);
+
+/* The Ricker model (elfi/examples/ricker.py), fused as the time-series models above: draws, the stock recurrence of every
+ * simulation, the Poisson observation of every step, the three summaries and the distance in one pass.  1 <= n_obs <=
+ * ELFIHIP_SERIES_MAX_OBS and n >= 1; anything else is ELFIHIP_ERR_ARG, and so is a distance without obs.
+ * Stochastic form (stochastic_ricker): log_rate, sd (the reference's std), scale (n each), stock_init a host scalar.  Z (n, n_obs) standard
+ * normals -- the reference's randn(batch) of step i in column i - 1; Z == NULL: element e of the row-major matrix is normal
+ * number e of (seed, stream), as elfihip_randn_dev writes it.  With s_0 = stock_init, for i = 1 .. n_obs, the device's exp:
+ *     s_i = s_{i-1} exp((log_rate - s_{i-1}) + sd z_i)           y_i = poisson_draw(scale s_i, seed, stream + 1, e)
+ * with e = row n_obs + i - 1 (attempt j of that element reads stream + 1 + j; the normals keep `stream` to themselves).  A
+ * stock that has underflowed to 0 is observed as 0; one that has overflowed (s = inf, then NaN) as NaN.
+ * Deterministic form (ricker), selected by sd == scale == NULL (one without the other is ELFIHIP_ERR_ARG; Z and Zo must
+ * be NULL): y_0 = stock_init, y_i = y_{i-1} exp((log_rate - y_{i-1})), i = 1 .. n_obs - 1; no draws.
+ * Each step is within an ulp or two of NumPy's on the same s_{i-1} (the exponential's argument is formed identically);
+ * the map is chaotic, so whole trajectories are not comparable.  Everything after the series is exact arithmetic on it,
+ * bit-identical to NumPy: S (n, 3) = Mean np.mean(y, axis=1), Var np.var(y, axis=1) (ddof 0), #0 np.sum(y == 0, axis=1) as a
+ * double.  Optional outputs, each may be NULL: Y (n, n_obs) the observed counts (deterministic form: the stock), St (n,
+ * n_obs) the latent stock s_1 .. s_n_obs (deterministic form: the same series as Y), Zo (n, n_obs) the normals used, D (n)
+ * the distance of the row of S to obs (3 host values) named by `which`:
+ *   ELFIHIP_RICKER_CHI2         (((S0 - o0)^2 / o0) + ((S1 - o1)^2 / o1)) + ((S2 - o2)^2 / o2), the reference's chi_squared; an
+ *                               observed 0 gives inf or NaN as there
+ *   ELFIHIP_RICKER_EUCLID_MEAN  sqrt((S0 - o0)^2), bit-identical to elfihip_dist_rows 'euclidean' on the Mean column
+ * Host form: contiguous host arrays, synchronises.  _dev form: device pointers, Z, S, Y, St, Zo with the caller's leading
+ * dimension (in doubles), no synchronisation.  obs is a host array in both. */
+#define ELFIHIP_RICKER_CHI2 0
+#define ELFIHIP_RICKER_EUCLID_MEAN 1
+int elfihip_ricker_summaries(elfihip_ctx* ctx, const double* Z, uint64_t seed, uint64_t stream, int64_t n, int n_obs,
+                             const double* log_rate, const double* sd, const double* scale, double stock_init,
+                             const double* obs, int which, double* S, double* Y, double* St, double* Zo, double* D);
+int elfihip_ricker_summaries_dev(elfihip_ctx* ctx, const double* dZ, int64_t ldz, uint64_t seed, uint64_t stream, int64_t n,
+                                 int n_obs, const double* dlog_rate, const double* dsd, const double* dscale,
+                                 double stock_init, const double* obs, int which, double* dS, int64_t lds, double* dY,
+                                 int64_t ldy, double* dSt, int64_t ldst, double* dZo, int64_t ldzo, double* dD);
+
 /* The stochastic Lorenz-96 forecast model (elfi/examples/lorenz.py), fused the same way: draws, the Runge-Kutta recurrence,
  * the six summaries and the distance in one pass; series and summaries bit-identical to the reference's NumPy on the same
  * draws.  K = n_obs variables in 4 .. ELFIHIP_LORENZ_MAX_VARS, T = n_timestep >= 2 rows, T K <= ELFIHIP_LORENZ_MAX_TERMS
