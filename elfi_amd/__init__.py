@@ -29,9 +29,11 @@ from .summaries import autocov, gauss_distance, ma2_distance, ma2_draw_distance,
 from .summaries import arch_summaries, lorenz_summaries, mg1_summaries  # noqa: F401
 from .summaries import bignk_summaries, gnk_summaries  # noqa: F401
 from .summaries import poisson, ricker_summaries  # noqa: F401
+from .summaries import lotka_volterra_draws, lotka_volterra_summaries  # noqa: F401
 from .fused_models import arch_model, lorenz_model, mg1_model  # noqa: F401
 from .fused_models import bignk_model, gnk_model  # noqa: F401
 from .fused_models import ricker_model  # noqa: F401
+from .fused_models import lotka_volterra_model, lv_summary_rows  # noqa: F401
 from .lcb_acquisition import HipLCBSC  # noqa: F401
 from .posterior import HipBolfiPosterior, sample_posterior  # noqa: F401
 from .bolfi import HipBOLFI, hip_bolfi_class  # noqa: F401

@@ -242,6 +242,15 @@ PROTOTYPES = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int,
                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                C.c_void_p, C.c_int64, C.c_void_p]),
+    "elfihip_lv_summaries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64,
+                                       C.c_int64, C.c_int, C.c_double, C.c_int64] + [C.c_void_p] * 13),
+    "elfihip_lv_summaries_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_int64] +
+                                 [C.c_void_p] * 8 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                     C.c_void_p]),
+    "elfihip_lv_draws": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "elfihip_lv_draws_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                       C.c_int64, C.c_void_p, C.c_int64]),
     "elfihip_randn_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_double, C.c_double, C.c_void_p]),
     "elfihip_random_bits_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p]),
     "elfihip_gp_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, c_void_pp]),

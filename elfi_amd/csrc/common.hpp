@@ -80,6 +80,8 @@ struct elfihip_ctx {
   elfihip::DevBuf stat;   // workgroup partials of the fused adaptive-distance pass (adaptive.hip; topk.hip owns `scratch`)
   elfihip::DevBuf sel;    // twostage.hip: a block of subset distances and its survivors; the partial sums of the entropy
                           // adjust.hip: the tile factors, the tile sums, the jobs' means and coefficients
+  elfihip::DevBuf lv;     // gillespie.hip: the counter simulations are dealt from, and the observations when the caller keeps none
+  int lv_per_cu[4] = {0, 0, 0, 0};   // gillespie.hip: resident workgroups per CU of lv_sim_kernel<DRAWN, NOISE>, asked for once
   // the distances the last host-form distance call returned, kept on the device for the sampler state
   // (elfihip_kept_distances / elfihip_reject_push_kept): (keep_n, keep_cols) row-major; the epoch names the call
   elfihip::DevBuf keep;

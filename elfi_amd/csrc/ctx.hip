@@ -165,6 +165,7 @@ int elfihip_ctx_destroy(elfihip_ctx* ctx) {
     ctx->scratch.release();
     ctx->stat.release();
     ctx->sel.release();
+    ctx->lv.release();
     ctx->keep.release();
     ctx->rows.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

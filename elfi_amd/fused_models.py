@@ -8,6 +8,7 @@
     m = elfi_amd.fused_models.gnk_model(n_obs=50, seed=4)             # elfi.examples.gnk.get_model(...)
     m = elfi_amd.fused_models.bignk_model(n_obs=150, seed=4)          # elfi.examples.bignk.get_model(...)
     m = elfi_amd.fused_models.ricker_model(n_obs=50, seed_obs=4)      # elfi.examples.ricker.get_model(...)
+    m = elfi_amd.fused_models.lotka_volterra_model(seed_obs=4)        # elfi.examples.lotka_volterra.get_model(...)
     elfi_amd.HipRejection(m['d'], batch_size=10**6, seed=1).sample(1000, n_sim=10**8)
 
 The reference's Simulator node draws the series on the host (MA2: random_state.randn(batch, n_obs + 2),
@@ -53,6 +54,16 @@ ulp of NumPy's on the same previous stock, the counts are the NumPy statement's 
 for bit on the device's counts (tests/test_ricker_gpu.py).  An overflowed stock is observed as NaN, where the reference
 raises ValueError for the whole batch.
 
+lotka_volterra_model is the stochastic predator-prey example (elfi/examples/lotka_volterra.py: a Markov jump process
+simulated by Gillespie's direct method, whose number of events per simulation varies over three orders of magnitude under
+the priors) on csrc/gillespie.hip: one lane per simulation in persistent wavefronts that take the next simulation from a
+counter as soon as theirs ends, observations emitted as the events pass their times, then the nine summaries.  Its
+Simulator node LV returns the (batch, 9) summaries, the Summary nodes pick their column, d is elfi.Distance over
+HipDistance('euclidean').  Observations, event counts and final times are the NumPy statement's bit for bit on given draws;
+the summaries are NumPy's bit for bit except the two log-variances (within 4 ulp, the device's log)
+(tests/test_lotka_volterra_gpu.py).  A simulation is cut off after max_events events (default 2^20) with NaN summaries, where
+the reference runs on without bound.
+
 The draws are the device generator's, not MT19937's: a run of this model is a different (equally valid) random
 realisation than a run of elfi.examples.*.get_model with the same seed; the arithmetic on given draws is bit-identical
 to the reference's (tests/test_summaries_gpu.py, tests/test_gauss_gpu.py).
@@ -68,6 +79,7 @@ from .priors import SIMULATOR_STREAM_BASE
 from .summaries import LORENZ_NAMES, arch_summaries, gauss_distance, lorenz_summaries, ma2_draw_distance, mg1_summaries
 from .summaries import GNK_SUMMARIES, bignk_summaries, gnk_summaries
 from .summaries import RICKER_NAMES, ricker_summaries
+from .summaries import LV_NAMES, lotka_volterra_summaries
 
 
 def _elfi():
@@ -416,6 +428,58 @@ def ricker_model(n_obs=50, true_params=None, seed_obs=None, stochastic=True, dev
         elfi.Simulator(partial(ricker_summary_rows, n_obs=n_obs), m['t1'], observed=obs, name='Ricker')
         mean = elfi.Summary(partial(column, j=0), m['Ricker'], name='Mean')
         elfi.Distance(HipDistance('euclidean'), mean, name='d')
+    return m
+
+
+def lv_summary_rows(r1, r2, r3, prey_init=50, predator_init=100, sigma=None, n_obs=16, time_end=30., max_events=1 << 20,
+                    batch_size=1, random_state=None):
+    """Simulator operation: (batch, 9) summaries of Lotka-Volterra trajectories simulated, observed and reduced on the
+    device (sigma None: no observation noise)."""
+    params = (r1, r2, r3, prey_init, predator_init) + (() if sigma is None else (sigma,))
+    params = _per_simulation(batch_size, *params)
+    return lotka_volterra_summaries(*params, n_obs=n_obs, time_end=time_end, max_events=max_events,
+                                    seed=_seed_of(random_state), stream=SIMULATOR_STREAM_BASE)
+
+
+def lotka_volterra_model(n_obs=50, true_params=None, observation_noise=False, seed_obs=None, device_priors=True, **kwargs):
+    """elfi.examples.lotka_volterra.get_model(n_obs, true_params, observation_noise, seed_obs, **kwargs) with the simulation
+    on the device; nodes r1, r2, r3, prey0, predator0 [, sigma], LV, the nine summaries LV_NAMES, d.  The node LV returns
+    the (batch, 9) summaries, the Summary nodes pick their column; d is elfi.Distance over HipDistance('euclidean').  kwargs
+    go to the simulator (time_end, max_events; prey_init and the like are parameters).  The observed series is the
+    reference's own simulator with RandomState(seed_obs), reduced once with the reference's summary functions.
+    device_priors: the ExpUniform priors draw on the device (elfi_amd.priors.ExpUniform); the normal priors stay SciPy's."""
+    if true_params is None:
+        true_params = [1.0, 0.005, 0.6, 50, 100, 10.] if observation_noise else [1.0, 0.005, 0.6, 50, 100, 0.]
+    elif observation_noise:
+        if len(true_params) != 6:
+            raise ValueError("Option observation_noise = True. Provide six input parameters.")
+    else:
+        if len(true_params) != 5:
+            raise ValueError("Option observation_noise = False. Provide five input parameters.")
+        true_params = list(true_params) + [0]
+    elfi = _elfi()
+    from elfi.examples import lotka_volterra as lv
+    from . import priors
+    kwargs = dict(kwargs, n_obs=n_obs)
+    ref_kwargs = {k: v for k, v in kwargs.items() if k != 'max_events'}
+    y = lv.lotka_volterra(*true_params, random_state=np.random.RandomState(seed_obs), **ref_kwargs)
+    fns = [partial(lv.stock_mean, species=0), partial(lv.stock_mean, species=1), partial(lv.stock_log_variance, species=0),
+           partial(lv.stock_log_variance, species=1), partial(lv.stock_autocorr, species=0, lag=1),
+           partial(lv.stock_autocorr, species=1, lag=1), partial(lv.stock_autocorr, species=0, lag=2),
+           partial(lv.stock_autocorr, species=1, lag=2), lv.stock_crosscorr]
+    obs = np.column_stack([f(y) for f in fns]).astype(np.float64)
+    m = elfi.ElfiModel()
+    exp_uniform = priors.ExpUniform if device_priors else lv.ExpUniform
+    nodes = [elfi.Prior(exp_uniform, -6., 2., model=m, name='r1'),
+             elfi.Prior(exp_uniform, -6., 2., model=m, name='r2'),
+             elfi.Prior(exp_uniform, -6., 2., model=m, name='r3'),
+             elfi.Prior('normal', 50, np.sqrt(50), model=m, name='prey0'),
+             elfi.Prior('normal', 100, np.sqrt(100), model=m, name='predator0')]
+    if observation_noise:
+        nodes.append(elfi.Prior(exp_uniform, np.log(0.5), np.log(50), model=m, name='sigma'))
+    elfi.Simulator(partial(lv_summary_rows, **kwargs), *nodes, observed=obs, name='LV')
+    sumstats = [elfi.Summary(partial(column, j=k), m['LV'], name=name) for k, name in enumerate(LV_NAMES)]
+    elfi.Distance(HipDistance('euclidean'), *sumstats, name='d')
     return m
 
 

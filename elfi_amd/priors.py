@@ -3,6 +3,7 @@
     elfi.Prior(elfi_amd.priors.uniform, 0, 2, model=m, name='mu')          # ss.uniform
     elfi.Prior(elfi_amd.priors.MA2Prior1, 2, model=m, name='t1')           # elfi.examples.ma2.CustomPrior1
     elfi.Prior(elfi_amd.priors.MA2Prior2, m['t1'], 1, name='t2')           # elfi.examples.ma2.CustomPrior2
+    elfi.Prior(elfi_amd.priors.ExpUniform, -6., 2., model=m, name='r1')    # elfi.examples.lotka_volterra.ExpUniform
 
 A Prior node's operation is rvs_from_distribution (elfi/model/utils.py:6-35): `distribution.rvs(*params, size=(batch,),
 random_state=...)` -- scipy.stats on the host.  Once simulator and distance run on the GPU that call is most of what is
@@ -92,6 +93,30 @@ class uniform:
     def ppf(cls, q, loc=0, scale=1):
         import scipy.stats as ss
         return ss.uniform.ppf(q, loc, scale)
+
+
+class ExpUniform:
+    """elfi.examples.lotka_volterra.ExpUniform: log x ~ Uniform(a, b).  The uniform is drawn on the device, np.exp is taken on
+    the host (as the reference takes it); pdf / logpdf are the running ELFI's own class's."""
+
+    @classmethod
+    def _reference(cls):
+        from elfi.examples import lotka_volterra
+        return lotka_volterra.ExpUniform
+
+    @classmethod
+    def rvs(cls, a, b, size=1, random_state=None):
+        if np.ndim(a) or np.ndim(b):
+            raise ValueError('elfi_amd.priors.ExpUniform draws with scalar a / b (a prior without parent nodes)')
+        return np.exp(prior_draw(UNIFORM, (a, b - a), None, size, random_state))
+
+    @classmethod
+    def pdf(cls, x, a, b):
+        return cls._reference().pdf(x, a, b)
+
+    @classmethod
+    def logpdf(cls, x, a, b):
+        return cls._reference().logpdf(x, a, b)
 
 
 class _MA2Backed:

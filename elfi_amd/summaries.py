@@ -15,6 +15,8 @@ leading dimension of 1 -- elfi/model/elfi_model.py:915-943, elfi/compiler.py:94-
                          statistics [+ distance]                                      elfi/examples/gnk.py, bignk.py
     ricker_summaries(...)  the fused Ricker example: stock, Poisson counts, Mean / Var / #0 [+ distance]  elfi/examples/ricker.py
     poisson(lam, ...)    Poisson variates from the library's counter-based generator (csrc/poisson.hpp)
+    lotka_volterra_summaries(...)  the stochastic Lotka-Volterra example: Gillespie simulation, observations, 9 summaries
+                         [+ distance]                                             elfi/examples/lotka_volterra.py
 
     S1 = elfi.Summary(elfi_amd.autocov, Y);  S2 = elfi.Summary(elfi_amd.autocov, Y, 2)
 
@@ -507,4 +509,104 @@ def ricker_summaries(log_rate, std=None, scale=None, stock_init=1., n_obs=50, no
              C.c_double(float(stock_init)), _lib.ptr(obs), RICKER_DISTANCES.index(distance), _lib.ptr(S), _lib.ptr(Y),
              _lib.ptr(St), _lib.ptr(Zo), _lib.ptr(D))
     out = tuple(a for a in (S, Y, St, Zo, D) if a is not None)
+    return out if len(out) > 1 else S
+
+
+# ---- the stochastic Lotka-Volterra example model (csrc/gillespie.hip) -------------------------------------------------
+LV_NAMES = ('prey_mean', 'pred_mean', 'prey_log_var', 'pred_log_var', 'prey_autocorr_1', 'pred_autocorr_1',
+            'prey_autocorr_2', 'pred_autocorr_2', 'crosscorr')
+LV_MAX_EVENTS = 1 << 30                                   # include/elfihip.h: ELFIHIP_LV_MAX_EVENTS
+LV_STATUS = ('reached_end', 'extinct', 'out_of_events', 'invalid')     # ELFIHIP_LV_REACHED_END ...
+
+
+def _lv_index_range(first_index, n):
+    if not 0 <= int(first_index) <= 2 ** 32 - n:
+        raise ValueError('simulation indices first_index .. first_index + batch - 1 must lie in [0, 2^32)')
+    return int(first_index)
+
+
+def lotka_volterra_draws(n, n_events, seed=0, stream=0, first_index=0, ctx=None):
+    """(E, U), each (n, n_events): the unit exponentials and uniforms the drawn form of lotka_volterra_summaries uses for
+    events 1 .. n_events of simulations first_index .. first_index + n - 1 -- Philox counter (i << 32) | k of (seed,
+    stream).  Handing them back as draws=(E, U) reproduces the drawn form bit for bit."""
+    n, n_events = int(n), int(n_events)
+    if n < 1 or not 1 <= n_events <= LV_MAX_EVENTS:
+        raise ValueError('need n >= 1 and 1 <= n_events <= 2^30')
+    first_index = _lv_index_range(first_index, n)
+    E, U = np.empty((n, n_events)), np.empty((n, n_events))
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_lv_draws", C.c_uint64(int(seed)), C.c_uint64(int(stream)), first_index, n, n_events, _lib.ptr(E),
+             _lib.ptr(U))
+    return E, U
+
+
+def lotka_volterra_summaries(r1, r2, r3, prey_init=50, predator_init=100, sigma=None, n_obs=16, time_end=30.,
+                             max_events=1 << 20, draws=None, noise=None, seed=0, stream=0, observed=None,
+                             return_series=False, return_status=False, first_index=0, ctx=None):
+    """The stochastic Lotka-Volterra example (elfi/examples/lotka_volterra.py) as ONE device operation: Gillespie's direct
+    method for prey and predators with hazards r1 x, r2 x y, r3 y from floor(prey_init), floor(predator_init) up to
+    time_end, the n_obs observations at np.linspace(0, time_end, n_obs) (linear interpolation between the bracketing
+    events, plus sigma z when sigma is given, truncated as the reference's int32 array does) and the nine summaries
+    LV_NAMES.  include/elfihip.h (elfihip_lv_summaries) states every operation.
+
+    r1, r2, r3, prey_init, predator_init, sigma: (batch,) or scalars.  draws: (E, U), each (batch, n_events) -- unit
+    exponentials and uniforms in [0, 1), column k - 1 for event k; they bound the events (max_events is then n_events).
+    draws=None draws on the device: event k of simulation i reads Philox counter ((first_index + i) << 32) | k of (seed,
+    stream), so a simulation does not depend on the batch it runs in.  noise: (batch, 2 (n_obs - 1)) standard normals, prey
+    before predator for each observation (needs sigma); noise=None with sigma draws them from (seed, stream + 1).
+    A simulation that has not reached time_end after max_events events is cut off: its remaining observations, its
+    summaries and its distance are NaN (status 2; the reference has no bound and runs on).  Invalid parameters (a rate or
+    sigma NaN, negative or infinite; an initial stock NaN, negative or >= 2^31) give a NaN row (status 3).
+    observed: the 9 observed summaries; with them the euclidean distance is returned too.
+    Returns S (batch, 9) [, series (batch, n_obs, 2)] [, status (batch,) int32, events (batch,) int64, final times
+    (batch,)] [, d (batch,)] -- the bare array when nothing else is asked for."""
+    n_obs, max_events = int(n_obs), int(max_events)
+    if not 3 <= n_obs <= SERIES_MAX_OBS:
+        raise ValueError('n_obs must be in [3, %d]' % SERIES_MAX_OBS)
+    time_end = float(time_end)
+    if not (np.isfinite(time_end) and time_end > 0):
+        raise ValueError('time_end must be finite and positive')
+    E = U = None
+    if draws is not None:
+        E, U = (np.asarray(a) for a in draws)
+        if E.ndim != 2 or E.shape != U.shape or E.shape[1] < 1:
+            raise ValueError('draws must be (E, U), each (batch, n_events)')
+        max_events = E.shape[1]
+    if not 1 <= max_events <= LV_MAX_EVENTS:
+        raise ValueError('max_events must be in [1, 2^30]')
+    if noise is not None:
+        if sigma is None:
+            raise ValueError('noise needs sigma')
+        noise = np.asarray(noise)
+        if noise.ndim != 2 or noise.shape[1] != 2 * (n_obs - 1):
+            raise ValueError('noise must be (batch, 2 (n_obs - 1)) = (batch, %d)' % (2 * (n_obs - 1)))
+    params = (r1, r2, r3, prey_init, predator_init) + (() if sigma is None else (sigma,))
+    n = E.shape[0] if E is not None else noise.shape[0] if noise is not None else _batch_of(*params)
+    if n < 1:
+        raise ValueError('need at least one simulation')
+    if noise is not None and noise.shape[0] != n:
+        raise ValueError('noise must hold one row per simulation (%d)' % n)
+    first_index = _lv_index_range(first_index, n)
+    params = _params(n, *params)
+    obs = None
+    if observed is not None:
+        obs = np.ascontiguousarray(np.asarray(observed, dtype=np.float64).reshape(-1))
+        if obs.shape[0] != len(LV_NAMES):
+            raise ValueError('observed must hold the %d observed summaries' % len(LV_NAMES))
+    if E is not None:
+        E, U = np.ascontiguousarray(E, dtype=np.float64), np.ascontiguousarray(U, dtype=np.float64)
+    if noise is not None:
+        noise = np.ascontiguousarray(noise, dtype=np.float64)
+    S = np.empty((n, len(LV_NAMES)))
+    Y = np.empty((n, n_obs, 2)) if return_series else None
+    status = np.empty(n, dtype=np.int32) if return_status else None
+    events = np.empty(n, dtype=np.int64) if return_status else None
+    T = np.empty(n) if return_status else None
+    D = np.empty(n) if obs is not None else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_lv_summaries", _lib.ptr(E), _lib.ptr(U), _lib.ptr(noise), C.c_uint64(int(seed)), C.c_uint64(int(stream)),
+             first_index, n, n_obs, C.c_double(time_end), max_events, *[_lib.ptr(a) for a in params],
+             *(() if sigma is not None else (None,)), _lib.ptr(obs), _lib.ptr(Y), _lib.ptr(T), _lib.ptr(status),
+             _lib.ptr(events), _lib.ptr(S), _lib.ptr(D))
+    out = tuple(a for a in (S, Y, status, events, T, D) if a is not None)
     return out if len(out) > 1 else S

@@ -643,6 +643,74 @@ int elfihip_ricker_summaries_dev(elfihip_ctx* ctx, const double* dZ, int64_t ldz
                                  double stock_init, const double* obs, int which, double* dS, int64_t lds, double* dY,
                                  int64_t ldy, double* dSt, int64_t ldst, double* dZo, int64_t ldzo, double* dD);
 
+/* The stochastic Lotka-Volterra model (elfi/examples/lotka_volterra.py; Owen, Wilkinson and Gillespie 2015): Gillespie's
+ * direct method for prey x and predators y, observed at n_obs evenly spaced times, the nine summaries and the distance
+ * (csrc/gillespie.hip; the NumPy statement is tests/lv_ref.py).  Per simulation: r1, r2, r3, prey_init, predator_init and
+ * optionally sigma (n each); host scalars n_obs, time_end, max_events.  x = floor(prey_init), y = floor(predator_init), t = 0,
+ * kept as doubles (exact; the reference's int32 stock would wrap past 2^31).  Event k = 1, 2, .. in fp64, FMA contraction off:
+ *     h0 = r1 x;  h1 = (r2 x) y;  h2 = r3 y;  s = (h0 + h1) + h2;  inv = 1.0 / s
+ *     t_new = t + inv e_k                                  e_k a unit exponential
+ *     p0 = h0 inv;  p1 = h1 inv;  c0 = p0;  c1 = p0 + p1
+ *     reaction = (u_k >= c0) + (u_k >= c1)                 0: x + 1    1: x - 1, y + 1    2: y - 1;   isinf(inv): none
+ *     apply;  if y == 0: t_new = time_end
+ * Observation times t_out are np.linspace(0, time_end, n_obs): i (time_end / (n_obs - 1)), the last one time_end itself.
+ * Observation 0 is the initial state, without noise.  Observation i >= 1 belongs to the first event j >= 1 with t_j >=
+ * t_out[i]; its value is, per species with stock s,
+ *     v = ((s_j - s_{j-1}) ((t_out[i] - t_{j-1}) / (t_j - t_{j-1})) + s_{j-1}) + sigma z
+ * (the reference's linear interpolation between events; without sigma nothing is added), stored as the reference's int32
+ * slot keeps it: truncated toward zero, -0 as +0, as a double; |v| >= 2^31 or NaN is stored as NaN (the reference's cast is
+ * undefined there).  The simulation stops at the first event with t >= time_end, the y == 0 case included.  IEEE
+ * arithmetic carries the degenerate cases as NumPy does: with both species at 0, inv = inf, no reaction, y == 0 ends the
+ * simulation and every observation is 0.
+ * Randomness.  Given form: E and U (n, n_events) unit exponentials and uniforms in [0, 1), column k - 1 feeds event k and
+ * max_events = n_events; Z (n, 2 (n_obs - 1)) standard normals with sigma, observation i's prey at column 2 (i - 1), its
+ * predator next to it (the reference's draw order).  Drawn form (E == U == NULL): event k of simulation i reads Philox
+ * counter p = ((first + i) << 32) | k of (seed, stream) (csrc/philox.hpp's layout with p in place of the pair index):
+ * e_k = -log((((w0 << 21) | (w1 >> 11)) + 1) 2^-53), u_k = ((w2 << 21) | (w3 >> 11)) 2^-53.  Z == NULL with sigma: noise normal
+ * number (first + i) 2 (n_obs - 1) + q is that normal of (seed, stream + 1), as elfihip_randn_dev writes it.  `first` shifts the
+ * simulation indices of a call (first + n <= 2^32): simulation i of one call is simulation 0 of a call with first = i.  So
+ * a simulation's result is a function of its own parameters, (seed, stream, first + i), n_obs and time_end alone: not of n,
+ * of the grid, of max_events short of reaching it, or of the lane that ran it.  elfihip_lv_draws writes the E and U of the
+ * drawn form into memory: the drawn form IS the given form on them.
+ * Limits: 3 <= n_obs <= ELFIHIP_SERIES_MAX_OBS, 1 <= max_events <= ELFIHIP_LV_MAX_EVENTS, n >= 1, time_end finite and > 0;
+ * anything else is ELFIHIP_ERR_ARG, and so are a distance without obs, E without U and Z without sigma.
+ * Marks per simulation, status (int32) and the number of events made (int64):
+ *   ELFIHIP_LV_REACHED_END    an event reached time_end
+ *   ELFIHIP_LV_EXTINCT        the predators died out (the time is set to time_end)
+ *   ELFIHIP_LV_OUT_OF_EVENTS  max_events used up before time_end: the observations not yet emitted are NaN, and so are the
+ *                             row's summaries and distance.  The reference has no such bound: it doubles its arrays and
+ *                             goes on for as long as the slowest simulation of the batch takes.
+ *   ELFIHIP_LV_INVALID        a rate or sigma NaN, negative or infinite, or a floored initial stock NaN, negative or >= 2^31:
+ *                             every output of the row is NaN, 0 events
+ * Outputs, each may be NULL: Y (n, n_obs, 2) the observations (prey, predator), T (n) the time of the last event, status,
+ * events, S (n, 9) the summaries in the reference's order -- prey / predator mean, log-variance log(var(ddof 1) + 1),
+ * autocorrelation lag 1 and lag 2 ((y - mean) / std(ddof 1), products summed and divided by n_obs - 1), the
+ * cross-correlation (std with ddof 0, divided by n_obs - 1 as the reference has it) -- with NumPy's pairwise sums,
+ * bit-identical to the reference's functions except for the device's log in the log-variances (within 4 ulp); a constant
+ * series gives 0 / 0 = NaN in its correlations as there.  D (n): euclidean distance of the row of S to obs (9 host values),
+ * bit-identical to elfihip_dist_rows 'euclidean'.
+ * Host form: contiguous host arrays, synchronises.  _dev form: device pointers, E, U, Z, Y, S with the caller's leading
+ * dimension (in doubles; Y's per simulation), no synchronisation.  obs is a host array in both. */
+#define ELFIHIP_LV_SUMMARIES 9
+#define ELFIHIP_LV_MAX_EVENTS (1LL << 30)
+#define ELFIHIP_LV_REACHED_END 0
+#define ELFIHIP_LV_EXTINCT 1
+#define ELFIHIP_LV_OUT_OF_EVENTS 2
+#define ELFIHIP_LV_INVALID 3
+int elfihip_lv_summaries(elfihip_ctx* ctx, const double* E, const double* U, const double* Z, uint64_t seed, uint64_t stream,
+                         int64_t first, int64_t n, int n_obs, double time_end, int64_t max_events, const double* r1,
+                         const double* r2, const double* r3, const double* prey, const double* pred, const double* sigma,
+                         const double* obs, double* Y, double* T, int32_t* status, int64_t* events, double* S, double* D);
+int elfihip_lv_summaries_dev(elfihip_ctx* ctx, const double* dE, int64_t lde, const double* dU, int64_t ldu, const double* dZ,
+                             int64_t ldz, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int n_obs, double time_end,
+                             int64_t max_events, const double* dr1, const double* dr2, const double* dr3, const double* dprey,
+                             const double* dpred, const double* dsigma, const double* obs, double* dY, int64_t ldy, double* dT,
+                             int32_t* dstatus, int64_t* devents, double* dS, int64_t lds, double* dD);
+int elfihip_lv_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int64_t n_events, double* E,
+                     double* U);
+int elfihip_lv_draws_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int64_t n_events,
+                         double* dE, int64_t lde, double* dU, int64_t ldu);
+
 /* The stochastic Lorenz-96 forecast model (elfi/examples/lorenz.py), fused the same way: draws, the Runge-Kutta recurrence,
  * the six summaries and the distance in one pass; series and summaries bit-identical to the reference's NumPy on the same
  * draws.  K = n_obs variables in 4 .. ELFIHIP_LORENZ_MAX_VARS, T = n_timestep >= 2 rows, T K <= ELFIHIP_LORENZ_MAX_TERMS
