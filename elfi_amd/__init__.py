@@ -30,10 +30,12 @@ from .summaries import arch_summaries, lorenz_summaries, mg1_summaries  # noqa: 
 from .summaries import bignk_summaries, gnk_summaries  # noqa: F401
 from .summaries import poisson, ricker_summaries  # noqa: F401
 from .summaries import lotka_volterra_draws, lotka_volterra_summaries  # noqa: F401
+from .summaries import daycare_distance, daycare_draws, daycare_summaries  # noqa: F401
 from .fused_models import arch_model, lorenz_model, mg1_model  # noqa: F401
 from .fused_models import bignk_model, gnk_model  # noqa: F401
 from .fused_models import ricker_model  # noqa: F401
 from .fused_models import lotka_volterra_model, lv_summary_rows  # noqa: F401
+from .fused_models import daycare_model, daycare_summary_rows  # noqa: F401
 from .lcb_acquisition import HipLCBSC  # noqa: F401
 from .posterior import HipBolfiPosterior, sample_posterior  # noqa: F401
 from .bolfi import HipBOLFI, hip_bolfi_class  # noqa: F401

@@ -9,6 +9,7 @@
     m = elfi_amd.fused_models.bignk_model(n_obs=150, seed=4)          # elfi.examples.bignk.get_model(...)
     m = elfi_amd.fused_models.ricker_model(n_obs=50, seed_obs=4)      # elfi.examples.ricker.get_model(...)
     m = elfi_amd.fused_models.lotka_volterra_model(seed_obs=4)        # elfi.examples.lotka_volterra.get_model(...)
+    m = elfi_amd.fused_models.daycare_model(seed_obs=4)               # elfi.examples.daycare.get_model(...)
     elfi_amd.HipRejection(m['d'], batch_size=10**6, seed=1).sample(1000, n_sim=10**8)
 
 The reference's Simulator node draws the series on the host (MA2: random_state.randn(batch, n_obs + 2),
@@ -64,6 +65,15 @@ the summaries are NumPy's bit for bit except the two log-variances (within 4 ulp
 (tests/test_lotka_volterra_gpu.py).  A simulation is cut off after max_events events (default 2^20) with NaN summaries, where
 the reference runs on without bound.
 
+daycare_model is the pneumococcal day-care-centre transmission example (elfi/examples/daycare.py: the model BOLFI was
+introduced on; a Markov jump process over the carriage of 33 strains by the 53 individuals of each of 29 centres) on
+csrc/daycare.hip: one wavefront per (simulation, centre) pair, taken from a counter, with the factorised hazard.  Its Simulator
+node DCC returns the (batch, 4, n_dcc) summaries of every centre, the Summary nodes Shannon, n_strains, prevalence and multi pick
+their (batch, n_dcc) slice, d is an elfi.Discrepancy over elfi_amd.daycare_distance (the example's sorted L1 distance, on the
+device) and logd its logarithm: the node BOLFI is meant to model.  Every centre stops at its own first event at or past
+time_end; the reference keeps all of a batch jumping until the slowest has passed it, so it is reproduced exactly -- final
+states and event counts on given draws -- per centre (tests/test_daycare.py, tests/test_daycare_gpu.py).
+
 The draws are the device generator's, not MT19937's: a run of this model is a different (equally valid) random
 realisation than a run of elfi.examples.*.get_model with the same seed; the arithmetic on given draws is bit-identical
 to the reference's (tests/test_summaries_gpu.py, tests/test_gauss_gpu.py).
@@ -80,6 +90,7 @@ from .summaries import LORENZ_NAMES, arch_summaries, gauss_distance, lorenz_summ
 from .summaries import GNK_SUMMARIES, bignk_summaries, gnk_summaries
 from .summaries import RICKER_NAMES, ricker_summaries
 from .summaries import LV_NAMES, lotka_volterra_summaries
+from .summaries import DAYCARE_NAMES, daycare_distance, daycare_summaries
 
 
 def _elfi():
@@ -480,6 +491,45 @@ def lotka_volterra_model(n_obs=50, true_params=None, observation_noise=False, se
     elfi.Simulator(partial(lv_summary_rows, **kwargs), *nodes, observed=obs, name='LV')
     sumstats = [elfi.Summary(partial(column, j=k), m['LV'], name=name) for k, name in enumerate(LV_NAMES)]
     elfi.Distance(HipDistance('euclidean'), *sumstats, name='d')
+    return m
+
+
+def daycare_summary_rows(t1, t2, t3, n_dcc=29, n_ind=53, n_strains=33, freq_strains_commun=None, n_obs=36, time_end=10.,
+                         max_events=1 << 16, batch_size=1, random_state=None):
+    """Simulator operation: (batch, 4, n_dcc) summaries of day-care centres simulated and reduced on the device."""
+    t1, t2, t3 = _per_simulation(batch_size, t1, t2, t3)
+    return daycare_summaries(t1, t2, t3, n_dcc=n_dcc, n_ind=n_ind, n_strains=n_strains, freq_strains_commun=freq_strains_commun,
+                             n_obs=n_obs, time_end=time_end, max_events=max_events, seed=_seed_of(random_state),
+                             stream=SIMULATOR_STREAM_BASE)
+
+
+def daycare_model(true_params=None, seed_obs=None, device_priors=True, **kwargs):
+    """elfi.examples.daycare.get_model(true_params, seed_obs, **kwargs) with the simulation on the device; nodes t1, t2, t3,
+    DCC, Shannon, n_strains, prevalence, multi, d, logd.  The node DCC returns the (batch, 4, n_dcc) summaries, the Summary
+    nodes pick their (batch, n_dcc) slice; d is an elfi.Discrepancy over elfi_amd.daycare_distance and logd = log d.  kwargs go
+    to the simulator (n_dcc, n_ind, n_strains, freq_strains_commun, n_obs, time_end, max_events).  The observed state is the
+    reference's own simulator with RandomState(seed_obs), reduced once with the reference's summary functions.
+    device_priors: the uniform priors draw on the device (elfi_amd.priors.uniform)."""
+    if true_params is None:
+        true_params = [3.6, 0.6, 0.1]
+    if len(true_params) != 3:
+        raise ValueError('true_params must be [t1, t2, t3]')
+    elfi = _elfi()
+    from elfi.examples import daycare as dc
+    from . import priors
+    ref_kwargs = {k: v for k, v in kwargs.items() if k != 'max_events'}
+    y = dc.daycare(*true_params, random_state=np.random.RandomState(seed_obs), **ref_kwargs)
+    fns = [dc.ss_shannon, dc.ss_strains, dc.ss_prevalence, dc.ss_prevalence_multi]
+    obs = np.stack([f(y) for f in fns], axis=1).astype(np.float64)            # (1, 4, n_dcc)
+    m = elfi.ElfiModel()
+    uniform = priors.uniform if device_priors else 'uniform'
+    nodes = [elfi.Prior(uniform, 0, 11, model=m, name='t1'),
+             elfi.Prior(uniform, 0, 2, model=m, name='t2'),
+             elfi.Prior(uniform, 0, 1, model=m, name='t3')]
+    elfi.Simulator(partial(daycare_summary_rows, **kwargs), *nodes, observed=obs, name='DCC')
+    sumstats = [elfi.Summary(partial(column, j=k), m['DCC'], name=name) for k, name in enumerate(DAYCARE_NAMES)]
+    elfi.Discrepancy(daycare_distance, *sumstats, name='d')
+    elfi.Operation(np.log, m['d'], name='logd')
     return m
 
 

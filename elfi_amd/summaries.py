@@ -17,6 +17,8 @@ leading dimension of 1 -- elfi/model/elfi_model.py:915-943, elfi/compiler.py:94-
     poisson(lam, ...)    Poisson variates from the library's counter-based generator (csrc/poisson.hpp)
     lotka_volterra_summaries(...)  the stochastic Lotka-Volterra example: Gillespie simulation, observations, 9 summaries
                          [+ distance]                                             elfi/examples/lotka_volterra.py
+    daycare_summaries(...)  the day-care-centre transmission example: Gillespie simulation of every centre, 4 summaries per
+                         centre [+ distance]; daycare_distance(...) its sorted L1 distance      elfi/examples/daycare.py
 
     S1 = elfi.Summary(elfi_amd.autocov, Y);  S2 = elfi.Summary(elfi_amd.autocov, Y, 2)
 
@@ -609,4 +611,131 @@ def lotka_volterra_summaries(r1, r2, r3, prey_init=50, predator_init=100, sigma=
              *(() if sigma is not None else (None,)), _lib.ptr(obs), _lib.ptr(Y), _lib.ptr(T), _lib.ptr(status),
              _lib.ptr(events), _lib.ptr(S), _lib.ptr(D))
     out = tuple(a for a in (S, Y, status, events, T, D) if a is not None)
+    return out if len(out) > 1 else S
+
+
+# ---- the day-care-centre transmission example model (csrc/daycare.hip) ------------------------------------------------
+DAYCARE_NAMES = ('Shannon', 'n_strains', 'prevalence', 'multi')
+DAYCARE_MAX_EVENTS = 1 << 21                              # include/elfihip.h: ELFIHIP_DAYCARE_MAX_EVENTS
+DAYCARE_MAX_DCC = 1024                                    # ELFIHIP_DAYCARE_MAX_DCC
+DAYCARE_STATUS = ('reached_end', 'out_of_events', 'invalid')     # ELFIHIP_DAYCARE_REACHED_END ...
+
+
+def _daycare_shape(n_dcc, n_ind=2, n_strains=1, n_obs=1):
+    n_dcc, n_ind, n_strains, n_obs = int(n_dcc), int(n_ind), int(n_strains), int(n_obs)
+    if not 1 <= n_dcc <= DAYCARE_MAX_DCC:
+        raise ValueError('n_dcc must be in [1, %d]' % DAYCARE_MAX_DCC)
+    if not 2 <= n_ind <= 64:
+        raise ValueError('n_ind must be in [2, 64]')
+    if not 1 <= n_strains <= 64:
+        raise ValueError('n_strains must be in [1, 64]')
+    if not 1 <= n_obs <= n_ind:
+        raise ValueError('n_obs must be in [1, n_ind]')
+    return n_dcc, n_ind, n_strains, n_obs
+
+
+def daycare_draws(n, n_dcc, n_events, seed=0, stream=0, first_index=0, ctx=None):
+    """(E, U), each (n, n_dcc, n_events): the unit exponentials and uniforms the drawn form of daycare_summaries uses for
+    events 1 .. n_events of the centres of simulations first_index .. first_index + n - 1 -- Philox counter words ((centre <<
+    22) | event, simulation) of (seed, stream).  Handing them back as draws=(E, U) reproduces the drawn form bit for bit."""
+    n, n_events = int(n), int(n_events)
+    n_dcc = _daycare_shape(n_dcc)[0]
+    if n < 1 or not 1 <= n_events <= DAYCARE_MAX_EVENTS:
+        raise ValueError('need n >= 1 and 1 <= n_events <= 2^21')
+    first_index = _lv_index_range(first_index, n)
+    E, U = np.empty((n, n_dcc, n_events)), np.empty((n, n_dcc, n_events))
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_daycare_draws", C.c_uint64(int(seed)), C.c_uint64(int(stream)), first_index, n, n_dcc, n_events,
+             _lib.ptr(E), _lib.ptr(U))
+    return E, U
+
+
+def _daycare_observed(observed, k, m):
+    obs = np.ascontiguousarray(np.asarray([np.asarray(o, dtype=np.float64).reshape(-1) for o in observed]
+                                          if isinstance(observed, (list, tuple)) else observed, dtype=np.float64))
+    if obs.size != k * m:
+        raise ValueError('observed must hold %d summaries of %d columns' % (k, m))
+    if not np.all(np.isfinite(obs)):
+        raise ValueError('observed summaries must be finite')
+    return obs.reshape(k, m)
+
+
+def daycare_distance(*summaries, observed, ctx=None):
+    """The day-care example's distance (elfi/examples/daycare.py: distance) on the device, usable as an elfi.Discrepancy
+    operation: k summaries of shape (batch, m) and their k observed rows (1, m); every row divided by the observed row's
+    maximum (1 where that is 0) and sorted, the L1 distance to the sorted observed row, summed over the summaries and divided
+    by k m.  One array (batch, k, m) in place of the k summaries works too.  Returns (batch,); a NaN summary gives NaN."""
+    if len(summaries) == 1 and np.ndim(summaries[0]) == 3:
+        X = np.ascontiguousarray(summaries[0], dtype=np.float64)
+    else:
+        X = np.ascontiguousarray(np.stack([np.atleast_2d(np.asarray(s, dtype=np.float64)) for s in summaries], axis=1))
+    if X.ndim != 3 or X.shape[0] < 1:
+        raise ValueError('summaries must be k arrays of shape (batch, m)')
+    n, k, m = X.shape
+    if not (1 <= k <= 16 and 1 <= m <= DAYCARE_MAX_DCC and k * m <= 4096):
+        raise ValueError('1 to 16 summaries of 1 to %d columns, at most 4096 values' % DAYCARE_MAX_DCC)
+    obs = _daycare_observed(observed, k, m)
+    D = np.empty(n)
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_daycare_distance", _lib.ptr(X), n, k, m, _lib.ptr(obs), _lib.ptr(D))
+    return D
+
+
+def daycare_summaries(t1, t2, t3, n_dcc=29, n_ind=53, n_strains=33, freq_strains_commun=None, n_obs=36, time_end=10.,
+                      max_events=1 << 16, draws=None, seed=0, stream=0, observed=None, return_state=False, return_status=False,
+                      first_index=0, ctx=None):
+    """The day-care-centre transmission example (elfi/examples/daycare.py) as ONE device operation: Gillespie's direct method
+    for the carriage of n_strains strains by the n_ind individuals of each of n_dcc centres up to time_end, and the four
+    summaries DAYCARE_NAMES over the first n_obs individuals of every centre.  include/elfihip.h (elfihip_daycare_summaries)
+    states every operation.
+
+    t1, t2, t3: (batch,) or scalars.  Every centre stops at its own first event at or past time_end, so a simulation does not
+    depend on the batch it runs in (the reference's lock-step does; it is reproduced exactly per centre).  draws: (E, U), each
+    (batch, n_dcc, n_events) -- unit exponentials and uniforms in [0, 1), column k - 1 for event k; they bound the events
+    (max_events is then n_events).  draws=None draws on the device from (seed, stream, first_index + simulation, centre,
+    event).  A centre that has not reached time_end after max_events events has NaN summaries (status 1) and its simulation a
+    NaN distance; t1, t2 or t3 NaN, negative or infinite gives NaN everywhere (status 2).
+    observed: the (4, n_dcc) observed summaries; with them the example's distance is returned too.
+    Returns S (batch, 4, n_dcc) [, state (batch, n_dcc, n_obs, n_strains) bool] [, status (batch, n_dcc) int32, events (batch,
+    n_dcc) int64, final times (batch, n_dcc)] [, d (batch,)] -- the bare array when nothing else is asked for."""
+    n_dcc, n_ind, n_strains, n_obs = _daycare_shape(n_dcc, n_ind, n_strains, n_obs)
+    max_events = int(max_events)
+    time_end = float(time_end)
+    if not (np.isfinite(time_end) and time_end > 0):
+        raise ValueError('time_end must be finite and positive')
+    freq = None
+    if freq_strains_commun is not None:
+        freq = np.ascontiguousarray(np.asarray(freq_strains_commun, dtype=np.float64).reshape(-1))
+        if freq.shape[0] != n_strains or not np.all(np.isfinite(freq) & (freq >= 0)):
+            raise ValueError('freq_strains_commun must hold n_strains finite values that are not negative')
+    E = U = None
+    if draws is not None:
+        E, U = (np.asarray(a) for a in draws)
+        if E.ndim != 3 or E.shape != U.shape or E.shape[1] != n_dcc or E.shape[2] < 1:
+            raise ValueError('draws must be (E, U), each (batch, n_dcc, n_events)')
+        max_events = E.shape[2]
+    if not 1 <= max_events <= DAYCARE_MAX_EVENTS:
+        raise ValueError('max_events must be in [1, 2^21]')
+    n = E.shape[0] if E is not None else _batch_of(t1, t2, t3)
+    if n < 1:
+        raise ValueError('need at least one simulation')
+    first_index = _lv_index_range(first_index, n)
+    params = _params(n, t1, t2, t3)
+    obs = _daycare_observed(observed, len(DAYCARE_NAMES), n_dcc) if observed is not None else None
+    if E is not None:
+        E, U = np.ascontiguousarray(E, dtype=np.float64), np.ascontiguousarray(U, dtype=np.float64)
+    S = np.empty((n, len(DAYCARE_NAMES), n_dcc))
+    M = np.empty((n, n_dcc, n_obs), dtype=np.uint64) if return_state else None
+    status = np.empty((n, n_dcc), dtype=np.int32) if return_status else None
+    events = np.empty((n, n_dcc), dtype=np.int64) if return_status else None
+    T = np.empty((n, n_dcc)) if return_status else None
+    D = np.empty(n) if obs is not None else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_daycare_summaries", _lib.ptr(E), _lib.ptr(U), C.c_uint64(int(seed)), C.c_uint64(int(stream)), first_index,
+             n, n_dcc, n_ind, n_strains, n_obs, C.c_double(time_end), max_events, *[_lib.ptr(a) for a in params], _lib.ptr(freq),
+             _lib.ptr(obs), _lib.ptr(M), _lib.ptr(T), _lib.ptr(status), _lib.ptr(events), _lib.ptr(S), _lib.ptr(D))
+    state = None
+    if M is not None:
+        state = ((M[..., None] >> np.arange(n_strains, dtype=np.uint64)) & np.uint64(1)).astype(bool)
+    out = tuple(a for a in (S, state, status, events, T, D) if a is not None)
     return out if len(out) > 1 else S

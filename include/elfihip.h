@@ -711,6 +711,81 @@ int elfihip_lv_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t f
 int elfihip_lv_draws_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int64_t n_events,
                          double* dE, int64_t lde, double* dU, int64_t ldu);
 
+/* The day-care-centre transmission model (elfi/examples/daycare.py; Numminen, Cheng, Gyllenberg and Corander 2013; the model
+ * BOLFI was introduced on, Gutmann and Corander 2016): Gillespie's direct method for the carriage I_is of n_strains strains by the
+ * n_ind individuals of each of n_dcc centres, the four summaries over the first n_obs individuals of every centre and the
+ * example's distance (csrc/daycare.hip; the NumPy statement is tests/daycare_ref.py).  Per simulation: t1, t2, t3 (n each);
+ * host scalars n_dcc, n_ind, n_strains, n_obs, time_end, max_events and freq (n_strains host values, NULL: 0.1 each).  Every
+ * (simulation, centre) pair is simulated on its own from I = 0, t = 0.  Event k = 1, 2, .. in fp64, FMA contraction off, every
+ * sum from 0 in ascending index order:
+ *     k_i = sum_s I_is;  P_s = sum_i (I_is ? 1.0 / k_i : 0);  g_s = ((t1 P_s) nf + 1e-9) + t2 freq_s;  nf = 1.0 / (n_ind - 1)
+ *     c_i = k_i > 0 ? t3 : 1;  hazard h_is = I_is ? 1 : c_i g_s  (recovery at rate 1, infection scaled by t3 for carriers)
+ *     r_i = sum_s h_is;  cum_i = r_0 + .. + r_i;  total = cum_{n_ind - 1}
+ *     t = t + e_k / total                                   e_k a unit exponential
+ *     target = u_k total;  i* = #{i < n_ind - 1: target >= cum_i};  rem = target - (i* > 0 ? cum_{i* - 1} : 0)
+ *     s* = #{s < n_strains - 1: rem >= h_{i* 0} + .. + h_{i* s}};  I_{i* s*} flips
+ * -- the reference's choice among its row-major (individual-major) hazards, which it sums pairwise and compares as
+ * probabilities: the same event unless u_k lies within rounding of a boundary.  A pair stops at ITS first event with t >=
+ * time_end and the state after that event is its result: what the reference returns for batch_size = 1, n_dcc = 1.  (With
+ * more it keeps every centre of every simulation of the batch jumping until the slowest has passed time_end, so that a result
+ * depends on what else is in the batch; that is not reproduced.)
+ * Randomness.  Given form: E and U (n, n_dcc, n_events) unit exponentials and uniforms in [0, 1), column k - 1 feeds event k
+ * and max_events = n_events.  Drawn form (E == U == NULL): event k of centre c of simulation i reads the Philox counter words
+ * ((c << 22) | k, first + i, stream low, stream high) under key seed: e_k = -log((((w0 << 21) | (w1 >> 11)) + 1) 2^-53), u_k =
+ * ((w2 << 21) | (w3 >> 11)) 2^-53.  `first` shifts the simulation indices of a call (first + n <= 2^32).  So a pair's result is a
+ * function of its simulation's parameters, (seed, stream, first + i, c) and the shape alone: not of n, of the grid, of
+ * max_events short of reaching it, or of the wavefront that ran it.  elfihip_daycare_draws writes the E and U of the drawn form
+ * into memory: the drawn form IS the given form on them.
+ * Limits: 2 <= n_ind <= ELFIHIP_DAYCARE_MAX_IND, 1 <= n_strains <= ELFIHIP_DAYCARE_MAX_STRAINS, 1 <= n_obs <= n_ind, 1 <= n_dcc
+ * <= ELFIHIP_DAYCARE_MAX_DCC, 1 <= n <= ELFIHIP_DAYCARE_MAX_BATCH, time_end finite and > 0, freq finite and >= 0, 1 <=
+ * max_events <= ELFIHIP_DAYCARE_MAX_EVENTS; anything else is ELFIHIP_ERR_ARG, and so are a distance without obs and E without U.
+ * Marks per pair, status (int32), the number of events made (int64) and the time of the last one:
+ *   ELFIHIP_DAYCARE_REACHED_END    an event reached time_end
+ *   ELFIHIP_DAYCARE_OUT_OF_EVENTS  max_events used up before time_end: the centre's summaries and the simulation's distance
+ *                                  are NaN; the masks are the state reached
+ *   ELFIHIP_DAYCARE_INVALID        t1, t2 or t3 NaN, negative or infinite: every centre of the simulation has this mark, 0
+ *                                  events, time NaN, empty masks, NaN summaries and distance
+ * Outputs, each may be NULL: M (n, n_dcc, n_obs) the observed state, bit s of a word = that individual carries strain s; T,
+ * status, events (n, n_dcc); S (n, 4, n_dcc) the summaries of every centre in the reference's order --
+ *   Shannon index  p_s = (observed carriers of s) / (observed carriages), 0 / 0 -> 0 and then 0 -> 1; -(sum_s p_s log p_s) in
+ *                  NumPy's pairwise order: the reference's bit for bit except for the device's log (within 4 ulp)
+ *   the number of strains observed;  (individuals carrying anything) / n_obs;  (individuals carrying two or more) / n_obs
+ * D (n): the example's distance of S to obs (4, n_dcc host values), as elfihip_daycare_distance gives it.
+ * elfihip_daycare_distance: X (n, k, m), obs (k, m) finite host values.  o_j = max_c obs_jc, 1 where that is 0; x = X / o_j and y =
+ * obs / o_j, each row sorted over c (NaN last, as np.sort); D_i = (sum_j (sum_c |x_ijc - y_jc|)) / (k m), the inner sums left to
+ * right and then the outer one: the reference's sum up to its order.  A NaN in X makes D_i NaN.  1 <= k <=
+ * ELFIHIP_DAYCARE_DIST_MAX_SUMMARIES, 1 <= m <= ELFIHIP_DAYCARE_MAX_DCC, k m <= ELFIHIP_DAYCARE_DIST_MAX_TERMS.
+ * Host forms: contiguous host arrays, synchronise.  _dev forms: device pointers and the caller's leading dimensions -- E and U
+ * per (simulation, centre) row in doubles, M per (simulation, centre) row in words, S and X per simulation in doubles -- no
+ * synchronisation.  freq and obs are host arrays in both. */
+#define ELFIHIP_DAYCARE_SUMMARIES 4
+#define ELFIHIP_DAYCARE_MAX_IND 64
+#define ELFIHIP_DAYCARE_MAX_STRAINS 64
+#define ELFIHIP_DAYCARE_MAX_DCC 1024
+#define ELFIHIP_DAYCARE_MAX_BATCH 2147483647LL
+#define ELFIHIP_DAYCARE_MAX_EVENTS (1LL << 21)
+#define ELFIHIP_DAYCARE_DIST_MAX_SUMMARIES 16
+#define ELFIHIP_DAYCARE_DIST_MAX_TERMS 4096
+#define ELFIHIP_DAYCARE_REACHED_END 0
+#define ELFIHIP_DAYCARE_OUT_OF_EVENTS 1
+#define ELFIHIP_DAYCARE_INVALID 2
+int elfihip_daycare_summaries(elfihip_ctx* ctx, const double* E, const double* U, uint64_t seed, uint64_t stream, int64_t first,
+                              int64_t n, int n_dcc, int n_ind, int n_strains, int n_obs, double time_end, int64_t max_events,
+                              const double* t1, const double* t2, const double* t3, const double* freq, const double* obs,
+                              uint64_t* M, double* T, int32_t* status, int64_t* events, double* S, double* D);
+int elfihip_daycare_summaries_dev(elfihip_ctx* ctx, const double* dE, int64_t lde, const double* dU, int64_t ldu, uint64_t seed,
+                                  uint64_t stream, int64_t first, int64_t n, int n_dcc, int n_ind, int n_strains, int n_obs,
+                                  double time_end, int64_t max_events, const double* dt1, const double* dt2, const double* dt3,
+                                  const double* freq, const double* obs, uint64_t* dM, int64_t ldm, double* dT, int32_t* dstatus,
+                                  int64_t* devents, double* dS, int64_t lds, double* dD);
+int elfihip_daycare_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int n_dcc, int64_t n_events,
+                          double* E, double* U);
+int elfihip_daycare_draws_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int n_dcc,
+                              int64_t n_events, double* dE, int64_t lde, double* dU, int64_t ldu);
+int elfihip_daycare_distance(elfihip_ctx* ctx, const double* X, int64_t n, int k, int m, const double* obs, double* D);
+int elfihip_daycare_distance_dev(elfihip_ctx* ctx, const double* dX, int64_t ldx, int64_t n, int k, int m, const double* obs,
+                                 double* dD);
+
 /* The stochastic Lorenz-96 forecast model (elfi/examples/lorenz.py), fused the same way: draws, the Runge-Kutta recurrence,
  * the six summaries and the distance in one pass; series and summaries bit-identical to the reference's NumPy on the same
  * draws.  K = n_obs variables in 4 .. ELFIHIP_LORENZ_MAX_VARS, T = n_timestep >= 2 rows, T K <= ELFIHIP_LORENZ_MAX_TERMS
