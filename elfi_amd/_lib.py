@@ -261,6 +261,16 @@ PROTOTYPES = {
                                         C.c_void_p]),
     "elfihip_daycare_draws_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int64,
                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "elfihip_stable": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64] + [C.c_void_p] * 5),
+    "elfihip_stable_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64] + [C.c_void_p] * 5),
+    "elfihip_toad_summaries": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                                              C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double] +
+                               [C.c_void_p] * 10),
+    "elfihip_toad_summaries_dev": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64,
+                                                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                                  C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                  C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "elfihip_daycare_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "elfihip_daycare_distance_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                                C.c_void_p]),

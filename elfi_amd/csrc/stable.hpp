@@ -1,0 +1,62 @@
+// Symmetric (beta = 0) alpha-stable variates on the device, S1 parameterisation: the Chambers-Mallows-Stuck transform as
+// SciPy 1.15's levy_stable.rvs evaluates it (scipy/stats/_levy_stable: _rvs_Z1), in SciPy's order of operations, FMA
+// contraction off -- so the device differs from NumPy only through tan, sin, cos and pow (and log, in the exponential
+// variate).  tests/toad_ref.py states the same rule in NumPy beside a first-order error bound.
+//
+//   stable_transform(alpha, scale, TH, W), TH in (-pi/2, pi/2) an angle, W > 0 a standard exponential:
+//     alpha NaN or outside (0, 2], scale NaN or negative      NaN for that element
+//     alpha == 1      ((2 / pi) ((pi / 2) tan TH)) scale      SciPy's alpha1func at beta = 0, its constants as doubles
+//     otherwise       aTH = alpha TH
+//                     Z = (W / (cos TH / tan aTH + sin TH)) ((cos aTH + sin aTH tan TH) / W) ^ (1 / alpha)
+//                     the variate is Z scale
+//   stable_draw(alpha, scale, seed, stream, e) reads Philox counter e of stream (seed, stream):
+//     TH = u1 pi + (-pi / 2), u1 = ((r0 << 21) | (r1 >> 11)) 2^-53 in [0, 1)            (SciPy: uniform.rvs(loc, scale))
+//     W  = -log(u2),          u2 = (((r2 << 21) | (r3 >> 11)) + 1) 2^-53 in (0, 1]
+//   so element e is the same number wherever it is drawn: by elfihip_stable_dev into memory or inside toad.hip.
+// beta != 0 and the S0 parameterisation are not here (the stochastic-volatility example needs them).
+#pragma once
+
+#include <cmath>
+
+#include "philox.hpp"
+
+namespace elfihip {
+
+#define ELFIHIP_PI 3.141592653589793        // np.pi
+#define ELFIHIP_HALF_PI 1.5707963267948966  // np.pi / 2
+#define ELFIHIP_TWO_BY_PI 0.6366197723675814  // 2 / np.pi
+
+__device__ __forceinline__ bool stable_valid(double alpha, double scale) { return alpha > 0.0 && alpha <= 2.0 && scale >= 0.0; }
+
+__device__ __forceinline__ double stable_transform(double alpha, double scale, double TH, double W) {
+#pragma clang fp contract(off)
+  if (!stable_valid(alpha, scale)) return __builtin_nan("");
+  const double tanTH = tan(TH);
+  if (alpha == 1.0) return (ELFIHIP_TWO_BY_PI * (ELFIHIP_HALF_PI * tanTH)) * scale;
+  const double aTH = alpha * TH;
+  const double cosTH = cos(TH);
+  const double den = cosTH / tan(aTH) + sin(TH);
+  const double num = cos(aTH) + sin(aTH) * tanTH;
+  const double Z = (W / den) * pow(num / W, 1.0 / alpha);
+  return Z * scale;
+}
+
+// the angle and the exponential of Philox counter e of stream (seed, stream)
+__device__ __forceinline__ void stable_angle_expo(uint64_t seed, uint64_t stream, uint64_t e, double& TH, double& W) {
+#pragma clang fp contract(off)
+  uint32_t r[4];
+  philox4x32_10((uint32_t)e, (uint32_t)(e >> 32), (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed,
+                (uint32_t)(seed >> 32), r);
+  const uint64_t a = ((uint64_t)r[0] << 21) | (r[1] >> 11), b = ((uint64_t)r[2] << 21) | (r[3] >> 11);
+  const double u1 = (double)a * 0x1.0p-53, u2 = (double)(b + 1) * 0x1.0p-53;
+  TH = u1 * ELFIHIP_PI + (-ELFIHIP_HALF_PI);
+  W = -log(u2);
+}
+
+__device__ __forceinline__ double stable_draw(double alpha, double scale, uint64_t seed, uint64_t stream, uint64_t e) {
+  double TH, W;
+  stable_angle_expo(seed, stream, e, TH, W);
+  return stable_transform(alpha, scale, TH, W);
+}
+
+}  // namespace elfihip

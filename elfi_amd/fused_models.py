@@ -10,6 +10,7 @@
     m = elfi_amd.fused_models.ricker_model(n_obs=50, seed_obs=4)      # elfi.examples.ricker.get_model(...)
     m = elfi_amd.fused_models.lotka_volterra_model(seed_obs=4)        # elfi.examples.lotka_volterra.get_model(...)
     m = elfi_amd.fused_models.daycare_model(seed_obs=4)               # elfi.examples.daycare.get_model(...)
+    m = elfi_amd.fused_models.toad_model(seed_obs=4)                  # elfi.examples.toad.get_model(...)
     elfi_amd.HipRejection(m['d'], batch_size=10**6, seed=1).sample(1000, n_sim=10**8)
 
 The reference's Simulator node draws the series on the host (MA2: random_state.randn(batch, n_obs + 2),
@@ -74,6 +75,14 @@ device) and logd its logarithm: the node BOLFI is meant to model.  Every centre 
 time_end; the reference keeps all of a batch jumping until the slowest has passed it, so it is reproduced exactly -- final
 states and event counts on given draws -- per centre (tests/test_daycare.py, tests/test_daycare_gpu.py).
 
+toad_model is Marchand's toad movement example (elfi/examples/toad.py: 66 toads over 63 days, alpha-stable foraging steps
+and returns to earlier refuges; An, Nott and Drovandi's 48 summaries, the standard BSL test problem) on csrc/toad.hip: one
+workgroup per simulation keeps the positions in LDS, every lane makes steps (the library's stable-law sampler,
+csrc/stable.hpp), a lane per toad walks its chain, and per lag the workgroup sorts the displacements of the toads that did not
+return (csrc/wg_sort.hpp).  Its Simulator node toad returns the (batch, 48) summaries, the Summary nodes S1, S2, S4, S8 slice
+their 12 columns -- what HipBSL / syn_loglik take.  On given steps the positions are NumPy's bit for bit, on the positions the
+counts and medians are, the log quantile differences within 4 ulp (tests/test_toad.py, tests/test_toad_gpu.py).
+
 The draws are the device generator's, not MT19937's: a run of this model is a different (equally valid) random
 realisation than a run of elfi.examples.*.get_model with the same seed; the arithmetic on given draws is bit-identical
 to the reference's (tests/test_summaries_gpu.py, tests/test_gauss_gpu.py).
@@ -91,6 +100,7 @@ from .summaries import GNK_SUMMARIES, bignk_summaries, gnk_summaries
 from .summaries import RICKER_NAMES, ricker_summaries
 from .summaries import LV_NAMES, lotka_volterra_summaries
 from .summaries import DAYCARE_NAMES, daycare_distance, daycare_summaries
+from .summaries import TOAD_LAGS, toad_summaries
 
 
 def _elfi():
@@ -530,6 +540,43 @@ def daycare_model(true_params=None, seed_obs=None, device_priors=True, **kwargs)
     sumstats = [elfi.Summary(partial(column, j=k), m['DCC'], name=name) for k, name in enumerate(DAYCARE_NAMES)]
     elfi.Discrepancy(daycare_distance, *sumstats, name='d')
     elfi.Operation(np.log, m['d'], name='logd')
+    return m
+
+
+def toad_summary_rows(alpha, gamma, p0, n_toads=66, n_days=63, batch_size=1, random_state=None):
+    """Simulator operation: (batch, 48) summaries S1 | S2 | S4 | S8 of toad movements drawn, walked, sorted and reduced on the
+    device."""
+    alpha, gamma, p0 = _per_simulation(batch_size, alpha, gamma, p0)
+    return toad_summaries(alpha, gamma, p0, n_toads=n_toads, n_days=n_days, seed=_seed_of(random_state),
+                          stream=SIMULATOR_STREAM_BASE)
+
+
+def toad_model(true_params=None, seed_obs=None, device_priors=True):
+    """elfi.examples.toad.get_model(true_params, seed_obs) with the simulation on the device; nodes alpha, gamma, p0, toad,
+    S1, S2, S4, S8, d.  The node toad returns the (batch, 48) summaries of the four lags, the Summary nodes slice their 12
+    columns; d is elfi.Distance over HipDistance('euclidean') (as in the reference the example is written for BSL: a
+    summary may be inf, and d is not what it is tested on).  The observed positions are the reference's own simulator with
+    RandomState(seed_obs), reduced once with the reference's compute_summaries.  device_priors: the three uniform priors draw
+    on the device (elfi_amd.priors.uniform)."""
+    if true_params is None:
+        true_params = [1.7, 35.0, 0.6]
+    if len(true_params) != 3:
+        raise ValueError('true_params must be [alpha, gamma, p0]')
+    elfi = _elfi()
+    from elfi.examples import toad
+    from . import priors
+    y = toad.toad(*true_params, random_state=np.random.RandomState(seed_obs))
+    obs = np.hstack([toad.compute_summaries(y, lag) for lag in TOAD_LAGS]).astype(np.float64)     # (1, 48)
+    width = obs.shape[1] // len(TOAD_LAGS)
+    m = elfi.ElfiModel()
+    uniform = priors.uniform if device_priors else 'uniform'
+    nodes = [elfi.Prior(uniform, 1, 1, model=m, name='alpha'),
+             elfi.Prior(uniform, 0, 100, model=m, name='gamma'),
+             elfi.Prior(uniform, 0, 0.9, model=m, name='p0')]
+    elfi.Simulator(toad_summary_rows, *nodes, observed=obs, name='toad')
+    sumstats = [elfi.Summary(partial(columns, start=k * width, stop=(k + 1) * width), m['toad'], name='S%d' % lag)
+                for k, lag in enumerate(TOAD_LAGS)]
+    elfi.Distance(HipDistance('euclidean'), *sumstats, name='d')
     return m
 
 

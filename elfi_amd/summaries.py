@@ -15,6 +15,9 @@ leading dimension of 1 -- elfi/model/elfi_model.py:915-943, elfi/compiler.py:94-
                          statistics [+ distance]                                      elfi/examples/gnk.py, bignk.py
     ricker_summaries(...)  the fused Ricker example: stock, Poisson counts, Mean / Var / #0 [+ distance]  elfi/examples/ricker.py
     poisson(lam, ...)    Poisson variates from the library's counter-based generator (csrc/poisson.hpp)
+    toad_summaries(...)  the fused toad movement example: alpha-stable steps, refuge chain, a workgroup sort per lag,
+                         48 summaries                                                  elfi/examples/toad.py
+    levy_stable(alpha, ...)  symmetric alpha-stable variates from the library's counter-based generator (csrc/stable.hpp)
     lotka_volterra_summaries(...)  the stochastic Lotka-Volterra example: Gillespie simulation, observations, 9 summaries
                          [+ distance]                                             elfi/examples/lotka_volterra.py
     daycare_summaries(...)  the day-care-centre transmission example: Gillespie simulation of every centre, 4 summaries per
@@ -738,4 +741,109 @@ def daycare_summaries(t1, t2, t3, n_dcc=29, n_ind=53, n_strains=33, freq_strains
     if M is not None:
         state = ((M[..., None] >> np.arange(n_strains, dtype=np.uint64)) & np.uint64(1)).astype(bool)
     out = tuple(a for a in (S, state, status, events, T, D) if a is not None)
+    return out if len(out) > 1 else S
+
+
+# ---- alpha-stable variates and Marchand's toad example model (csrc/stable.hpp, csrc/toad.hip) -----------------------
+TOAD_MAX_CELLS = 8192                                     # include/elfihip.h: ELFIHIP_TOAD_MAX_CELLS
+TOAD_MAX_LAGS = 8                                         # ELFIHIP_TOAD_MAX_LAGS
+TOAD_MAX_QUANTILES = 64                                   # ELFIHIP_TOAD_MAX_QUANTILES
+TOAD_LAGS = (1, 2, 4, 8)
+
+
+def levy_stable(alpha, scale=1., seed=0, stream=0, angle=None, expo=None, ctx=None):
+    """Symmetric (beta = 0) alpha-stable variates in the shape of `alpha`, S1 parameterisation, as float64: SciPy's
+    levy_stable.rvs(alpha, beta=0, scale=scale) -- the Chambers-Mallows-Stuck transform of an angle TH and a standard
+    exponential W in SciPy's order of operations (csrc/stable.hpp; include/elfihip.h states it).  Element e of the flattened
+    array is a fixed function of alpha[e], scale[e] and Philox counter e of stream (seed, stream), so it does not depend on the
+    batch, and a fused kernel that draws element e itself (the toad kernel does) gets the same number.  With `angle` and
+    `expo` (both, in the shape of alpha) the transform is applied to those TH and W and nothing is drawn.  alpha == 1 is the
+    Cauchy branch tan TH.  alpha outside (0, 2], NaN alpha or a negative or NaN scale gives NaN for that element."""
+    alpha = np.asarray(alpha, dtype=np.float64)
+    if (angle is None) != (expo is None):
+        raise ValueError('angle and expo are given together or not at all')
+    flat = np.ascontiguousarray(alpha.reshape(-1))
+    n = flat.shape[0]
+    scale = np.asarray(scale, dtype=np.float64)
+    if scale.size not in (1, n):
+        raise ValueError('scale must be a scalar or have the shape of alpha')
+    scale = np.ascontiguousarray(np.broadcast_to(scale.reshape(-1), (n,)))
+    TH = W = None
+    if angle is not None:
+        TH, W = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)) for a in (angle, expo)]
+        if TH.shape[0] != n or W.shape[0] != n:
+            raise ValueError('angle and expo must have the shape of alpha')
+    out = np.empty(n)
+    if n == 0:
+        return out.reshape(alpha.shape)
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_stable", C.c_uint64(int(seed)), C.c_uint64(int(stream)), n, _lib.ptr(flat), _lib.ptr(scale), _lib.ptr(TH),
+             _lib.ptr(W), _lib.ptr(out))
+    return out.reshape(alpha.shape)
+
+
+def _toad_shape(n_toads, n_days, lags, p, thd):
+    n_toads, n_days = int(n_toads), int(n_days)
+    if n_days < 2 or n_toads < 1 or n_days * n_toads > TOAD_MAX_CELLS:
+        raise ValueError('need n_days >= 2, n_toads >= 1 and n_days * n_toads <= %d' % TOAD_MAX_CELLS)
+    lags = np.ascontiguousarray(np.asarray(lags).reshape(-1))
+    if not 1 <= lags.shape[0] <= TOAD_MAX_LAGS:
+        raise ValueError('1 to %d lags' % TOAD_MAX_LAGS)
+    if lags.dtype.kind not in 'iu' or not np.all((lags >= 1) & (lags <= n_days - 1)):
+        raise ValueError('every lag must be an integer in [1, n_days - 1]')
+    p = np.linspace(0, 1, 11) if p is None else np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1))
+    if not 1 <= p.shape[0] <= TOAD_MAX_QUANTILES:
+        raise ValueError('1 to %d quantiles' % TOAD_MAX_QUANTILES)
+    if not (np.all((p >= 0) & (p <= 1)) and np.all(np.diff(p) > 0)):
+        raise ValueError('quantiles must increase within [0, 1]')
+    thd = float(thd)
+    if thd != thd:
+        raise ValueError('thd is NaN')
+    return n_toads, n_days, lags.astype(np.int32), p, thd
+
+
+def toad_summaries(alpha, gamma, p0, n_toads=66, n_days=63, lags=TOAD_LAGS, p=None, thd=10., draws=None, seed=0, stream=0,
+                   first_index=0, return_series=False, return_steps=False, return_draws=False, ctx=None):
+    """Marchand's toad movement example (elfi/examples/toad.py) as ONE device operation: the positions X[0] = 0, X[i] = X[r]
+    for a toad that returns (probability p0) to the refuge of an earlier day r, X[i - 1] + dx otherwise, dx a symmetric
+    alpha-stable step of scale gamma (elfi_amd.levy_stable's transform), and compute_summaries for every lag: the number of
+    displacements |X[i + lag] - X[i]| below thd, np.nanmedian of the others and log(max(diff(np.nanquantile(others, p)),
+    exp(-20))), NaN -> inf -- len(p) + 1 columns per lag (p: default np.linspace(0, 1, 11)), lag by lag, the reference's S1, S2,
+    S4, S8 side by side.  include/elfihip.h (elfihip_toad_summaries) states every operation.
+
+    alpha, gamma, p0: (batch,) or scalars.  draws: (U, TH, W, R), each (batch, n_days - 1, n_toads) -- per day the reference's
+    uniform((n_toads, batch)), levy_stable's angle uniform * pi + (-pi / 2) and standard exponential, and choice(day, size),
+    simulation first (tests/toad_ref.py: draws_from_state); R integers in [0, day).  draws=None draws on the device, a fixed
+    function of (seed, stream, first_index + row, day, toad) that does not depend on the batch.
+    An invalid parameter row (alpha outside (0, 2], gamma < 0, p0 outside [0, 1], NaN) has NaN summaries, positions and steps.
+    Returns S (batch, (len(p) + 1) len(lags)) [, X (batch, n_days, n_toads) -- the reference's X is (n_days, n_toads, batch)]
+    [, dx (batch, n_days - 1, n_toads), the step of every cell, used or not] [, (U, TH, W, R) the draws used] -- the bare array
+    when nothing else is asked for."""
+    n_toads, n_days, lags, p, thd = _toad_shape(n_toads, n_days, lags, p, thd)
+    cells = (n_days - 1, n_toads)
+    given = [None] * 4
+    if draws is not None:
+        given = [np.asarray(a) for a in draws]
+        if len(given) != 4 or any(a.ndim != 3 or a.shape[1:] != cells or a.shape[0] != given[0].shape[0] for a in given):
+            raise ValueError('draws must be (U, TH, W, R), each (batch, n_days - 1, n_toads) = (batch, %d, %d)' % cells)
+        R = given[3]
+        if R.dtype.kind not in 'iu' and not np.array_equal(R, np.floor(R)):
+            raise ValueError('the refuge indices R must be integers')
+        if R.size and not np.all((R >= 0) & (R < np.arange(1, n_days).reshape(1, -1, 1))):
+            raise ValueError('the refuge index of day i must lie in [0, i)')
+        given = [np.ascontiguousarray(a, dtype=np.float64) for a in given[:3]] + [np.ascontiguousarray(R, dtype=np.int32)]
+    n = given[0].shape[0] if draws is not None else _batch_of(alpha, gamma, p0)
+    if n < 1:
+        raise ValueError('need at least one simulation')
+    first_index = _lv_index_range(first_index, n)
+    params = _params(n, alpha, gamma, p0)
+    S = np.empty((n, (p.shape[0] + 1) * lags.shape[0]))
+    X = np.empty((n, n_days, n_toads)) if return_series else None
+    Dx = np.empty((n,) + cells) if return_steps else None
+    echo = [np.empty((n,) + cells, dtype=t) if return_draws else None for t in (np.float64,) * 3 + (np.int32,)]
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_toad_summaries", *[_lib.ptr(a) for a in given], C.c_uint64(int(seed)), C.c_uint64(int(stream)), first_index,
+             n, n_toads, n_days, lags.shape[0], _lib.ptr(lags), p.shape[0], _lib.ptr(p), C.c_double(thd),
+             *[_lib.ptr(a) for a in params], _lib.ptr(S), _lib.ptr(X), _lib.ptr(Dx), *[_lib.ptr(a) for a in echo])
+    out = tuple(a for a in (S, X, Dx, tuple(echo) if return_draws else None) if a is not None)
     return out if len(out) > 1 else S

@@ -786,6 +786,67 @@ int elfihip_daycare_distance(elfihip_ctx* ctx, const double* X, int64_t n, int k
 int elfihip_daycare_distance_dev(elfihip_ctx* ctx, const double* dX, int64_t ldx, int64_t n, int k, int m, const double* obs,
                                  double* dD);
 
+/* Symmetric (beta = 0) alpha-stable variates, S1 parameterisation: the Chambers-Mallows-Stuck transform as SciPy 1.15's
+ * levy_stable.rvs evaluates it (_rvs_Z1), in SciPy's order of operations, FMA contraction off (csrc/stable.hpp; the NumPy
+ * statement is tests/toad_ref.py: stable_step).  From an angle TH in (-pi/2, pi/2) and a standard exponential W:
+ *   alpha NaN or outside (0, 2], scale NaN or negative: NaN for that element, the batch goes on.
+ *   alpha == 1: ((2 / pi) ((pi / 2) tan TH)) scale -- SciPy's alpha1func at beta = 0, 2 / pi and pi / 2 its doubles.
+ *   otherwise: aTH = alpha TH, Z = (W / (cos TH / tan aTH + sin TH)) ((cos aTH + sin aTH tan TH) / W) ^ (1 / alpha); Z scale.
+ * angle == expo == NULL (one without the other is ELFIHIP_ERR_ARG): element e draws its own from Philox counter e of stream
+ * (seed, stream) -- TH = u1 pi + (-pi / 2) with u1 = ((r0 << 21) | (r1 >> 11)) 2^-53 in [0, 1), W = -log(u2) with u2 =
+ * (((r2 << 21) | (r3 >> 11)) + 1) 2^-53 in (0, 1] -- so element e does not depend on n or on where it is drawn.  With angle
+ * and expo (n each) the transform is applied to them and nothing is drawn.  The device differs from NumPy on the same TH
+ * and W only through tan, sin, cos and pow.  beta != 0 and the S0 parameterisation are not provided.
+ * Host form: host pointers, synchronises; _dev form: device pointers, no synchronisation, writes out[0 .. n - 1] only. */
+int elfihip_stable(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t n, const double* alpha, const double* scale,
+                   const double* angle, const double* expo, double* out);
+int elfihip_stable_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t n, const double* dalpha, const double* dscale,
+                       const double* dangle, const double* dexpo, double* dout);
+
+/* Marchand's toad movement model (elfi/examples/toad.py) with An, Nott and Drovandi's summaries, one workgroup per
+ * simulation (csrc/toad.hip; the NumPy statement is tests/toad_ref.py).  Per simulation alpha, gamma, p0 (n each).  X[0] = 0;
+ * cell (day i = 1 .. n_days - 1, toad j), number c = (i - 1) n_toads + j, has four draws U, TH, W, R:
+ *   the toad returns iff U < p0, and then X[i][j] = X[R][j], 0 <= R < i;
+ *   otherwise X[i][j] = X[i - 1][j] + dx with dx = the stable transform above of (alpha, gamma, TH, W).
+ * Given draws: U, TH, W doubles and R int32, each (n, cells) with cells = (n_days - 1) n_toads -- what the reference draws
+ * per day as uniform((n_toads, batch)), levy_stable's uniform pi + (-pi / 2) and standard_exponential, choice(i, size),
+ * transposed; all four or none.  A given R outside [0, i) makes that toad's positions NaN from day i on.
+ * U == NULL: drawn here, a fixed function of (seed, stream, g = first_index + row, i, j), whatever the batch or the launch:
+ * with the 64-bit Philox counter e = (g << 32) | (i << 16) | j,
+ *   stream `stream`:      TH and W of element e exactly as elfihip_stable draws them;
+ *   stream `stream + 1`:  U = ((r0 << 21) | (r1 >> 11)) 2^-53 in [0, 1), R = floor(r2 i / 2^32) (multiply-high of ONE word: day r
+ *                         has probability floor or ceil of 2^32 / i over 2^32, within i 2^-32 < 2^-26 relative of 1 / i for i <
+ *                         64, below 2^-19 at the largest i; NumPy's choice rejects instead -- its bits are not reproduced).
+ * first_index + n <= 2^32.
+ * Summaries, for every lag in lags (host array, n_lags of them, each in [1, n_days - 1]) over the n_toads (n_days - lag)
+ * displacements |X[i + lag] - X[i]|: the number below thd; np.nanmedian of the others; log(max(diff(np.nanquantile(others,
+ * p)), exp(-20))) for the nq probabilities p (host array, increasing in [0, 1]) -- nq + 1 columns per lag, lag by lag, then
+ * np.nan_to_num(., nan=inf): NaN (no toad left: every column but the count) becomes +inf and an infinity the largest finite
+ * double of its sign.  NaN displacements are neither counted nor sorted, as nanquantile drops them.  On given dx the
+ * positions are NumPy's bit for bit; on the positions the counts and medians are, the log differences differ by the device's
+ * log (a difference at or below exp(-20) gives -20 exactly).
+ * An invalid parameter row -- alpha outside (0, 2], gamma < 0, p0 outside [0, 1], or NaN -- gives NaN summaries, positions and
+ * steps for that row alone.  Limits: n >= 1, n_days >= 2, n_toads >= 1, n_days n_toads <= ELFIHIP_TOAD_MAX_CELLS, 1 .. MAX_LAGS
+ * lags, 1 .. MAX_QUANTILES probabilities, thd not NaN; anything else is ELFIHIP_ERR_ARG.
+ * Outputs: S (n, (nq + 1) n_lags); optional, each may be NULL: X (n, n_days n_toads) the positions, row-major (day, toad) --
+ * the reference's X is (n_days, n_toads, batch); Dx (n, cells) the steps of every cell, used or not; Uo, THo, Wo, Ro (n, cells)
+ * the draws used, all four or none.  Host form: contiguous host arrays, synchronises.  _dev form: device pointers, the
+ * given draws at pitch ldd, S at lds, X at ldx, Dx at lddx, the draw outputs at ldo (in elements), no synchronisation;
+ * lags and p are host arrays in both. */
+#define ELFIHIP_TOAD_MAX_CELLS 8192
+#define ELFIHIP_TOAD_MAX_LAGS 8
+#define ELFIHIP_TOAD_MAX_QUANTILES 64
+int elfihip_toad_summaries(elfihip_ctx* ctx, const double* U, const double* TH, const double* W, const int32_t* R, uint64_t seed,
+                           uint64_t stream, int64_t first_index, int64_t n, int n_toads, int n_days, int n_lags, const int* lags,
+                           int nq, const double* p, double thd, const double* alpha, const double* gamma, const double* p0,
+                           double* S, double* X, double* Dx, double* Uo, double* THo, double* Wo, int32_t* Ro);
+int elfihip_toad_summaries_dev(elfihip_ctx* ctx, const double* dU, const double* dTH, const double* dW, const int32_t* dR,
+                               int64_t ldd, uint64_t seed, uint64_t stream, int64_t first_index, int64_t n, int n_toads,
+                               int n_days, int n_lags, const int* lags, int nq, const double* p, double thd,
+                               const double* dalpha, const double* dgamma, const double* dp0, double* dS, int64_t lds,
+                               double* dX, int64_t ldx, double* dDx, int64_t lddx, double* dUo, double* dTHo, double* dWo,
+                               int32_t* dRo, int64_t ldo);
+
 /* The stochastic Lorenz-96 forecast model (elfi/examples/lorenz.py), fused the same way: draws, the Runge-Kutta recurrence,
  * the six summaries and the distance in one pass; series and summaries bit-identical to the reference's NumPy on the same
  * draws.  K = n_obs variables in 4 .. ELFIHIP_LORENZ_MAX_VARS, T = n_timestep >= 2 rows, T K <= ELFIHIP_LORENZ_MAX_TERMS
