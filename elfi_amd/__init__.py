@@ -36,6 +36,8 @@ from .fused_models import bignk_model, gnk_model  # noqa: F401
 from .fused_models import ricker_model  # noqa: F401
 from .summaries import levy_stable, toad_summaries  # noqa: F401
 from .fused_models import toad_model  # noqa: F401
+from .summaries import levy_stable_general, sv_summaries  # noqa: F401
+from .fused_models import sv_model  # noqa: F401
 from .fused_models import lotka_volterra_model, lv_summary_rows  # noqa: F401
 from .fused_models import daycare_model, daycare_summary_rows  # noqa: F401
 from .lcb_acquisition import HipLCBSC  # noqa: F401

@@ -271,6 +271,13 @@ PROTOTYPES = {
                                                                   C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                                   C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "elfihip_stable_general": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int] + [C.c_void_p] * 7),
+    "elfihip_stable_general_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int] + [C.c_void_p] * 7),
+    "elfihip_sv_summaries": (C.c_int, [C.c_void_p] * 4 + [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int] +
+                             [C.c_void_p] * 16),
+    "elfihip_sv_summaries_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int] +
+                                 [C.c_void_p] * 10 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "elfihip_daycare_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "elfihip_daycare_distance_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                                C.c_void_p]),

@@ -11,6 +11,7 @@
     m = elfi_amd.fused_models.lotka_volterra_model(seed_obs=4)        # elfi.examples.lotka_volterra.get_model(...)
     m = elfi_amd.fused_models.daycare_model(seed_obs=4)               # elfi.examples.daycare.get_model(...)
     m = elfi_amd.fused_models.toad_model(seed_obs=4)                  # elfi.examples.toad.get_model(...)
+    m = elfi_amd.fused_models.sv_model(n_obs=50, seed_obs=4)          # elfi.examples.stochastic_volatility_model.get_model(...)
     elfi_amd.HipRejection(m['d'], batch_size=10**6, seed=1).sample(1000, n_sim=10**8)
 
 The reference's Simulator node draws the series on the host (MA2: random_state.randn(batch, n_obs + 2),
@@ -83,6 +84,15 @@ return (csrc/wg_sort.hpp).  Its Simulator node toad returns the (batch, 48) summ
 their 12 columns -- what HipBSL / syn_loglik take.  On given steps the positions are NumPy's bit for bit, on the positions the
 counts and medians are, the log quantile differences within 4 ulp (tests/test_toad.py, tests/test_toad_gpu.py).
 
+sv_model is the alpha-stable stochastic-volatility example (elfi/examples/stochastic_volatility_model.py: AR(1)
+log-volatilities under skewed alpha-stable shocks; the test problem of Priddle and Drovandi's semiparametric synthetic
+likelihood) on csrc/sv.hip: one workgroup per simulation (one wavefront up to 1024 observations), every lane makes the draws
+and the shock of its cells (the general stable sampler of csrc/stable.hpp, S0 parameterisation), one lane walks the chain,
+and the workgroup sorts the returns for the two quantile summaries.  Its Simulator node a_svm returns (batch, n_obs + 2): the
+returns, kurt, skew; the Summary nodes returns, kurt and skew slice its columns.  On given normals the chain is NumPy's bit
+for bit, on the returns the summaries are; each shock is within twice its first-order bound of SciPy's expression in NumPy
+(tests/test_sv.py, tests/test_sv_gpu.py).  An invalid parameter row is NaN, where SciPy raises for the whole batch.
+
 The draws are the device generator's, not MT19937's: a run of this model is a different (equally valid) random
 realisation than a run of elfi.examples.*.get_model with the same seed; the arithmetic on given draws is bit-identical
 to the reference's (tests/test_summaries_gpu.py, tests/test_gauss_gpu.py).
@@ -101,6 +111,7 @@ from .summaries import RICKER_NAMES, ricker_summaries
 from .summaries import LV_NAMES, lotka_volterra_summaries
 from .summaries import DAYCARE_NAMES, daycare_distance, daycare_summaries
 from .summaries import TOAD_LAGS, toad_summaries
+from .summaries import sv_summaries
 
 
 def _elfi():
@@ -577,6 +588,45 @@ def toad_model(true_params=None, seed_obs=None, device_priors=True):
     sumstats = [elfi.Summary(partial(columns, start=k * width, stop=(k + 1) * width), m['toad'], name='S%d' % lag)
                 for k, lag in enumerate(TOAD_LAGS)]
     elfi.Distance(HipDistance('euclidean'), *sumstats, name='d')
+    return m
+
+
+def sv_rows(alpha, beta, kappa, eta, mu, phi, sigma, n_obs=50, batch_size=1, random_state=None):
+    """Simulator operation: (batch, n_obs + 2) -- the returns of the alpha-stable stochastic-volatility model, then kurt, then
+    skew, drawn, chained, sorted and reduced on the device."""
+    params = _per_simulation(batch_size, alpha, beta, kappa, eta, mu, phi, sigma)
+    S, y = sv_summaries(*params, n_obs=n_obs, seed=_seed_of(random_state), stream=SIMULATOR_STREAM_BASE, return_series=True)
+    return np.hstack([y, S])
+
+
+def sv_model(n_obs=50, true_params=None, seed_obs=None, device_priors=True):
+    """elfi.examples.stochastic_volatility_model.get_model(n_obs, true_params, seed_obs) with the simulation on the device;
+    nodes alpha, beta, the constants kappa, eta, mu, phi, sigma, a_svm, kurt, skew, d -- and returns.  The node a_svm returns
+    (batch, n_obs + 2): the series, then kurt, then skew; the Summary nodes returns, kurt and skew slice its columns (returns
+    is what semiBSL is run on in Priddle and Drovandi's paper); d is elfi.Distance over HipDistance('euclidean') of kurt and
+    skew.  The observed series is the reference's own simulator with RandomState(seed_obs), reduced once with the
+    reference's kurt and skew.  device_priors: the two uniform priors draw on the device (elfi_amd.priors.uniform)."""
+    if true_params is None:
+        true_params = [1.2, 0.5]
+    if len(true_params) != 2:
+        raise ValueError('true_params must be [alpha, beta]')
+    n_obs = int(n_obs)
+    elfi = _elfi()
+    from elfi.examples import stochastic_volatility_model as svm
+    from . import priors
+    fixed = {'kappa': 1, 'eta': 0, 'mu': 0, 'phi': 0.95, 'sigma': 0.2}
+    y = svm.alpha_stochastic_volatility_model(*true_params, **fixed, n_obs=n_obs, random_state=np.random.RandomState(seed_obs))
+    obs = np.hstack([y, np.reshape(svm.kurt(y), (1, 1)), np.reshape(svm.skew(y), (1, 1))]).astype(np.float64)    # (1, n_obs + 2)
+    m = elfi.ElfiModel()
+    uniform = priors.uniform if device_priors else 'uniform'
+    nodes = [elfi.Prior(uniform, 0.5, 1.5, model=m, name='alpha'),
+             elfi.Prior(uniform, -1, 2, model=m, name='beta')]
+    nodes += [elfi.Constant(value, model=m, name=name) for name, value in fixed.items()]
+    elfi.Simulator(partial(sv_rows, n_obs=n_obs), *nodes, observed=obs, name='a_svm')
+    elfi.Summary(partial(columns, start=0, stop=n_obs), m['a_svm'], name='returns')
+    kurt = elfi.Summary(partial(column, j=n_obs), m['a_svm'], name='kurt')
+    skew = elfi.Summary(partial(column, j=n_obs + 1), m['a_svm'], name='skew')
+    elfi.Distance(HipDistance('euclidean'), kurt, skew, name='d')
     return m
 
 

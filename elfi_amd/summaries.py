@@ -18,6 +18,9 @@ leading dimension of 1 -- elfi/model/elfi_model.py:915-943, elfi/compiler.py:94-
     toad_summaries(...)  the fused toad movement example: alpha-stable steps, refuge chain, a workgroup sort per lag,
                          48 summaries                                                  elfi/examples/toad.py
     levy_stable(alpha, ...)  symmetric alpha-stable variates from the library's counter-based generator (csrc/stable.hpp)
+    sv_summaries(...)    the fused alpha-stable stochastic-volatility example: AR(1) log-volatilities, skewed stable shocks,
+                         returns, a workgroup sort, kurt and skew               elfi/examples/stochastic_volatility_model.py
+    levy_stable_general(alpha, beta, ...)  alpha-stable variates with skewness and location, S1 or S0 (csrc/stable.hpp)
     lotka_volterra_summaries(...)  the stochastic Lotka-Volterra example: Gillespie simulation, observations, 9 summaries
                          [+ distance]                                             elfi/examples/lotka_volterra.py
     daycare_summaries(...)  the day-care-centre transmission example: Gillespie simulation of every centre, 4 summaries per
@@ -846,4 +849,108 @@ def toad_summaries(alpha, gamma, p0, n_toads=66, n_days=63, lags=TOAD_LAGS, p=No
              n, n_toads, n_days, lags.shape[0], _lib.ptr(lags), p.shape[0], _lib.ptr(p), C.c_double(thd),
              *[_lib.ptr(a) for a in params], _lib.ptr(S), _lib.ptr(X), _lib.ptr(Dx), *[_lib.ptr(a) for a in echo])
     out = tuple(a for a in (S, X, Dx, tuple(echo) if return_draws else None) if a is not None)
+    return out if len(out) > 1 else S
+
+
+# ---- general alpha-stable variates and the stochastic-volatility example (csrc/stable.hpp, csrc/sv.hip) ---------------
+SV_MAX_OBS = 4096                                         # include/elfihip.h: ELFIHIP_SV_MAX_OBS
+SV_Q_KURT = (.05, .25, .75, .95)
+SV_Q_SKEW = (.05, .5, .95)
+
+
+def levy_stable_general(alpha, beta, loc=0., scale=1., parameterization='S1', seed=0, stream=0, angle=None, expo=None, ctx=None):
+    """Alpha-stable variates in the shape of `alpha`, as float64: SciPy 1.15's levy_stable.rvs(alpha, beta, loc, scale), per
+    element and in SciPy's order of operations -- _rvs_Z1's branch (alpha == 1; beta == 0, elfi_amd.levy_stable's expression;
+    otherwise) on an angle TH and a standard exponential W, Z scale + loc, rvs's shift at alpha == 1 and, for parameterization
+    'S0', the shift to S0 (csrc/stable.hpp: stable_general; include/elfihip.h states every operation).  beta, loc, scale:
+    scalars or in the shape of alpha.  Element e of the flattened array is a fixed function of its parameters and Philox
+    counter e of stream (seed, stream): it does not depend on the batch, and at beta = 0, loc = 0, 'S1' it is
+    elfi_amd.levy_stable's element e.  With `angle` and `expo` (both, in the shape of alpha) the transform is applied to those
+    TH and W and nothing is drawn.
+    The one difference from SciPy: alpha outside (0, 2], beta outside [-1, 1], a negative scale, or NaN in alpha, beta or scale
+    gives NaN for that element alone, where SciPy raises for the whole call.  As in SciPy, scale == 0 at alpha == 1 is 0 log 0
+    = NaN."""
+    if parameterization not in ('S0', 'S1'):
+        raise ValueError("parameterization must be 'S0' or 'S1'")
+    alpha = np.asarray(alpha, dtype=np.float64)
+    if (angle is None) != (expo is None):
+        raise ValueError('angle and expo are given together or not at all')
+    flat = np.ascontiguousarray(alpha.reshape(-1))
+    n = flat.shape[0]
+    others = []
+    for name, a in (('beta', beta), ('loc', loc), ('scale', scale)):
+        a = np.asarray(a, dtype=np.float64)
+        if a.size not in (1, n):
+            raise ValueError('%s must be a scalar or have the shape of alpha' % name)
+        others.append(np.ascontiguousarray(np.broadcast_to(a.reshape(-1), (n,))))
+    TH = W = None
+    if angle is not None:
+        TH, W = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)) for a in (angle, expo)]
+        if TH.shape[0] != n or W.shape[0] != n:
+            raise ValueError('angle and expo must have the shape of alpha')
+    out = np.empty(n)
+    if n == 0:
+        return out.reshape(alpha.shape)
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_stable_general", C.c_uint64(int(seed)), C.c_uint64(int(stream)), n, int(parameterization == 'S0'),
+             _lib.ptr(flat), *[_lib.ptr(a) for a in others], _lib.ptr(TH), _lib.ptr(W), _lib.ptr(out))
+    return out.reshape(alpha.shape)
+
+
+def _sv_quantiles(q_kurt, q_skew):
+    qk, qs = [np.asarray(q, dtype=np.float64).reshape(-1) for q in (q_kurt, q_skew)]
+    if qk.shape[0] != 4 or qs.shape[0] != 3:
+        raise ValueError('q_kurt holds four probabilities and q_skew three')
+    q = np.ascontiguousarray(np.concatenate([qk, qs]))
+    if not np.all((q >= 0) & (q <= 1)):
+        raise ValueError('quantile probabilities must lie in [0, 1]')
+    return q
+
+
+def sv_summaries(alpha, beta, kappa=1., eta=0., mu=0., phi=0.95, sigma=0.2, n_obs=50, x_0=None, draws=None, seed=0, stream=0,
+                 first_index=0, q_kurt=SV_Q_KURT, q_skew=SV_Q_SKEW, return_series=True, return_logvol=False,
+                 return_shocks=False, return_draws=False, ctx=None):
+    """The alpha-stable stochastic-volatility example (elfi/examples/stochastic_volatility_model.py) as ONE device operation:
+    the log-volatilities x[0] = z[0] sigma / sqrt(1 - min(phi^2, 0.99999)) + mu (with x_0: z[0] sigma + (mu + phi (x_0 - mu))),
+    x[t] = z[t] sigma + (mu + phi (x[t - 1] - mu)); the shocks v[t], alpha-stable with skewness beta, location eta and scale
+    kappa in the S0 parameterisation (elfi_amd.levy_stable_general's transform); the returns y[t] = exp(x[t] / 2) v[t]; and the
+    reference's summaries kurt = (q95 - q05) / (q75 - q25) and skew = ((q95 - q50) - (q50 - q05)) / (q95 - q05) of np.quantile(y,
+    q_kurt) and np.quantile(y, q_skew).  include/elfihip.h (elfihip_sv_summaries) states every operation.
+
+    Every parameter is a scalar or (batch,); x_0 None is the stationary start.  draws: (Z, TH, W), each (batch, n_obs) -- the
+    reference's n_obs calls of standard_normal(batch), then levy_stable's angle uniform((n_obs, batch)) * pi + (-pi / 2) and
+    standard_exponential((n_obs, batch)), simulation first (tests/sv_ref.py: draws_from_state).  draws=None draws on the
+    device, a fixed function of (seed, stream, first_index + row, t) that does not depend on the batch: TH and W from Philox
+    counter ((first_index + row) << 32) | t of `stream` as levy_stable_general draws that counter, Z the first normal of that
+    counter of `stream + 1`.  1 <= n_obs <= 4096.
+    An invalid parameter row (alpha outside (0, 2], beta outside [-1, 1], kappa < 0, sigma < 0, or a NaN parameter) is NaN
+    throughout, for that row alone -- SciPy raises for the whole batch.  A NaN in y makes both summaries NaN.
+    Returns S (batch, 2) = [kurt, skew] [, y (batch, n_obs)] [, x (batch, n_obs)] [, v (batch, n_obs)] [, (Z, TH, W) the draws
+    used] -- the bare array when nothing else is asked for."""
+    n_obs = int(n_obs)
+    if not 1 <= n_obs <= SV_MAX_OBS:
+        raise ValueError('need 1 <= n_obs <= %d' % SV_MAX_OBS)
+    q = _sv_quantiles(q_kurt, q_skew)
+    given = [None] * 3
+    if draws is not None:
+        given = [np.asarray(a) for a in draws]
+        if len(given) != 3 or any(a.ndim != 2 or a.shape != (given[0].shape[0], n_obs) for a in given):
+            raise ValueError('draws must be (Z, TH, W), each (batch, n_obs) = (batch, %d)' % n_obs)
+        given = [np.ascontiguousarray(a, dtype=np.float64) for a in given]
+    ps = [alpha, beta, kappa, eta, mu, phi, sigma] + ([x_0] if x_0 is not None else [])
+    n = given[0].shape[0] if draws is not None else _batch_of(*ps)
+    if n < 1:
+        raise ValueError('need at least one simulation')
+    first_index = _lv_index_range(first_index, n)
+    params = _params(n, *ps)
+    if x_0 is None:
+        params.append(None)
+    S = np.empty((n, 2))
+    Y, X, V = [np.empty((n, n_obs)) if flag else None for flag in (return_series, return_logvol, return_shocks)]
+    echo = [np.empty((n, n_obs)) if return_draws else None for _ in range(3)]
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_sv_summaries", *[_lib.ptr(a) for a in given], C.c_uint64(int(seed)), C.c_uint64(int(stream)), first_index,
+             n, n_obs, _lib.ptr(q), *[_lib.ptr(a) for a in params], _lib.ptr(S), _lib.ptr(Y), _lib.ptr(X), _lib.ptr(V),
+             *[_lib.ptr(a) for a in echo])
+    out = tuple(a for a in (S, Y, X, V, tuple(echo) if return_draws else None) if a is not None)
     return out if len(out) > 1 else S

@@ -847,6 +847,69 @@ int elfihip_toad_summaries_dev(elfihip_ctx* ctx, const double* dU, const double*
                                double* dX, int64_t ldx, double* dDx, int64_t lddx, double* dUo, double* dTHo, double* dWo,
                                int32_t* dRo, int64_t ldo);
 
+/* General alpha-stable variates: SciPy 1.15's levy_stable.rvs(alpha, beta, loc, scale) per element, in SciPy's order of
+ * operations, FMA contraction off (csrc/stable.hpp: stable_general; the NumPy statement is tests/sv_ref.py:
+ * stable_general_step).  From an angle TH and a standard exponential W, with aTH = alpha TH:
+ *   alpha NaN or outside (0, 2], beta NaN or outside [-1, 1], scale NaN or negative: NaN for that element, the batch goes on
+ *   (SciPy raises for the whole call -- the one difference).
+ *   Z, SciPy's _rvs_Z1:
+ *     alpha == 1: (2 / pi) ((pi / 2 + beta TH) tan TH - beta log(((pi / 2) W cos TH) / (pi / 2 + beta TH)));
+ *     beta == 0:  the symmetric expression of elfihip_stable above, one and the same function;
+ *     otherwise:  val0 = beta tan(pi alpha / 2), th0 = atan(val0) / alpha, val3 = W / (cos TH / tan(alpha (th0 + TH)) + sin TH),
+ *                 Z = val3 (((cos aTH + sin aTH tan TH) - val0 (sin aTH - cos aTH tan TH)) / W) ^ (1 / alpha).
+ *   X1 = Z scale + loc; at alpha == 1, X1 = X1 + (((2 beta) scale) log(scale)) / pi (levy_stable.rvs's shift in S1); with s0 = 1
+ *   (the S0 parameterisation) then X1 - ((((beta 2) scale) log(scale)) / pi) at alpha == 1 and X1 - (scale beta) tan((pi alpha)
+ *   / 2) elsewhere; s0 = 0 is S1.  scale == 0 at alpha == 1 is 0 log 0 = NaN, as in SciPy.
+ * angle == expo == NULL (one without the other is ELFIHIP_ERR_ARG): element e draws TH and W from Philox counter e of stream
+ * (seed, stream) exactly as elfihip_stable does, so at beta = 0, loc = 0, s0 = 0 element e is elfihip_stable's element e.
+ * With angle and expo (n each) the transform is applied to them and nothing is drawn.  The device differs from NumPy on the
+ * same TH and W only through tan, sin, cos, atan, log and pow.
+ * Host form: host pointers, synchronises; _dev form: device pointers, no synchronisation, writes out[0 .. n - 1] only. */
+int elfihip_stable_general(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t n, int s0, const double* alpha,
+                           const double* beta, const double* loc, const double* scale, const double* angle, const double* expo,
+                           double* out);
+int elfihip_stable_general_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t n, int s0, const double* dalpha,
+                               const double* dbeta, const double* dloc, const double* dscale, const double* dangle,
+                               const double* dexpo, double* dout);
+
+/* The alpha-stable stochastic-volatility model (elfi/examples/stochastic_volatility_model.py) with its quantile-based
+ * kurtosis and skewness, one workgroup per simulation (csrc/sv.hip; the NumPy statement is tests/sv_ref.py).  Per simulation
+ * alpha, beta, kappa, eta, mu, phi, sigma (n each) and optionally x0 (n, or NULL).  Cell t = 0 .. n_obs - 1 has three draws:
+ * a standard normal Z, an angle TH and a standard exponential W.
+ *   x[0] = Z[0] (sigma / sqrt(1 - min(phi phi, 0.99999))) + mu, or with x0: x[0] = Z[0] sigma + (mu + phi (x0 - mu));
+ *   x[t] = Z[t] sigma + (mu + phi (x[t - 1] - mu))          the reference's log_vol: ss.norm.rvs is standard_normal scale + loc;
+ *   v[t] = the general stable transform above of (alpha, beta, loc = eta, scale = kappa, s0 = 1, TH[t], W[t]);
+ *   y[t] = exp(0.5 x[t]) v[t].
+ * Given draws: Z, TH, W doubles, each (n, n_obs) -- the reference draws n_obs times standard_normal(batch), then uniform((n_obs,
+ * batch)) pi + (-pi / 2) and standard_exponential((n_obs, batch)), transposed here; all three or none.
+ * Z == NULL: drawn here, a fixed function of (seed, stream, g = first_index + row, t), whatever the batch or the launch: with
+ * the 64-bit Philox counter e = (g << 32) | t,
+ *   stream `stream`:      TH and W of element e exactly as elfihip_stable and elfihip_stable_general draw them;
+ *   stream `stream + 1`:  Z = the first normal of counter e: sqrt(-2 log u1) cospi(2 u2), u1 = (((r0 << 21) | (r1 >> 11)) + 1)
+ *                         2^-53 in (0, 1], u2 = ((r2 << 21) | (r3 >> 11)) 2^-53 in [0, 1).
+ * first_index + n <= 2^32.
+ * Summaries: with q = (q_kurt[0 .. 3], q_skew[0 .. 2]) (host array of 7 probabilities in [0, 1]; the example's are 0.05, 0.25,
+ * 0.75, 0.95 and 0.05, 0.5, 0.95) and Q = np.quantile(y, q) (method 'linear'): S[0] = (Q3 - Q0) / (Q2 - Q1), S[1] = ((Q6 - Q5) -
+ * (Q5 - Q4)) / (Q6 - Q4).  A NaN in y makes both NaN, as np.quantile does; n_obs = 1 gives 0 / 0.  On given Z the chain x is
+ * NumPy's bit for bit, on y the summaries are; v and y differ by the device's tan, sin, cos, atan, log, pow and exp.
+ * An invalid parameter row -- alpha outside (0, 2], beta outside [-1, 1], kappa < 0, sigma < 0, or any parameter NaN (x0
+ * included when given) -- is NaN throughout (S, y, x, v) for that row alone.  Limits: n >= 1, 1 <= n_obs <= ELFIHIP_SV_MAX_OBS;
+ * anything else is ELFIHIP_ERR_ARG.
+ * Outputs: S (n, 2); optional, each may be NULL: Y, X, V (n, n_obs) the returns, log-volatilities and shocks; Zo, THo, Wo (n,
+ * n_obs) the draws used, all three or none.  Host form: contiguous host arrays, synchronises.  _dev form: device pointers,
+ * the given draws at pitch ldd, S at lds, Y at ldy, X at ldx, V at ldv, the draw outputs at ldo (in elements), no
+ * synchronisation; q is a host array in both. */
+#define ELFIHIP_SV_MAX_OBS 4096
+int elfihip_sv_summaries(elfihip_ctx* ctx, const double* Z, const double* TH, const double* W, uint64_t seed, uint64_t stream,
+                         int64_t first_index, int64_t n, int n_obs, const double* q, const double* alpha, const double* beta,
+                         const double* kappa, const double* eta, const double* mu, const double* phi, const double* sigma,
+                         const double* x0, double* S, double* Y, double* X, double* V, double* Zo, double* THo, double* Wo);
+int elfihip_sv_summaries_dev(elfihip_ctx* ctx, const double* dZ, const double* dTH, const double* dW, int64_t ldd, uint64_t seed,
+                             uint64_t stream, int64_t first_index, int64_t n, int n_obs, const double* q, const double* dalpha,
+                             const double* dbeta, const double* dkappa, const double* deta, const double* dmu, const double* dphi,
+                             const double* dsigma, const double* dx0, double* dS, int64_t lds, double* dY, int64_t ldy, double* dX,
+                             int64_t ldx, double* dV, int64_t ldv, double* dZo, double* dTHo, double* dWo, int64_t ldo);
+
 /* The stochastic Lorenz-96 forecast model (elfi/examples/lorenz.py), fused the same way: draws, the Runge-Kutta recurrence,
  * the six summaries and the distance in one pass; series and summaries bit-identical to the reference's NumPy on the same
  * draws.  K = n_obs variables in 4 .. ELFIHIP_LORENZ_MAX_VARS, T = n_timestep >= 2 rows, T K <= ELFIHIP_LORENZ_MAX_TERMS
