@@ -388,7 +388,7 @@ static int adjust_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64_
   const GroupParams B = group_params(prefixes, K, n, toff.data(), nullptr, 0);
   ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve(B.words.size() * sizeof(double)));
   double* dpar = ctx->par.as<double>();
-  // pageable host memory: the copy has left it before hipMemcpyAsync returns
+  // pageable host memory: the copy is done with it when hipMemcpyAsync returns (common.hpp: pageable uploads)
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, B.words.data(), B.words.size() * sizeof(double), hipMemcpyHostToDevice, st));
   const size_t J = (size_t)G * Ke, tiles = (size_t)G * (size_t)sumT, rec_len = (size_t)W + 2 * m + 1;
   // scratch: [tri tiles W W][rec tiles rec_len][mean J W][beta J q m][jflag J][jstatus J]

@@ -242,6 +242,15 @@ static inline int launch_by_tiles(elfihip_ctx* ctx, int m, unsigned grid, const 
   return rc != ELFIHIP_OK ? rc : launch_status(ctx, name);
 }
 
+// Pageable uploads.  The _dev entry points upload small host arrays (prefixes, penalties, masks, group parameters built in a
+// local vector) with hipMemcpyAsync from pageable memory and return at once; the caller, or the end of the function, may
+// then overwrite the source.  That is safe on this runtime (ROCm 7.0, measured on a stream kept busy for 20 ms): a copy of up
+// to 1 MiB is staged before the call returns -- it returns within microseconds, the stream is still busy, the device
+// receives the bytes as they were at the call -- and a copy too long to stage (16 MiB) holds the CALL until the stream has
+// drained, so the source is done with on return either way; an upload beyond the staging size would make a _dev entry
+// point wait for the stream.  tests/test_stream_order_gpu.py overwrites every host array argument the moment its call
+// returns, on a busy stream, and compares bit for bit.
+
 // rows x m doubles from host memory at pitch ld (in doubles) to contiguous device memory, on the context's stream
 inline int upload_rows(elfihip_ctx* ctx, double* dst, const double* src, size_t rows, int m, int64_t ld) {
   const size_t md = (size_t)m * sizeof(double);

@@ -294,7 +294,7 @@ static int semibsl_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64
   const int MP = 16 * group_tiles(m);
   ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve(B.words.size() * sizeof(double)));
   double* dpar = ctx->par.as<double>();
-  // pageable host memory: the copy has left it before hipMemcpyAsync returns
+  // pageable host memory: the copy is done with it when hipMemcpyAsync returns (common.hpp: pageable uploads)
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, B.words.data(), B.words.size() * sizeof(double), hipMemcpyHostToDevice, st));
   const size_t qd = (size_t)GK * (size_t)n * MP;
   ELFIHIP_CHECK_HIP(ctx, ctx->scratch.reserve((qd + (size_t)GK * SEMI_STATS) * sizeof(double)));

@@ -277,7 +277,7 @@ static int synlik_dev_impl(elfihip_ctx* ctx, const double* dX, int G, int64_t n,
   const GroupParams B = group_params(prefixes, K, n, konst.data(), penalties, P);
   ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve((B.words.size() + m) * sizeof(double)));
   double* dpar = ctx->par.as<double>();
-  // pageable host memory: the copy has left it before hipMemcpyAsync returns
+  // pageable host memory: the copy is done with it when hipMemcpyAsync returns (common.hpp: pageable uploads)
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, B.words.data(), B.words.size() * sizeof(double), hipMemcpyHostToDevice, st));
   SynArgs A;
   A.X = dX;

@@ -867,8 +867,8 @@ int topk_dev_impl(elfihip_ctx* ctx, const double* dD, int64_t n, int64_t stride,
   ELFIHIP_CHECK_HIP(ctx, ctx->scratch.reserve(bytes));
   SelState* ds = ctx->scratch.as<SelState>();
   unsigned int* counts = reinterpret_cast<unsigned int*>(ds + 1);
-  // (a kernel, not a copy of a host struct: an asynchronous copy from this function's stack may be read after it returned
-  // when the stream is busy -- found by scripts/soak_round.py once the sampler stopped draining the stream before its fall-back)
+  // (a kernel, not a copy of a host struct: the values travel as kernel arguments, nothing is staged on the stream.  The late
+  // read of a stack source that scripts/soak_round.py once reported here has not shown again: common.hpp, pageable uploads)
   hipLaunchKernelGGL(sel_init_kernel, dim3(SEL_BINS / 256), dim3(256), 0, st, ds, (unsigned long long)k);
   // one workgroup per CU at most: each pays a device-scope fence, and a launch of this size is latency-bound anyway
   // (10^6 keys: 0.16 ms with 8 workgroups per CU, 0.10 ms with one)

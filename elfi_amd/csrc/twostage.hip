@@ -348,7 +348,7 @@ static int subset_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t n, int m,
   ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve((size_t)C * m * sizeof(double)));
   ELFIHIP_CHECK_HIP(ctx, ctx->sel.reserve((size_t)Cmax * per_col));
   double* dM = ctx->par.as<double>();
-  // pageable host memory: the copy has left it before hipMemcpyAsync returns
+  // pageable host memory: the copy is done with it when hipMemcpyAsync returns (common.hpp: pageable uploads)
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dM, masks, (size_t)C * m * sizeof(double), hipMemcpyHostToDevice, st));
   double* dD = ctx->sel.as<double>();
   double* sv = dD + (size_t)n * Cmax;

@@ -14,7 +14,13 @@
  *    buffers it owns and never keeps a caller pointer after it returns.
  *  - "_dev" twins take DEVICE pointers (every pointer argument, including the small
  *    y / w vectors), enqueue on the context's stream and return without
- *    synchronising; results are ordered with later work on the same stream.
+ *    synchronising; results are ordered with later work on the same stream.  Where a _dev
+ *    form takes a small HOST array (it says so below), the array may be overwritten as soon
+ *    as the call has returned; the entry points that do wait for the stream say so below
+ *    (elfihip_subset_best_dev, elfihip_adaptive_push_dev's first-batch check, and pushes,
+ *    elfihip_reject_flush and elfihip_reject_state_dev on host-merge states).
+ *    tests/test_stream_order_gpu.py holds every _dev entry point to this
+ *    on an adopted stream that is busy.
  *  - a context is bound to one GPU and one HIP stream; it is not thread-safe, but
  *    distinct contexts may be used from distinct threads.
  *  - all floating point is IEEE binary64; row sums are accumulated in the same
@@ -251,8 +257,10 @@ int elfihip_reject_export_dev(elfihip_reject* h, void* ddst);
  * current k-th distance from above, so nothing is missed.  States with k <= 1024 pushed through the row distances
  * (m = 16 / 32 / 64) SEAL the list at a merge point instead, and the next such push merges it in one workgroup of its own
  * distance launch; every other reader or push form merges a sealed list first.  The export buffer written is the one
- * current when the merge is launched.  elfihip_reject_flush merges what is pending now (asynchronous); _result,
- * _state_dev do so themselves. */
+ * current when the merge is launched.  elfihip_reject_flush merges what is pending now; _result, _state_dev do so
+ * themselves.  On a device state (k <= 2048) _flush and _state_dev only queue that merge on the context's stream and
+ * return: work queued behind _state_dev sees every batch merged at the pointers it returns.  On a host-merge state
+ * both wait for the stream, as its pushes do. */
 int elfihip_reject_flush(elfihip_reject* h);
 /* vals / rows: k entries each; *count = entries in use.  A NaN distance never enters the state (the reference's argsort
  * would list such rows last, after every finite distance): while fewer than k finite distances have been seen, count is
