@@ -261,6 +261,15 @@ PROTOTYPES = {
                                         C.c_void_p]),
     "elfihip_daycare_draws_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int64,
                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "elfihip_assay_summaries": (C.c_int, [C.c_void_p] * 4 + [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                                               C.c_int, C.c_int] + [C.c_void_p] * 7),
+    "elfihip_assay_summaries_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                                                   C.c_int, C.c_int] + [C.c_void_p] * 4 +
+                                    [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "elfihip_assay_draws": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int] +
+                            [C.c_void_p] * 4),
+    "elfihip_assay_draws_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int] +
+                                [C.c_void_p] * 4),
     "elfihip_stable": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64] + [C.c_void_p] * 5),
     "elfihip_stable_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64] + [C.c_void_p] * 5),
     "elfihip_toad_summaries": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int,

@@ -83,6 +83,8 @@ struct elfihip_ctx {
   elfihip::DevBuf lv;     // gillespie.hip: the counter simulations are dealt from, and the observations when the caller keeps none
   elfihip::DevBuf dc;     // daycare.hip: the counter pairs are dealt from, carriage masks and summaries the caller keeps none of, the sorted observed rows
   int dc_per_cu[2] = {0, 0};         // daycare.hip: resident workgroups per CU of dc_sim_kernel<DRAWN>, asked for once
+  elfihip::DevBuf sa;     // scratch_assay.hip: the counter simulations are dealt from
+  int sa_per_cu[2] = {0, 0};         // scratch_assay.hip: resident workgroups per CU of sa_sim_kernel<DRAWN>, asked for once
   int lv_per_cu[4] = {0, 0, 0, 0};   // gillespie.hip: resident workgroups per CU of lv_sim_kernel<DRAWN, NOISE>, asked for once
   // the distances the last host-form distance call returned, kept on the device for the sampler state
   // (elfihip_kept_distances / elfihip_reject_push_kept): (keep_n, keep_cols) row-major; the epoch names the call

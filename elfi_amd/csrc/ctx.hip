@@ -167,6 +167,7 @@ int elfihip_ctx_destroy(elfihip_ctx* ctx) {
     ctx->sel.release();
     ctx->lv.release();
     ctx->dc.release();
+    ctx->sa.release();
     ctx->keep.release();
     ctx->rows.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

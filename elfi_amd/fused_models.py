@@ -112,6 +112,7 @@ from .summaries import LV_NAMES, lotka_volterra_summaries
 from .summaries import DAYCARE_NAMES, daycare_distance, daycare_summaries
 from .summaries import TOAD_LAGS, toad_summaries
 from .summaries import sv_summaries
+from .summaries import scratch_assay_summaries
 
 
 def _elfi():
@@ -627,6 +628,45 @@ def sv_model(n_obs=50, true_params=None, seed_obs=None, device_priors=True):
     kurt = elfi.Summary(partial(column, j=n_obs), m['a_svm'], name='kurt')
     skew = elfi.Summary(partial(column, j=n_obs + 1), m['a_svm'], name='skew')
     elfi.Distance(HipDistance('euclidean'), kurt, skew, name='d')
+    return m
+
+
+def scratch_assay_rows(pm, pp, init_arr, batch_size=1, random_state=None):
+    """Simulator operation: (batch, n_obs + 1) summaries of scratch assays walked and reduced on the device."""
+    pm, pp = _per_simulation(batch_size, pm, pp)
+    return scratch_assay_summaries(pm, pp, init_arr, seed=_seed_of(random_state), stream=SIMULATOR_STREAM_BASE)
+
+
+def scratch_assay_model(true_params=None, init_arr=None, init_params=None, seed_obs=None, device_priors=True):
+    """elfi.examples.scratch_assay.get_model(true_params, init_arr, init_params, seed_obs) with the simulation on the device;
+    nodes pm, pp, sim, sums, d.  The node sim returns the (batch, 145) summaries of Price et al. (the reference's sim returns
+    the frames and its sums reduces them on the host); the Summary node sums hands them on, and d is elfi.Distance over
+    HipDistance('euclidean', w=weis) with the reference's weights.  The observed frames are the reference's own cell_sim with
+    RandomState(seed_obs) -- which also draws the initial grid when init_arr is None -- reduced once with the reference's
+    cell_summaries.  The grid holds at most 1024 cells.  device_priors: the two uniform priors draw on the device
+    (elfi_amd.priors.uniform).
+
+    elfi.BSL(m, ..., feature_names=['sums']) runs this model under the reference's host likelihood; elfi_amd.HipBSL takes a
+    Summary of at most 64 columns and refuses the 145 of sums."""
+    if true_params is None:
+        true_params = [0.25, 0.002]
+    if len(true_params) != 2:
+        raise ValueError('true_params must be [pm, pp]')
+    elfi = _elfi()
+    from elfi.examples import scratch_assay as sa
+    from . import priors
+    obs = sa.cell_sim(*true_params, init_arr, init_params, random_state=np.random.RandomState(seed_obs))
+    init = np.ascontiguousarray(obs[:, :, 0], dtype=np.uint8)
+    observed = np.asarray(sa.cell_summaries(obs[None, :]), dtype=np.float64)                       # (1, n_obs + 1)
+    m = elfi.ElfiModel()
+    uniform = priors.uniform if device_priors else 'uniform'
+    nodes = [elfi.Prior(uniform, 0, 1, model=m, name='pm'),
+             elfi.Prior(uniform, 0, 1, model=m, name='pp')]
+    elfi.Simulator(partial(scratch_assay_rows, init_arr=init), *nodes, observed=observed, name='sim')
+    elfi.Summary(columns, m['sim'], name='sums')
+    num_ds = m['sums'].observed.size - 1
+    weis = np.concatenate((np.ones(num_ds) / num_ds, np.array([1]))) / np.sum(init) ** 2
+    elfi.Distance(HipDistance('euclidean', w=weis), m['sums'], name='d')
     return m
 
 

@@ -25,6 +25,8 @@ leading dimension of 1 -- elfi/model/elfi_model.py:915-943, elfi/compiler.py:94-
                          [+ distance]                                             elfi/examples/lotka_volterra.py
     daycare_summaries(...)  the day-care-centre transmission example: Gillespie simulation of every centre, 4 summaries per
                          centre [+ distance]; daycare_distance(...) its sorted L1 distance      elfi/examples/daycare.py
+    scratch_assay_summaries(...)  the scratch-assay example: the lattice walk of up to 1024 cells, its 145 summaries
+                                                                                  elfi/examples/scratch_assay.py
 
     S1 = elfi.Summary(elfi_amd.autocov, Y);  S2 = elfi.Summary(elfi_amd.autocov, Y, 2)
 
@@ -953,4 +955,100 @@ def sv_summaries(alpha, beta, kappa=1., eta=0., mu=0., phi=0.95, sigma=0.2, n_ob
              n, n_obs, _lib.ptr(q), *[_lib.ptr(a) for a in params], _lib.ptr(S), _lib.ptr(Y), _lib.ptr(X), _lib.ptr(V),
              *[_lib.ptr(a) for a in echo])
     out = tuple(a for a in (S, Y, X, V, tuple(echo) if return_draws else None) if a is not None)
+    return out if len(out) > 1 else S
+
+
+# ---- the scratch-assay example model (csrc/scratch_assay.hip) ------------------------------------------------------------
+ASSAY_MAX_CELLS = 1024                                    # include/elfihip.h: ELFIHIP_ASSAY_MAX_CELLS
+ASSAY_MAX_ITER = 1 << 21                                  # ELFIHIP_ASSAY_MAX_ITER
+ASSAY_STATUS = ('ok', 'bad_draw')                         # ELFIHIP_ASSAY_OK, ELFIHIP_ASSAY_BAD_DRAW
+
+
+def scratch_assay_shape(obs_period=12, obs_interval=1 / 12, tau=1 / 24):
+    """(n_iter, obs_every, n_obs) as elfi/examples/scratch_assay.py:73-75 computes them: int(obs_period / tau), int(obs_interval
+    / tau), int(n_iter / obs_every).  The device takes only these integers."""
+    with np.errstate(all='ignore'):
+        ratio, every = np.float64(obs_period) / np.float64(tau), np.float64(obs_interval) / np.float64(tau)
+    if not (np.isfinite(ratio) and np.isfinite(every) and 1 <= ratio <= ASSAY_MAX_ITER and every >= 1):
+        raise ValueError('need 1 <= int(obs_period / tau) <= 2^21 iterations and int(obs_interval / tau) >= 1')
+    n_iter, obs_every = int(ratio), int(every)
+    if obs_every > n_iter:
+        raise ValueError('no observation: int(obs_interval / tau) = %d exceeds the %d iterations' % (obs_every, n_iter))
+    return n_iter, obs_every, int(n_iter / obs_every)
+
+
+def _assay_grid(init_arr):
+    init = np.asarray(init_arr)
+    if init.ndim != 2 or not 1 <= init.size <= ASSAY_MAX_CELLS:
+        raise ValueError('init_arr must be a grid (nrows, ncols) of 1 to %d cells' % ASSAY_MAX_CELLS)
+    if not np.all((init == 0) | (init == 1)):
+        raise ValueError('init_arr must hold zeros and ones')
+    return np.ascontiguousarray(init, dtype=np.uint8)
+
+
+def scratch_assay_draws(num_cells, n_cells, seed=0, stream=0, first_index=0, ctx=None):
+    """(C, P, M), each (n, n_iter, 2, n_cells) -- int32 candidates, float64 uniforms, uint8 directions: what the drawn form of
+    scratch_assay_summaries uses in phase f of iteration t of simulations first_index .. first_index + n - 1 when that phase
+    has num_cells[i, t, f] slots (zero past them): one Philox call per slot, counter words (((2 t + f) << 10) | slot,
+    simulation) of (seed, stream).  Handing them back as draws=(C, P, M) reproduces the drawn form bit for bit."""
+    num = np.ascontiguousarray(num_cells, dtype=np.int32)
+    n_cells = int(n_cells)
+    if num.ndim != 3 or num.shape[2] != 2 or num.shape[0] < 1 or not 1 <= num.shape[1] <= ASSAY_MAX_ITER:
+        raise ValueError('num_cells must be (n, n_iter, 2) with n >= 1 and 1 <= n_iter <= 2^21')
+    if not 1 <= n_cells <= ASSAY_MAX_CELLS or num.min() < 0 or num.max() > n_cells:
+        raise ValueError('need 1 <= n_cells <= %d and 0 <= num_cells <= n_cells' % ASSAY_MAX_CELLS)
+    n, n_iter = num.shape[:2]
+    first_index = _lv_index_range(first_index, n)
+    Cd, P, M = (np.empty((n, n_iter, 2, n_cells), dtype=t) for t in (np.int32, np.float64, np.uint8))
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_assay_draws", C.c_uint64(int(seed)), C.c_uint64(int(stream)), first_index, n, n_iter, n_cells, _lib.ptr(num),
+             _lib.ptr(Cd), _lib.ptr(P), _lib.ptr(M))
+    return Cd, P, M
+
+
+def scratch_assay_summaries(pm, pp, init_arr, obs_period=12, obs_interval=1 / 12, tau=1 / 24, seed=0, stream=0, first_index=0,
+                            draws=None, return_frames=False, return_events=False, ctx=None):
+    """The scratch-assay example (elfi/examples/scratch_assay.py: cell_sim and cell_summaries) as ONE device operation: the
+    random walk with proliferation of the cells of the binary grid init_arr (nrows, ncols), at most 1024 cells, shared by the
+    batch, over int(obs_period / tau) iterations, and the summaries of Price et al. (2018) -- the number of cells that differ
+    between consecutive frames, a frame every int(obs_interval / tau) iterations, then the last frame's cell count.
+    include/elfihip.h (elfihip_assay_summaries) states every operation.
+
+    pm, pp: (batch,) or scalars, compared as they come (NaN selects nothing; no value is invalid).  draws: (C, P, M), each
+    (batch, n_iter, 2, nrows ncols) -- int32 candidates, float64 uniforms, uint8 directions per slot of the motility and the
+    proliferation phase of every iteration; entries past the current cell count are not read, and a candidate outside [0,
+    cell count) or a direction above 3 that IS read ends that simulation with status 1, NaN summaries, empty frames.
+    draws=None draws on the device from (seed, stream, first_index + simulation, iteration, phase, slot), so a simulation does
+    not depend on the batch it runs in.  The reference's RandomState stream is not reproduced: its choice() rejects, the
+    device's candidate is the high half of word x cell count (bias below 2.4e-7).
+    Returns S (batch, n_obs + 1) [, frames (batch, nrows, ncols, n_obs + 1) uint8, the reference's layout] [, status (batch,)
+    int32, events (batch, 2) int64: motility and proliferation events executed] -- the bare array when nothing else is asked
+    for."""
+    init = _assay_grid(init_arr)
+    nrows, ncols = init.shape
+    n_iter, obs_every, n_obs = scratch_assay_shape(obs_period, obs_interval, tau)
+    Cd = P = M = None
+    if draws is not None:
+        Cd, P, M = (np.asarray(a) for a in draws)
+        want = (n_iter, 2, nrows * ncols)
+        if Cd.ndim != 4 or Cd.shape[1:] != want or P.shape != Cd.shape or M.shape != Cd.shape:
+            raise ValueError('draws must be (C, P, M), each (batch, n_iter, 2, cells) = (batch, %d, 2, %d)' % (n_iter, want[2]))
+        Cd, P, M = (np.ascontiguousarray(a, dtype=t) for a, t in ((Cd, np.int32), (P, np.float64), (M, np.uint8)))
+    n = Cd.shape[0] if Cd is not None else _batch_of(pm, pp)
+    if n < 1:
+        raise ValueError('need at least one simulation')
+    first_index = _lv_index_range(first_index, n)
+    pm, pp = _params(n, pm, pp)
+    S = np.empty((n, n_obs + 1))
+    frames = np.empty((n, n_obs + 1, ASSAY_MAX_CELLS // 32), dtype=np.uint32) if return_frames else None
+    status = np.empty(n, dtype=np.int32) if return_events else None
+    events = np.empty((n, 2), dtype=np.int64) if return_events else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_assay_summaries", _lib.ptr(Cd), _lib.ptr(P), _lib.ptr(M), C.c_uint64(int(seed)), C.c_uint64(int(stream)),
+             first_index, n, nrows, ncols, n_iter, obs_every, _lib.ptr(init), _lib.ptr(pm), _lib.ptr(pp), _lib.ptr(S),
+             _lib.ptr(status), _lib.ptr(events), _lib.ptr(frames))
+    if frames is not None:
+        bits = np.unpackbits(frames.view(np.uint8), axis=2, bitorder='little')[:, :, :nrows * ncols]
+        frames = np.ascontiguousarray(bits.reshape(n, n_obs + 1, nrows, ncols).transpose(0, 2, 3, 1))
+    out = tuple(a for a in (S, frames, status, events) if a is not None)
     return out if len(out) > 1 else S

@@ -794,6 +794,63 @@ int elfihip_daycare_distance(elfihip_ctx* ctx, const double* X, int64_t n, int k
 int elfihip_daycare_distance_dev(elfihip_ctx* ctx, const double* dX, int64_t ldx, int64_t n, int k, int m, const double* obs,
                                  double* dD);
 
+/* The scratch-assay model (elfi/examples/scratch_assay.py; the cell-motility model of Johnston et al. 2014 with the summaries of
+ * Price et al. 2018, the test problem of the BSL paper): a random walk with proliferation of the cells of a binary grid of nrows
+ * x ncols cells, and its n_obs + 1 summaries (csrc/scratch_assay.hip; the NumPy statement is tests/assay_ref.py).  Per
+ * simulation: pm, pp (n each).  Host scalars nrows, ncols, n_iter, obs_every -- the caller computes n_iter = int(obs_period /
+ * tau) and obs_every = int(obs_interval / tau) as the example does; n_obs = n_iter / obs_every (integer division) -- and init
+ * (nrows ncols host bytes, each 0 or 1, row-major): the initial grid, shared by the batch.  Iteration t = 0 .. n_iter - 1:
+ *   1. num_cells = the cell count; the list = the occupied cells in row-major order (np.where).
+ *   2. A full grid: the iteration does nothing and consumes no draw.
+ *   3. Motility.  Slots k = 0 .. num_cells - 1 each have a candidate C[k] in [0, num_cells), a uniform P[k] and a direction
+ *      M[k].  The slots with P[k] < pm are events, executed in slot order.  The event's cell is list[C[k]]; its target is the
+ *      neighbour M 0: row + 1, 1: row - 1, 2: col + 1, 3: col - 1, clamped to the grid (at an edge: the cell itself).  An empty
+ *      target: the cell moves there and list[C[k]] becomes the target.  A candidate may occur, and move, several times.
+ *   4. Proliferation.  Fresh C, P, M over the same num_cells slots, against pp, on the list as motility left it (a cell born
+ *      here is in no list before the next iteration).  The clamped target is set to 1 whether or not it was empty.
+ *   5. (t + 1) % obs_every == 0: the grid is frame (t + 1) / obs_every.  Frame 0 is the initial grid.
+ * P[k] < pm is evaluated as it stands: a NaN selects nothing, values outside [0, 1] are legal, no parameter value is invalid.
+ * An empty grid stays empty (the reference runs it too and returns zeros).
+ * S (n, n_obs + 1): ds[j] = the number of cells that differ between frames j and j + 1, j = 0 .. n_obs - 1, then the cell count
+ * of frame n_obs; all integers, exact.  status (n) int32; events (n, 2) int64: the motility and the proliferation events
+ * executed (the slots selected); frames (n, n_obs + 1, 32) uint32: cell c = row ncols + col at bit c % 32 of word c / 32.
+ * status, events and frames may be NULL.
+ * Randomness.  Given form: C int32, P float64, M uint8, each (n, n_iter, 2, nrows ncols), contiguous: row (t, f) feeds phase f
+ * (0 motility, 1 proliferation) of iteration t.  Entries at k >= num_cells are never read; every entry read is checked before
+ * anything is indexed by it: a C[k] outside [0, num_cells) or an M[k] above 3 ends that simulation with status
+ * ELFIHIP_ASSAY_BAD_DRAW, NaN summaries, zero frames and zero event counts; no other simulation changes.  Drawn form (C == P ==
+ * M == NULL; one without the others is ELFIHIP_ERR_ARG): slot k of phase f of iteration t of simulation g = first + i makes ONE
+ * Philox4x32-10 call under key seed with the counter words (((2 t + f) << 10) | k, g, stream low, stream high):
+ *     C[k] = (w0 num_cells) >> 32;  P[k] = ((w1 << 21) | (w2 >> 11)) 2^-53;  M[k] = w3 >> 30
+ * The direction is keyed by the slot, not by the order of the events, so no draw depends on what happened before it, and a
+ * simulation's result is a function of (pm, pp, init, seed, stream, first + i) and the shape alone: not of n, of the launch, or of
+ * the wavefront that ran it.  (The reference's RandomState.choice rejects to be exactly uniform; the multiply-high candidate is
+ * biased by at most num_cells / 2^32 < 2.4e-7.  The reference draws a direction per event in event order; its stream is not
+ * reproduced.)  elfihip_assay_draws writes the C, P, M of the drawn form for num_cells (n, n_iter, 2) int32 slots per row -- zero
+ * past them, num_cells clamped to [0, cells] (the host form refuses values outside) -- into memory: the drawn form IS the given
+ * form on them, with num_cells the cell counts the simulation went through (0 where the grid was full).
+ * Limits: 1 <= nrows ncols <= ELFIHIP_ASSAY_MAX_CELLS, 1 <= n_iter <= ELFIHIP_ASSAY_MAX_ITER, 1 <= obs_every <= n_iter (so n_obs
+ * >= 1), 1 <= n <= ELFIHIP_ASSAY_MAX_BATCH, first >= 0 and first + n <= 2^32, init bytes 0 or 1; anything else is
+ * ELFIHIP_ERR_ARG, before the device is touched.
+ * Host forms: contiguous host arrays, synchronise.  _dev forms: device pointers, S with the caller's leading dimension lds >=
+ * n_obs + 1 in doubles, no synchronisation; init is a host array in both and is done with when the call returns. */
+#define ELFIHIP_ASSAY_MAX_CELLS 1024
+#define ELFIHIP_ASSAY_MAX_ITER (1 << 21)
+#define ELFIHIP_ASSAY_MAX_BATCH 2147483647LL
+#define ELFIHIP_ASSAY_OK 0
+#define ELFIHIP_ASSAY_BAD_DRAW 1
+int elfihip_assay_summaries(elfihip_ctx* ctx, const int32_t* C, const double* P, const uint8_t* M, uint64_t seed, uint64_t stream,
+                            int64_t first, int64_t n, int nrows, int ncols, int n_iter, int obs_every, const uint8_t* init,
+                            const double* pm, const double* pp, double* S, int32_t* status, int64_t* events, uint32_t* frames);
+int elfihip_assay_summaries_dev(elfihip_ctx* ctx, const int32_t* dC, const double* dP, const uint8_t* dM, uint64_t seed,
+                                uint64_t stream, int64_t first, int64_t n, int nrows, int ncols, int n_iter, int obs_every,
+                                const uint8_t* init, const double* dpm, const double* dpp, double* dS, int64_t lds,
+                                int32_t* dstatus, int64_t* devents, uint32_t* dframes);
+int elfihip_assay_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int n_iter, int cells,
+                        const int32_t* num_cells, int32_t* C, double* P, uint8_t* M);
+int elfihip_assay_draws_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int n_iter, int cells,
+                            const int32_t* dnum_cells, int32_t* dC, double* dP, uint8_t* dM);
+
 /* Symmetric (beta = 0) alpha-stable variates, S1 parameterisation: the Chambers-Mallows-Stuck transform as SciPy 1.15's
  * levy_stable.rvs evaluates it (_rvs_Z1), in SciPy's order of operations, FMA contraction off (csrc/stable.hpp; the NumPy
  * statement is tests/toad_ref.py: stable_step).  From an angle TH in (-pi/2, pi/2) and a standard exponential W:
