@@ -40,6 +40,8 @@ from .summaries import levy_stable_general, sv_summaries  # noqa: F401
 from .fused_models import sv_model  # noqa: F401
 from .summaries import scratch_assay_draws, scratch_assay_shape, scratch_assay_summaries  # noqa: F401
 from .fused_models import scratch_assay_model  # noqa: F401
+from .summaries import ar1_series, bdm_clusters, bdm_draws  # noqa: F401
+from .fused_models import ar1_model, ar1_rows, bdm_model, bdm_rows  # noqa: F401
 from .fused_models import lotka_volterra_model, lv_summary_rows  # noqa: F401
 from .fused_models import daycare_model, daycare_summary_rows  # noqa: F401
 from .lcb_acquisition import HipLCBSC  # noqa: F401

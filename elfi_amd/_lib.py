@@ -210,6 +210,10 @@ PROTOTYPES = {
     "elfihip_arch_summaries_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                              C.c_void_p, C.c_int64, C.c_void_p]),
+    "elfihip_ar1_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "elfihip_ar1_series_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "elfihip_mg1_summaries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -270,6 +274,15 @@ PROTOTYPES = {
                             [C.c_void_p] * 4),
     "elfihip_assay_draws_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int] +
                                 [C.c_void_p] * 4),
+    "elfihip_bdm_clusters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 6),
+    "elfihip_bdm_clusters_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64,
+                                           C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_void_p]),
+    "elfihip_bdm_draws": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "elfihip_bdm_draws_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_int64]),
     "elfihip_stable": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64] + [C.c_void_p] * 5),
     "elfihip_stable_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64] + [C.c_void_p] * 5),
     "elfihip_toad_summaries": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int,

@@ -85,6 +85,8 @@ struct elfihip_ctx {
   int dc_per_cu[2] = {0, 0};         // daycare.hip: resident workgroups per CU of dc_sim_kernel<DRAWN>, asked for once
   elfihip::DevBuf sa;     // scratch_assay.hip: the counter simulations are dealt from
   int sa_per_cu[2] = {0, 0};         // scratch_assay.hip: resident workgroups per CU of sa_sim_kernel<DRAWN>, asked for once
+  elfihip::DevBuf bd;     // bdm.hip: the counter simulations are dealt from
+  int bd_per_cu[6] = {0, 0, 0, 0, 0, 0};   // bdm.hip: resident workgroups per CU of bd_sim_kernel<DRAWN, WIDE> and bd_pair_kernel<DRAWN>, asked for once
   int lv_per_cu[4] = {0, 0, 0, 0};   // gillespie.hip: resident workgroups per CU of lv_sim_kernel<DRAWN, NOISE>, asked for once
   // the distances the last host-form distance call returned, kept on the device for the sampler state
   // (elfihip_kept_distances / elfihip_reject_push_kept): (keep_n, keep_cols) row-major; the epoch names the call

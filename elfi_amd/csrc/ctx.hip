@@ -168,6 +168,7 @@ int elfihip_ctx_destroy(elfihip_ctx* ctx) {
     ctx->lv.release();
     ctx->dc.release();
     ctx->sa.release();
+    ctx->bd.release();
     ctx->keep.release();
     ctx->rows.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

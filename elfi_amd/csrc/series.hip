@@ -13,9 +13,12 @@
 // and for elfi/examples/ricker.py:
 //     stock = stock_prev * np.exp(log_rate - stock_prev + std * randn(batch)); stock_obs[:, ii] = poisson(scale * stock)
 //     np.mean, np.var, num_zeros, chi_squared -- 2 n_obs small NumPy calls per batch                  ricker.py:11-167
+// and for elfi/examples/ar1.py:
+//     w = randn(batch, n_obs + 1); x[:, i] = phi * x_prev + w[:, i]  -- n_obs small NumPy calls        ar1.py:28-38
+//     and the euclidean distance on the raw series
 //
-// All three simulators have a recurrence along the series (ARCH: a chain of dependent square roots; M/G/1: two running sums
-// and a maximum; Ricker: a chain of dependent exponentials), so a simulation belongs to ONE lane from its first step to
+// All four simulators have a recurrence along the series (ARCH: a chain of dependent square roots; M/G/1: two running sums
+// and a maximum; Ricker: a chain of dependent exponentials; AR(1): a chain of multiply-adds, each rounded twice), so a simulation belongs to ONE lane from its first step to
 // its distance.  A workgroup is one wavefront and a tile is 64 simulations (fewer when 64 rows do not fit the LDS, and 32
 // for the stochastic Ricker model, see its launch): the 64 lanes first fill the tile's draws together
 // -- coalesced loads of the caller's draws, or Philox4x32-10 pairs, every lane drawing -- then each lane runs its row's
@@ -37,6 +40,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "dist_launch.hpp"
 #include "dist_metrics.hpp"
 #include "np_sum.hpp"
 #include "philox.hpp"
@@ -170,6 +174,89 @@ __global__ __launch_bounds__(SERIES_THREADS) void arch_kernel(ArchArgs A) {
         for (int j = i + 1; j < ARCH_MAX_LAGS; ++j)
           if (j < A.lags) put(ac[i] * ac[j]);
       if (A.D) A.D[gi] = Euclid::finish(acc, 0.5);
+    }
+  }
+}
+
+// ---- AR(1) ----------------------------------------------------------------------------------------------------------
+struct Ar1Args {
+  const double* W;      // (n, ldw) noise, or NULL: drawn here
+  int64_t ldw;
+  uint64_t seed, stream;
+  const double* phi;    // (n)
+  int64_t n;
+  int n_obs;
+  int Lp, rows;         // LDS row pitch (odd), rows per tile
+  double* X;            // optional (n, ldx): the series
+  int64_t ldx;
+  double* D;            // optional (n): euclidean distance to obs
+  const double* dobs;   // (n_obs) observed series on the device, with D
+};
+
+__global__ __launch_bounds__(SERIES_THREADS) void ar1_kernel(Ar1Args A) {
+  extern __shared__ __align__(16) double tile[];
+  using Euclid = Op<ELFIHIP_EUCLIDEAN, false>;   // cdist's euclidean, the distance kernels' own row arithmetic
+  const int tid = threadIdx.x, nobs = A.n_obs, Lw = A.n_obs + 1, Lp = A.Lp, Rt = A.rows;
+  const int64_t ntiles = (A.n + Rt - 1) / Rt;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t row0 = t * Rt;
+    const int rows = (int)((A.n - row0) < Rt ? (A.n - row0) : Rt);
+    __syncthreads();
+    if (A.W) {
+      for (int e = tid; e < rows * Lw; e += SERIES_THREADS) {
+        const int r = e / Lw, i = e - r * Lw;
+        tile[r * Lp + i] = A.W[(row0 + r) * A.ldw + i];
+      }
+    } else {
+      // elements [e0, e1) of the row-major (n, n_obs + 1) matrix; a pair that straddles the tile's end is drawn by both tiles
+      const int64_t e0 = row0 * Lw, e1 = e0 + (int64_t)rows * Lw;
+      for (int64_t p = e0 / 2 + tid; 2 * p < e1; p += SERIES_THREADS) {
+        double z[2];
+        normal_pair(A.seed, A.stream, (uint64_t)p, z[0], z[1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int64_t e = 2 * p + h;
+          if (e >= e0 && e < e1) {
+            const int off = (int)(e - e0), r = off / Lw, i = off - r * Lw;
+            tile[r * Lp + i] = z[h];
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < rows) {
+      // the chain: x_i takes the place of the noise before the one it has consumed (position i - 1 < i)
+      double* w = tile + (size_t)tid * Lp;
+      const double phi = A.phi[row0 + tid];
+      double x = 0.0;
+      for (int i = 1; i <= nobs; ++i) {
+        x = phi * x + w[i];
+        w[i - 1] = x;
+      }
+    }
+    __syncthreads();
+    if (A.X)     // (uniform) the series leaves in whole rows, coalesced
+      for (int e = tid; e < rows * nobs; e += SERIES_THREADS) {
+        const int r = e / nobs, i = e - r * nobs;
+        A.X[(row0 + r) * A.ldx + i] = tile[r * Lp + i];
+      }
+    if (!A.D) continue;   // (uniform)
+    // summed as elfihip_dist_rows sums a row of that length: left to right by the lane of the simulation, or, from
+    // kMaxTileM + 1 values on, by the whole wavefront with lane-strided partial sums and its butterfly (as gnk.hip)
+    if (nobs <= kMaxTileM) {
+      if (tid < rows) {
+        double acc = Euclid::init();
+        for (int j = 0; j < nobs; ++j) acc = Euclid::step(acc, tile[tid * Lp + j], A.dobs[j], 1.0, 2.0);
+        A.D[row0 + tid] = Euclid::finish(acc, 0.5);
+      }
+    } else {
+      for (int r = 0; r < rows; ++r) {
+        double acc = Euclid::init();
+        for (int j = tid; j < nobs; j += SERIES_THREADS) acc = Euclid::step(acc, tile[r * Lp + j], A.dobs[j], 1.0, 2.0);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc = Euclid::combine(acc, __shfl_xor(acc, off, 64));
+        if (tid == 0) A.D[row0 + r] = Euclid::finish(acc, 0.5);
+      }
     }
   }
 }
@@ -479,6 +566,42 @@ static int arch_dev_impl(elfihip_ctx* ctx, const double* dW, int64_t ldw, uint64
   return launch_status(ctx, "arch_kernel");
 }
 
+static int ar1_dev_impl(elfihip_ctx* ctx, const double* dW, int64_t ldw, uint64_t seed, uint64_t stream, int64_t n, int n_obs,
+                        const double* dphi, const double* obs, double* dX, int64_t ldx, double* dD) {
+  ELFIHIP_REQUIRE(ctx, n >= 0 && n_obs >= 1, "bad shape n=%lld n_obs=%d (at least 1)", (long long)n, n_obs);
+  ELFIHIP_REQUIRE(ctx, n_obs <= ELFIHIP_SERIES_MAX_OBS, "series of %d observations: at most %d", n_obs, ELFIHIP_SERIES_MAX_OBS);
+  ELFIHIP_REQUIRE(ctx, (!dW || ldw >= n_obs + 1) && (!dX || ldx >= n_obs), "leading dimension below the row length");
+  ELFIHIP_REQUIRE(ctx, !dD || obs, "a distance needs the observed series");
+  ELFIHIP_REQUIRE(ctx, n == 0 || dphi, "NULL data pointer");
+  if (n == 0) return ELFIHIP_OK;
+  Ar1Args A;
+  A.W = dW;
+  A.ldw = ldw;
+  A.seed = seed;
+  A.stream = stream;
+  A.phi = dphi;
+  A.n = n;
+  A.n_obs = n_obs;
+  A.Lp = (n_obs + 1) | 1;
+  A.X = dX;
+  A.ldx = ldx;
+  A.D = dD;
+  A.dobs = nullptr;
+  if (dD) {   // the observed series goes to the device on the stream
+    ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve((size_t)n_obs * sizeof(double)));
+    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(ctx->par.p, obs, (size_t)n_obs * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    A.dobs = ctx->par.as<double>();
+  }
+  const size_t row_bytes = (size_t)A.Lp * sizeof(double);
+  A.rows = tile_rows(row_bytes);
+  ELFIHIP_REQUIRE(ctx, A.rows >= 1, "series of %d observations do not fit the LDS tile", n_obs);
+  const size_t bytes = (size_t)A.rows * row_bytes;
+  const unsigned grid = series_grid(ctx, n, A.rows, bytes);
+  ELFIHIP_TRY(set_lds(ctx, ar1_kernel, bytes));
+  hipLaunchKernelGGL(ar1_kernel, dim3(grid), dim3(SERIES_THREADS), bytes, ctx->stream, A);
+  return launch_status(ctx, "ar1_kernel");
+}
+
 static int mg1_dev_impl(elfihip_ctx* ctx, const double* dE, int64_t lde, const double* dV, int64_t ldv, uint64_t seed,
                         uint64_t stream, int64_t n, int n_obs, const double* dt1, const double* dt2, const double* dt3, int nq,
                         const int* lo, const int* hi, const double* t, const double* obs, const double* w, double* dLogY,
@@ -638,6 +761,38 @@ int elfihip_arch_summaries(elfihip_ctx* ctx, const double* W, uint64_t seed, uin
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(S, dS, ns * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (Y) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Y, dY, ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ELFIHIP_OK;
+}
+
+int elfihip_ar1_series_dev(elfihip_ctx* ctx, const double* dW, int64_t ldw, uint64_t seed, uint64_t stream, int64_t n,
+                           int n_obs, const double* dphi, const double* obs, double* dX, int64_t ldx, double* dD) {
+  if (!ctx) return fail(nullptr, ELFIHIP_ERR_ARG, "ctx is NULL");
+  DeviceGuard g(ctx->device);
+  return ar1_dev_impl(ctx, dW, ldw, seed, stream, n, n_obs, dphi, obs, dX, ldx, dD);
+}
+
+int elfihip_ar1_series(elfihip_ctx* ctx, const double* W, uint64_t seed, uint64_t stream, int64_t n, int n_obs,
+                       const double* phi, const double* obs, double* X, double* D) {
+  if (!ctx) return fail(nullptr, ELFIHIP_ERR_ARG, "ctx is NULL");
+  ELFIHIP_REQUIRE(ctx, n >= 0 && n_obs >= 1 && n_obs <= ELFIHIP_SERIES_MAX_OBS, "bad shape n=%lld n_obs=%d", (long long)n, n_obs);
+  ELFIHIP_REQUIRE(ctx, n == 0 || phi, "NULL data pointer");
+  ELFIHIP_REQUIRE(ctx, !D || obs, "a distance needs the observed series");
+  if (n == 0) return ELFIHIP_OK;
+  DeviceGuard g(ctx->device);
+  const int L = n_obs + 1;
+  const size_t nw = W ? (size_t)n * L : 0, nx = X ? (size_t)n * n_obs : 0;
+  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((nw + (size_t)n) * sizeof(double)));
+  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(((size_t)n + nx) * sizeof(double)));
+  double* dW = ctx->in.as<double>();
+  double* dphi = dW + nw;
+  double* dD = ctx->out.as<double>();
+  double* dX = dD + n;
+  if (W) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dW, W, nw * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dphi, phi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  ELFIHIP_TRY(ar1_dev_impl(ctx, W ? dW : nullptr, L, seed, stream, n, n_obs, dphi, obs, X ? dX : nullptr, n_obs, D ? dD : nullptr));
+  if (X) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(X, dX, nx * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ELFIHIP_OK;
 }

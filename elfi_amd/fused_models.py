@@ -12,6 +12,8 @@
     m = elfi_amd.fused_models.daycare_model(seed_obs=4)               # elfi.examples.daycare.get_model(...)
     m = elfi_amd.fused_models.toad_model(seed_obs=4)                  # elfi.examples.toad.get_model(...)
     m = elfi_amd.fused_models.sv_model(n_obs=50, seed_obs=4)          # elfi.examples.stochastic_volatility_model.get_model(...)
+    m = elfi_amd.fused_models.bdm_model()                             # elfi.examples.bdm.get_model(...), no executable
+    m = elfi_amd.fused_models.ar1_model(n_obs=200, seed_obs=4)        # elfi.examples.ar1.get_model(...)
     elfi_amd.HipRejection(m['d'], batch_size=10**6, seed=1).sample(1000, n_sim=10**8)
 
 The reference's Simulator node draws the series on the host (MA2: random_state.randn(batch, n_obs + 2),
@@ -93,6 +95,19 @@ returns, kurt, skew; the Summary nodes returns, kurt and skew slice its columns.
 for bit, on the returns the summaries are; each shock is within twice its first-order bound of SciPy's expression in NumPy
 (tests/test_sv.py, tests/test_sv_gpu.py).  An invalid parameter row is NaN, where SciPy raises for the whole batch.
 
+bdm_model is the birth-death-mutation example (elfi/examples/bdm.py: the model of Lintusaari et al. 2017, the reference's
+showcase for elfi.tools.external_operation -- a text file, a `bdm` executable compiled by hand and two deleted files per batch)
+on csrc/bdm.hip: a jump chain of a few dozen to a thousand events, one wavefront per simulation.  Its Simulator node BDM
+returns the (batch, N) clusters as int16, T1 is the reference's own function on them, d is elfi.Distance over
+HipDistance('minkowski', p=1).  On the replayed uniforms of the reference binary the clusters are its clusters
+(tests/test_bdm.py, tests/test_bdm_gpu.py).  Two differences: the parameters are not rounded to 4 decimals on the way (the
+reference's text file does), and with seed_obs given or N != 20 the observed data are one DEVICE simulation where the
+reference calls its binary.
+
+ar1_model is the AR(1) example (elfi/examples/ar1.py) on csrc/series.hip, a lane per simulation like arch_model; its
+Simulator node AR1 returns the (batch, n_obs) series, bit for bit the reference's on given noise (tests/test_ar1_gpu.py), and d
+is elfi.Distance over HipDistance('euclidean') on it.
+
 The draws are the device generator's, not MT19937's: a run of this model is a different (equally valid) random
 realisation than a run of elfi.examples.*.get_model with the same seed; the arithmetic on given draws is bit-identical
 to the reference's (tests/test_summaries_gpu.py, tests/test_gauss_gpu.py).
@@ -113,6 +128,7 @@ from .summaries import DAYCARE_NAMES, daycare_distance, daycare_summaries
 from .summaries import TOAD_LAGS, toad_summaries
 from .summaries import sv_summaries
 from .summaries import scratch_assay_summaries
+from .summaries import ar1_series, bdm_clusters
 
 
 def _elfi():
@@ -667,6 +683,71 @@ def scratch_assay_model(true_params=None, init_arr=None, init_params=None, seed_
     num_ds = m['sums'].observed.size - 1
     weis = np.concatenate((np.ones(num_ds) / num_ds, np.array([1]))) / np.sum(init) ** 2
     elfi.Distance(HipDistance('euclidean', w=weis), m['sums'], name='d')
+    return m
+
+
+def bdm_rows(alpha, delta, tau, N, batch_size=1, random_state=None, max_events=1 << 16):
+    """Simulator operation: (batch, N) int16 cluster sizes of birth-death-mutation processes run on the device, the shape and
+    dtype of the reference's node (which parses its executable's output with np.loadtxt(dtype='int16'))."""
+    N = int(np.asarray(N).reshape(-1)[0])
+    alpha, delta, tau = _per_simulation(batch_size, alpha, delta, tau)
+    return bdm_clusters(alpha, delta, tau, N=N, mode=1, max_events=max_events, seed=_seed_of(random_state),
+                        stream=SIMULATOR_STREAM_BASE).astype(np.int16)
+
+
+def bdm_model(alpha=0.2, delta=0, tau=0.198, N=20, seed_obs=None, max_events=1 << 16, device_priors=True):
+    """elfi.examples.bdm.get_model(alpha, delta, tau, N, seed_obs) with the simulation on the device; nodes alpha, BDM, T1,
+    d.  No `bdm` executable, no files, no warning.  The node BDM returns the (batch, N) clusters as int16, T1 is the
+    reference's own T1 on them, d is elfi.Distance over HipDistance('minkowski', p=1).  With seed_obs None and N == 20 the
+    observed data are the clusters of Lintusaari et al. that the reference hard-codes; otherwise they are ONE device simulation
+    at (alpha, delta, tau) with seed seed_obs, where the reference would call its binary: a different, equally valid
+    realisation.  The parameters reach the simulator as they are; the reference rounds them to 4 decimals in its text file.  A
+    simulation is cut off after max_events events (the reference has no bound).  device_priors: the uniform prior draws on the
+    device (elfi_amd.priors.uniform)."""
+    N = int(N)
+    elfi = _elfi()
+    from elfi.examples import bdm
+    from . import priors
+    if seed_obs is None and N == 20:
+        y = np.zeros(N, dtype='int16')
+        data = np.array([6, 3, 2, 2, 1, 1, 1, 1, 1, 1, 1], dtype='int16')
+        y[0:len(data)] = data
+    else:
+        y = bdm_rows(alpha, delta, tau, N, random_state=np.random.RandomState(seed_obs), max_events=max_events)
+    m = elfi.ElfiModel(name='bdm')
+    uniform = priors.uniform if device_priors else 'uniform'
+    elfi.Prior(uniform, .005, 2, model=m, name='alpha')
+    elfi.Simulator(partial(bdm_rows, max_events=max_events), m['alpha'], delta, tau, N, observed=y, name='BDM')
+    elfi.Summary(bdm.T1, m['BDM'], name='T1')
+    elfi.Distance(HipDistance('minkowski', p=1), m['T1'], name='d')
+    return m
+
+
+def ar1_rows(phi, n_obs=200, batch_size=1, random_state=None):
+    """Simulator operation: (batch, n_obs) AR(1) series drawn and chained on the device."""
+    phi, = _per_simulation(batch_size, phi)
+    return ar1_series(phi, n_obs=n_obs, seed=_seed_of(random_state), stream=SIMULATOR_STREAM_BASE)
+
+
+def ar1_model(n_obs=200, true_params=None, seed_obs=None, device_priors=True):
+    """elfi.examples.ar1.get_model(n_obs, true_params, seed_obs) with the simulation on the device; nodes phi, AR1, d.  The
+    node AR1 returns the (batch, n_obs) series and d is elfi.Distance over HipDistance('euclidean') on it.  The observed series
+    is the reference's own AR1 with RandomState(seed_obs).  device_priors: the uniform prior draws on the device
+    (elfi_amd.priors.uniform)."""
+    if true_params is None:
+        true_params = [.9]
+    if len(true_params) != 1:
+        raise ValueError('true_params must be [phi]')
+    n_obs = int(n_obs)
+    elfi = _elfi()
+    from elfi.examples import ar1
+    from . import priors
+    y = ar1.AR1(*true_params, n_obs=n_obs, random_state=np.random.RandomState(seed_obs))
+    m = elfi.ElfiModel()
+    uniform = priors.uniform if device_priors else 'uniform'
+    elfi.Prior(uniform, -1, 2, model=m, name='phi')
+    elfi.Simulator(partial(ar1_rows, n_obs=n_obs), m['phi'], observed=y, name='AR1')
+    elfi.Distance(HipDistance('euclidean'), m['AR1'], name='d')
     return m
 
 

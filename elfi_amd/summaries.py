@@ -27,6 +27,9 @@ leading dimension of 1 -- elfi/model/elfi_model.py:915-943, elfi/compiler.py:94-
                          centre [+ distance]; daycare_distance(...) its sorted L1 distance      elfi/examples/daycare.py
     scratch_assay_summaries(...)  the scratch-assay example: the lattice walk of up to 1024 cells, its 145 summaries
                                                                                   elfi/examples/scratch_assay.py
+    bdm_clusters(...)    the birth-death-mutation example: the jump chain of up to 4096 clusters, T1, T2 [+ distance] -- no
+                         executable, no files                                          elfi/examples/bdm.py, cpp/bdm.cpp
+    ar1_series(...)      the AR(1) example: the series [+ the euclidean distance on it]          elfi/examples/ar1.py
 
     S1 = elfi.Summary(elfi_amd.autocov, Y);  S2 = elfi.Summary(elfi_amd.autocov, Y, 2)
 
@@ -217,6 +220,42 @@ def arch_summaries(t1, t2, n_obs=100, n_lags=5, noise=None, seed=0, stream=0, ob
     ctx.call("elfihip_arch_summaries", _lib.ptr(noise), C.c_uint64(int(seed)), C.c_uint64(int(stream)), n, n_obs, n_lags,
              _lib.ptr(t1), _lib.ptr(t2), _lib.ptr(obs), _lib.ptr(S), _lib.ptr(Y), _lib.ptr(D))
     return tuple(a for a in (S, Y, D) if a is not None) if (return_series or obs is not None) else S
+
+
+def ar1_series(phi, n_obs=200, noise=None, seed=0, stream=0, observed=None, ctx=None):
+    """The AR(1) example (elfi/examples/ar1.py) as ONE device operation: x_0 = 0, x_i = phi x_{i-1} + w_i, i = 1 .. n_obs, the
+    product rounded before the sum as NumPy does.
+
+    phi: (batch,) or a scalar; NaN and infinite values propagate as NumPy's do.  noise: (batch, n_obs + 1) standard normals,
+    the reference's `randn(batch, n_obs + 1)` with its unused column 0 (any other shape is a ValueError) -- the series is then
+    bit-identical to the reference's; noise=None draws on the device (Philox4x32-10 keyed by `seed`, counter stream `stream`:
+    element e of the row-major matrix is normal number e).  observed: the observed series (n_obs values); with it the
+    euclidean distance of every row, bit-identical to elfi_amd's row distance on the series, is returned too.
+    Returns X (batch, n_obs) [, d (batch,)]."""
+    n_obs = int(n_obs)
+    if not 1 <= n_obs <= SERIES_MAX_OBS:
+        raise ValueError('n_obs must be in [1, %d]' % SERIES_MAX_OBS)
+    if noise is not None:
+        noise = np.asarray(noise)
+        if noise.ndim != 2 or noise.shape[1] != n_obs + 1:
+            raise ValueError('noise must be (batch, n_obs + 1) = (batch, %d)' % (n_obs + 1))
+    n = noise.shape[0] if noise is not None else _batch_of(phi)
+    if n < 1:
+        raise ValueError('need at least one simulation')
+    phi, = _params(n, phi)
+    obs = None
+    if observed is not None:
+        obs = np.ascontiguousarray(np.asarray(observed, dtype=np.float64).reshape(-1))
+        if obs.shape[0] != n_obs:
+            raise ValueError('observed must hold the %d observed values' % n_obs)
+    if noise is not None:
+        noise = np.ascontiguousarray(noise, dtype=np.float64)
+    X = np.empty((n, n_obs))
+    D = np.empty(n) if obs is not None else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_ar1_series", _lib.ptr(noise), C.c_uint64(int(seed)), C.c_uint64(int(stream)), n, n_obs, _lib.ptr(phi),
+             _lib.ptr(obs), _lib.ptr(X), _lib.ptr(D))
+    return (X, D) if D is not None else X
 
 
 def quantile_positions(q, n):
@@ -1052,3 +1091,82 @@ def scratch_assay_summaries(pm, pp, init_arr, obs_period=12, obs_interval=1 / 12
         frames = np.ascontiguousarray(bits.reshape(n, n_obs + 1, nrows, ncols).transpose(0, 2, 3, 1))
     out = tuple(a for a in (S, frames, status, events) if a is not None)
     return out if len(out) > 1 else S
+
+
+# ---- the birth-death-mutation example model (csrc/bdm.hip) ----------------------------------------------------------------
+BDM_MAX_N = 4096                                          # include/elfihip.h: ELFIHIP_BDM_MAX_N
+BDM_MAX_EVENTS = 1 << 30                                  # ELFIHIP_BDM_MAX_EVENTS
+BDM_STATUS = ('reached_n', 'extinct', 'out_of_events', 'invalid')     # ELFIHIP_BDM_REACHED_N ...
+
+
+def bdm_draws(n, n_events, seed=0, stream=0, first_index=0, ctx=None):
+    """U (n, 2 n_events): the uniforms the drawn form of bdm_clusters uses for events 1 .. n_events of simulations first_index
+    .. first_index + n - 1 -- column 2 (k - 1) chooses the event, the next one the cluster; Philox counter (i << 32) | k of
+    (seed, stream).  Handing them back as draws=U reproduces the drawn form bit for bit."""
+    n, n_events = int(n), int(n_events)
+    if n < 1 or not 1 <= n_events <= BDM_MAX_EVENTS:
+        raise ValueError('need n >= 1 and 1 <= n_events <= 2^30')
+    first_index = _lv_index_range(first_index, n)
+    U = np.empty((n, 2 * n_events))
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_bdm_draws", C.c_uint64(int(seed)), C.c_uint64(int(stream)), first_index, n, n_events, _lib.ptr(U))
+    return U
+
+
+def bdm_clusters(alpha, delta=0., tau=0.198, N=20, mode=1, max_events=1 << 16, draws=None, seed=0, stream=0, first_index=0,
+                 observed=None, t2_n=None, return_summaries=False, return_status=False, ctx=None):
+    """The birth-death-mutation example (elfi/examples/bdm.py and its cpp/bdm.cpp) as ONE device operation: the jump chain
+    of births (rate alpha), deaths (delta) and mutations (tau) from one individual until the population reaches N, its
+    cluster sizes and the summaries T1 and T2.  include/elfihip.h (elfihip_bdm_clusters) states every operation.  No
+    executable, no files; the parameters are NOT rounded to 4 decimals as the reference's text file does.
+
+    alpha, delta, tau: (batch,) or scalars.  N: 1 .. 4096, the length of the cluster vector.  mode 1 (the example's): stop
+    just before the population would exceed N (Stadler 2011); mode 0: stop on reaching N (Tanaka et al. 2006).  draws: U
+    (batch, 2 n_events) uniforms in [0, 1), columns 2 (k - 1) and 2 (k - 1) + 1 for event k; they bound the events (max_events
+    is then n_events); one that is NaN or outside [0, 1) ends its own simulation with status 3.  draws=None draws on the
+    device: event k of simulation i reads Philox counter ((first_index + i) << 32) | k of (seed, stream), so a simulation
+    does not depend on the batch it runs in.  A simulation still running after max_events events is cut off: clusters as
+    they stand, NaN summaries (status 2; the reference has no bound, and never returns with alpha = delta = 0).  An extinct
+    population (status 1) has clusters 0, T1 NaN and T2 1, as NumPy gives.  Invalid rates (NaN, negative, infinite, or all
+    zero) give zero clusters and NaN summaries (status 3).
+    t2_n: the divisor of T2 (None: N, the reference's default of 20 at the example's N).  observed: the observed T1; with it
+    the example's distance |T1 - observed| is returned too.
+    Returns clusters (batch, N) int32 [, T (batch, 2): T1, T2] [, status (batch,) int32, events (batch,) int64] [, d
+    (batch,)] -- the bare array when nothing else is asked for."""
+    N, mode, max_events = int(N), int(mode), int(max_events)
+    if not 1 <= N <= BDM_MAX_N:
+        raise ValueError('N must be in [1, %d]' % BDM_MAX_N)
+    if mode not in (0, 1):
+        raise ValueError('mode must be 0 (stop on reaching N) or 1 (stop before exceeding N)')
+    U = None
+    if draws is not None:
+        U = np.asarray(draws)
+        if U.ndim != 2 or U.shape[1] < 2 or U.shape[1] % 2:
+            raise ValueError('draws must be (batch, 2 n_events)')
+        max_events = U.shape[1] // 2
+    if not 1 <= max_events <= BDM_MAX_EVENTS:
+        raise ValueError('max_events must be in [1, 2^30]')
+    n = U.shape[0] if U is not None else _batch_of(alpha, delta, tau)
+    if n < 1:
+        raise ValueError('need at least one simulation')
+    first_index = _lv_index_range(first_index, n)
+    alpha, delta, tau = _params(n, alpha, delta, tau)
+    t2_n = float(N if t2_n is None else t2_n)
+    obs = None
+    if observed is not None:
+        obs = np.ascontiguousarray(np.asarray(observed, dtype=np.float64).reshape(-1))
+        if obs.shape[0] != 1:
+            raise ValueError('observed must hold the one observed summary T1')
+    if U is not None:
+        U = np.ascontiguousarray(U, dtype=np.float64)
+    Cl = np.empty((n, N), dtype=np.int32)
+    T = np.empty((n, 2)) if return_summaries else None
+    status = np.empty(n, dtype=np.int32) if return_status else None
+    events = np.empty(n, dtype=np.int64) if return_status else None
+    D = np.empty(n) if obs is not None else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_bdm_clusters", _lib.ptr(U), C.c_uint64(int(seed)), C.c_uint64(int(stream)), first_index, n, N, mode,
+             max_events, _lib.ptr(alpha), _lib.ptr(delta), _lib.ptr(tau), C.c_double(t2_n), _lib.ptr(obs), _lib.ptr(Cl),
+             _lib.ptr(status), _lib.ptr(events), _lib.ptr(T), _lib.ptr(D))
+    out = tuple(a for a in (Cl, T, status, events, D) if a is not None)
+    return out if len(out) > 1 else Cl

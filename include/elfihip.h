@@ -573,6 +573,16 @@ int elfihip_arch_summaries(elfihip_ctx* ctx, const double* W, uint64_t seed, uin
 int elfihip_arch_summaries_dev(elfihip_ctx* ctx, const double* dW, int64_t ldw, uint64_t seed, uint64_t stream, int64_t n,
                                int n_obs, int n_lags, const double* dt1, const double* dt2, const double* obs, double* dS,
                                int64_t lds, double* dY, int64_t ldy, double* dD);
+/* AR(1) (elfi/examples/ar1.py): W (n, n_obs + 1) standard normals, the reference's randn(batch, n_obs + 1) -- column 0 is
+ * drawn and unused, as there; W == NULL: element e of the row-major matrix is normal number e of (seed, stream).  x_0 = 0,
+ * x_i = phi x_{i-1} + w_i for i = 1 .. n_obs: the product is rounded, then the sum (contraction off).  NaN and infinite phi
+ * propagate as NumPy's do (inf * 0 = NaN at i = 1).  X (n, n_obs): the series x_1 .. x_n_obs.  D (n): euclidean distance of
+ * the row of X to obs (n_obs host values), bit-identical to elfihip_dist_rows 'euclidean' on X.  X and D may each be NULL.
+ * 1 <= n_obs <= ELFIHIP_SERIES_MAX_OBS, n >= 0; anything else is ELFIHIP_ERR_ARG, and so is a distance without obs. */
+int elfihip_ar1_series(elfihip_ctx* ctx, const double* W, uint64_t seed, uint64_t stream, int64_t n, int n_obs,
+                       const double* phi, const double* obs, double* X, double* D);
+int elfihip_ar1_series_dev(elfihip_ctx* ctx, const double* dW, int64_t ldw, uint64_t seed, uint64_t stream, int64_t n,
+                           int n_obs, const double* dphi, const double* obs, double* dX, int64_t ldx, double* dD);
 /* M/G/1 (elfi/examples/mg1.py): E (n, n_obs) standard exponentials and V (n, n_obs) uniforms in [0, 1) -- the reference's
  * standard_exponential((n_obs, batch)) and random_sample((n_obs, batch)), transposed; both NULL: E_e = -log u with u the
  * 53-bit uniform in (0, 1] made of word e of (seed, stream) (the word + 1, as the normals' radius takes it), V_e = word e of
@@ -850,6 +860,63 @@ int elfihip_assay_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_
                         const int32_t* num_cells, int32_t* C, double* P, uint8_t* M);
 int elfihip_assay_draws_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int n_iter, int cells,
                             const int32_t* dnum_cells, int32_t* dC, double* dP, uint8_t* dM);
+
+/* The birth-death-mutation example (elfi/examples/bdm.py, the process of Tanaka et al. 2006 as the reference's cpp/bdm.cpp
+ * evaluates it; the NumPy statement is tests/bdm_ref.py): a jump chain of a few dozen to about a thousand events per
+ * simulation, two uniforms per event, one wavefront per simulation (csrc/bdm.hip).  No executable, no files.
+ * Per simulation: alpha, delta, tau (n each: birth, death and mutation rate) and the host scalars N and mode.
+ *   State.  clusters[0 .. N) unsigned counts, clusters[0] = 1; pop = 1, cluster_end = 1; cap = N + (mode == 1).
+ *   Rates.  FMA contraction off: c0 = 0.0 + alpha, c1 = c0 + delta, c2 = c1 + tau, tot = c2.
+ *   Loop.  While 0 < pop < cap, event k = 1, 2, .. takes two uniforms ue_k, uc_k in [0, 1):
+ *     event = the first i with c_i > ue_k tot; cluster = the first i < cluster_end with
+ *     (double)(clusters[0] + .. + clusters[i]) > uc_k (double)pop (the cumulative sum is an integer).
+ *     event 0: clusters[cluster] += 1, pop += 1.  event 1: clusters[cluster] -= 1, pop -= 1.
+ *     event 2, only if clusters[cluster] > 1: clusters[cluster] -= 1, the first j in [0, N) with clusters[j] == 0 becomes 1 and
+ *     cluster_end = max(cluster_end, j + 1).  Event 2 on a singleton changes nothing, but counts as an event and uses both draws.
+ *   Undo.  mode 1 (Stadler's stopping rule, the one the ELFI model uses) stops when the population WOULD exceed N: the birth
+ *     that reached cap is taken back.  mode 0 stops on reaching N.
+ *   A search that finds no index -- impossible for valid rates and uniforms below 1, u tot < tot and u pop < pop in fp64 -- takes
+ *   its last candidate (event 2, cluster cluster_end - 1); nothing is ever indexed outside [0, N).
+ * Randomness.  Given form: U (n, 2 max_events) doubles, column 2 (k - 1) is ue_k and the next uc_k.  Every uniform is checked
+ * before anything is indexed by it: one that is NaN or outside [0, 1) ends ITS simulation with status INVALID (events = the
+ * events completed before it); no other simulation changes.  Drawn form (U == NULL): event k of simulation i reads Philox4x32-10
+ * counter ((first + i) << 32) | k of (seed, stream), in philox.hpp's layout (counter words k, first + i, stream low, stream
+ * high; key seed):  ue_k = ((w0 << 21) | (w1 >> 11)) 2^-53,  uc_k = ((w2 << 21) | (w3 >> 11)) 2^-53.
+ * elfihip_bdm_draws writes these into memory, U (n, 2 n_events): the drawn form IS the given form on them.  A simulation's
+ * result depends only on its own parameters, (seed, stream, first + i), N and mode: not on n, the grid, max_events short of
+ * reaching it, or the wavefront that ran it.
+ * status (n) int32, events (n) int64 (the events made):
+ *   ELFIHIP_BDM_REACHED_N 0      the population reached N: normal outputs
+ *   ELFIHIP_BDM_EXTINCT 1        pop reached 0: clusters all 0, T1 = 0 / 0 = NaN and T2 = 1, as NumPy gives
+ *   ELFIHIP_BDM_OUT_OF_EVENTS 2  max_events used up: clusters as they stand (no undo), both summaries and the distance NaN
+ *                                (the reference has no bound and with alpha = delta = 0 never returns)
+ *   ELFIHIP_BDM_INVALID 3        a rate NaN, negative or infinite, tot zero or infinite, or a bad given uniform: clusters 0,
+ *                                summaries and distance NaN; 0 events for bad rates
+ * Outputs, each may be NULL.  Cl (n, N) int32.  T (n, 2): T1 = count(clusters > 0) / sum(clusters), one fp64 division of two
+ * exact integers; T2 = 1 - sum((clusters / t2_n)^2): divide, square, then NumPy's pairwise sum over the N terms -- bit-identical
+ * to the reference's T2(clusters, n=t2_n).  D (n): |T1 - obs[0]|, the example's minkowski p = 1 on one summary, bit-identical to
+ * elfihip_dist_rows on that column; obs is a HOST pointer to one double in both forms.
+ * Limits: 1 <= N <= ELFIHIP_BDM_MAX_N, mode 0 or 1, 1 <= max_events <= ELFIHIP_BDM_MAX_EVENTS, n >= 1, first >= 0 and
+ * first + n <= 2^32; anything else is ELFIHIP_ERR_ARG, and so is a distance without obs.  (The reference's
+ * cpp/example_input.txt runs N = 10000: a third level of the search tree would carry it.)
+ * Host forms: contiguous host arrays, synchronise.  _dev forms: device pointers, U, Cl and T with the caller's leading dimension
+ * (ldu >= 2 max_events in doubles, ldc >= N in int32, ldt >= 2 in doubles), no synchronisation. */
+#define ELFIHIP_BDM_MAX_N 4096
+#define ELFIHIP_BDM_MAX_EVENTS (1 << 30)
+#define ELFIHIP_BDM_REACHED_N 0
+#define ELFIHIP_BDM_EXTINCT 1
+#define ELFIHIP_BDM_OUT_OF_EVENTS 2
+#define ELFIHIP_BDM_INVALID 3
+int elfihip_bdm_clusters(elfihip_ctx* ctx, const double* U, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int N,
+                         int mode, int64_t max_events, const double* alpha, const double* delta, const double* tau, double t2_n,
+                         const double* obs, int32_t* Cl, int32_t* status, int64_t* events, double* T, double* D);
+int elfihip_bdm_clusters_dev(elfihip_ctx* ctx, const double* dU, int64_t ldu, uint64_t seed, uint64_t stream, int64_t first,
+                             int64_t n, int N, int mode, int64_t max_events, const double* dalpha, const double* ddelta,
+                             const double* dtau, double t2_n, const double* obs, int32_t* dCl, int64_t ldc, int32_t* dstatus,
+                             int64_t* devents, double* dT, int64_t ldt, double* dD);
+int elfihip_bdm_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int64_t n_events, double* U);
+int elfihip_bdm_draws_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int64_t n_events,
+                          double* dU, int64_t ldu);
 
 /* Symmetric (beta = 0) alpha-stable variates, S1 parameterisation: the Chambers-Mallows-Stuck transform as SciPy 1.15's
  * levy_stable.rvs evaluates it (_rvs_Z1), in SciPy's order of operations, FMA contraction off (csrc/stable.hpp; the NumPy
