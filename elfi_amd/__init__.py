@@ -56,6 +56,7 @@ from .bolfire import HipBOLFIRE, HipBOLFIREPosterior, hip_bolfire_class  # noqa:
 from .twostage import (HipTwoStageSelection, hip_two_stage_selection_class, knn_entropy, mrsse,  # noqa: F401
                        subset_best)
 from .adjust import HipLinearAdjustment, adjust_posterior, hip_linear_adjustment_class, linear_adjust  # noqa: F401
+from .kliep import HipDensityRatioEstimation, hip_density_ratio_class, kliep_fit, kliep_ratio  # noqa: F401
 
 
 

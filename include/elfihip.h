@@ -372,6 +372,44 @@ int elfihip_semi_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64
                             const int64_t* prefixes, int K, const double* penalties, int P, double* dloglik, double* du,
                             double* drho, double* dscores);
 
+/* KLIEP density-ratio estimation (elfi/methods/density_ratio_estimation.py: fit, _KLIEP :183-202, _KLIEP_lcv :157-181) of
+ * numerator rows x (Nx, d), pitch ldx, against denominator rows y (Ny, d), pitch ldy, for S basis scales in one call; with
+ * F > 0 folds also the S x F leave-fold-out fits of the likelihood cross-validation.
+ * Centres theta = x[:n]; A[i, j] = exp(-0.5 |x_i - theta_j|^2 / sigma / sigma); b_j = sum_t basis(theta_j, y_t) wy_norm[t],
+ * b_normalized = b / (b . b).  Row i is non-null when some A[i, j] > 1e-64; the filtered index of a non-null row is the
+ * number of non-null rows in front of it, L their count; fold f holds the filtered indices
+ * np.array_split(arange(L), F)[f].  Per problem (scale, held-out fold or none): alpha = 1 / n, prev = A alpha over all Nx
+ * rows; step i = 0 .. max_iter - 1: alpha += epsilon A_tr^T (w_tr / (A_tr alpha)) over the training rows (non-null, not
+ * held out), alpha = max(0, alpha + (1 - b . alpha) b_normalized), alpha /= b . alpha; when i % conv_check_interval == 0:
+ * t = A alpha over all rows, stop if |t - prev|_2 < abs_tol, else prev = t.  NaN and inf propagate as in NumPy.
+ * wx (Nx): the weights of the full fits, as the caller has them (the reference passes them unnormalised); wx_norm (Nx):
+ * the normalised weights of the fold fits and the scores (read with F > 0 only, may be NULL otherwise); wy_norm (Ny).
+ * sigmas: S scales, a host array in both forms.
+ * Outputs, each may be NULL: alpha (S, n), w (S, Nx) = A alpha of the full fit, iters (S) the index i at which its loop
+ * ended; with F > 0 scores (S, F), the weighted mean (wx_norm) of log w of the fold's fit over the held-out rows, and
+ * lcv (S), their mean over the folds -- +inf when L = 0, as the reference returns; a held-out ratio of 0 gives -inf.
+ * Limits (ELFIHIP_ERR_ARG before any launch): 1 <= d <= 64, 1 <= n <= 256, n <= Nx, Nx and Ny <= 65536, 1 <= S <= 16,
+ * 0 <= F <= 16, max_iter >= 1, conv_check_interval >= 1, every sigma positive and finite.
+ * Host form: host pointers, synchronises.  _dev form: x, y, the weights and the outputs are device pointers, no
+ * synchronisation.  Deterministic; a problem's result does not depend on S, on F or on the other problems. */
+int elfihip_kliep_fit(elfihip_ctx* ctx, const double* x, int64_t Nx, int d, int64_t ldx, const double* y, int64_t Ny,
+                      int64_t ldy, const double* wx, const double* wx_norm, const double* wy_norm, const double* sigmas,
+                      int S, int n, double epsilon, int max_iter, double abs_tol, int conv_check_interval, int F,
+                      double* alpha, double* w, int64_t* iters, double* scores, double* lcv);
+int elfihip_kliep_fit_dev(elfihip_ctx* ctx, const double* dx, int64_t Nx, int d, int64_t ldx, const double* dy, int64_t Ny,
+                          int64_t ldy, const double* dwx, const double* dwx_norm, const double* dwy_norm,
+                          const double* sigmas, int S, int n, double epsilon, int max_iter, double abs_tol,
+                          int conv_check_interval, int F, double* dalpha, double* dw, int64_t* diters, double* dscores,
+                          double* dlcv);
+
+/* The fitted ratio at M points (M, d), pitch ldp: out[i] = sum_j exp(-0.5 |p_i - c_j|^2 / sigma / sigma) alpha[j] for the
+ * n centres (n, d), pitch ldc (_weighted_basis_sum, :140-143) -- summed in the order of the fit, so the ratio at the
+ * fit's own rows has the bits of its w.  1 <= d <= 64, 1 <= n <= 256, sigma positive and finite; M = 0 does nothing. */
+int elfihip_kliep_ratio(elfihip_ctx* ctx, const double* points, int64_t M, int d, int64_t ldp, const double* centres, int n,
+                        int64_t ldc, const double* alpha, double sigma, double* out);
+int elfihip_kliep_ratio_dev(elfihip_ctx* ctx, const double* dpoints, int64_t M, int d, int64_t ldp, const double* dcentres,
+                            int n, int64_t ldc, const double* dalpha, double sigma, double* dout);
+
 /* Logistic-regression ratio estimation (the classifier of BOLFIRE; elfi/methods/classifier.py:72-121: StandardScaler,
  * then scikit-learn's LogisticRegression(penalty='l1', solver='liblinear'), then the log-odds) of G groups in one call.
  * X (G n, m) row-major with pitch ldx: the likelihood rows, label +1, group g = rows g n ... g n + n - 1.  M (nm, m) with
