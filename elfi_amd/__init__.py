@@ -57,6 +57,9 @@ from .twostage import (HipTwoStageSelection, hip_two_stage_selection_class, knn_
                        subset_best)
 from .adjust import HipLinearAdjustment, adjust_posterior, hip_linear_adjustment_class, linear_adjust  # noqa: F401
 from .kliep import HipDensityRatioEstimation, hip_density_ratio_class, kliep_fit, kliep_ratio  # noqa: F401
+from .fused_models import ma2_model  # noqa: F401
+from .romc import (HipROMC, RomcProblems, hip_romc_class, hip_romc_posterior_class, romc_count, romc_objective,  # noqa: F401
+                   romc_regions, romc_sample, romc_solve)
 
 
 

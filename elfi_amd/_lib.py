@@ -354,6 +354,29 @@ PROTOTYPES = {
     "elfihip_lbfgsb_feed": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "elfihip_lbfgsb_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "elfihip_lbfgsb_free": (C.c_int, [C.c_void_p]),
+    "elfihip_romc_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, c_void_pp]),
+    "elfihip_romc_create_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.c_void_p, c_void_pp]),
+    "elfihip_romc_free": (C.c_int, [C.c_void_p]),
+    "elfihip_romc_objective": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "elfihip_romc_objective_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "elfihip_romc_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "elfihip_romc_solve_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "elfihip_romc_regions": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_double,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "elfihip_romc_regions_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
+                                           C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "elfihip_romc_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64,
+                                      C.c_uint64, C.c_void_p, C.c_void_p]),
+    "elfihip_romc_sample_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_uint64, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "elfihip_romc_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "elfihip_romc_count_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_double, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

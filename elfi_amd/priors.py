@@ -30,9 +30,13 @@ UNIFORM, MA2_T1, MA2_T2 = 0, 1, 2
 PRIOR_STREAM_BASE = 0x5052494F52000000      # "PRIOR"; + the prior kind
 SIMULATOR_STREAM_BASE = 0x53494D0000000000  # "SIM"
 PROPOSAL_STREAM_BASE = 0x474D525653000000   # "GMRVS"; + 2 x the redraw round
+ROMC_STREAM_BASE = 0x524F4D4300000000       # "ROMC"; + the region's position in the posterior
 
 
 def _seed_of(random_state):
+    # (an integer seeds a fresh RandomState, as scipy.stats' rvs takes it: ROMC hands ModelPrior.rvs its integer seed)
+    if isinstance(random_state, (int, np.integer)) and not isinstance(random_state, bool):
+        random_state = np.random.RandomState(int(random_state))
     rs = random_state or np.random
     return int(rs.randint(0, 2 ** 31 - 1))
 

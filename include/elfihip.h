@@ -1330,6 +1330,91 @@ int elfihip_lbfgsb_feed(elfihip_lbfgsb* h, int64_t n, const double* f, const dou
 int elfihip_lbfgsb_result(const elfihip_lbfgsb* h, double* x, double* f, int* iters, int* status);
 int elfihip_lbfgsb_free(elfihip_lbfgsb* h);
 
+/* ------------------------------------------------------------------- ROMC: Robust Optimisation Monte Carlo (csrc/romc.hip)
+ * elfi.ROMC (elfi/methods/inference/romc.py; RomcPosterior, elfi/methods/posteriors.py:393-800) for the MA2 example: D = 2
+ * parameters, 3 <= n_obs <= 126.  ROMC freezes the simulator's noise into n1 deterministic objectives and evaluates them
+ * hundreds of thousands of times; here problem i's noise is one row of a matrix the handle keeps on the device, and every
+ * call below is one launch with one wavefront per problem or region.
+ *
+ * The objective.  f_i(theta) = D D, D the distance of elfihip_ma2_distance_dev for the row w_i and theta = (t1, t2):
+ *   x_k = (w[k+2] + t1 w[k+1]) + t2 w[k], S1 / S2 the lag-1 / lag-2 means in NumPy's pairwise order, FMA contraction off,
+ *   D = sqrt((S1 - obs1)^2 + (S2 - obs2)^2)
+ * -- bit for bit the square of that call's distance.  The rule is D D, not pow(D, 2): the reference's float(d) ** 2 goes
+ * through libm's pow, which differs from d d in about one value of a thousand.
+ *
+ * The handle owns the (n1, n_obs + 2) noise matrix: either the caller's W, or row i = normals 0 .. n_obs + 1 of stream
+ * (seeds[i], streams[i]) of elfihip_randn_dev, i.e. what elfihip_ma2_draw_distance_dev(seeds[i], streams[i], n = 1)
+ * simulates from.  Exactly one of W and the (seeds, streams) pair is given.  The host forms return when the work is done
+ * and answer a problem index outside [0, n1) with ELFIHIP_ERR_ARG; the _dev forms enqueue on the context's stream, return
+ * without synchronising and answer such an index with NaN (counts: the region adds nothing). */
+typedef struct elfihip_romc elfihip_romc;
+enum { ELFIHIP_ROMC_MA2 = 0 };
+#define ELFIHIP_ROMC_DIM 2
+#define ELFIHIP_ROMC_MAX_OBS 126
+#define ELFIHIP_ROMC_MAX_PROBLEMS (1 << 20)
+#define ELFIHIP_ROMC_MAX_POINTS (1 << 24)
+enum {
+  ELFIHIP_ROMC_SOLVED = 0,     /* the simplex met xatol and fatol */
+  ELFIHIP_ROMC_MAXFEV = 1,     /* SciPy's warnflag 1: the evaluation limit */
+  ELFIHIP_ROMC_MAXITER = 2,    /* SciPy's warnflag 2: the iteration limit */
+  ELFIHIP_ROMC_NONFINITE = 3   /* an objective value was NaN or infinite: the problem ended there, its outputs are NaN */
+};
+int elfihip_romc_create(elfihip_ctx* ctx, int model, int64_t n1, int n_obs, double obs1, double obs2, const double* W,
+                        const uint64_t* seeds, const uint64_t* streams, elfihip_romc** out);
+int elfihip_romc_create_dev(elfihip_ctx* ctx, int model, int64_t n1, int n_obs, double obs1, double obs2, const double* dW,
+                            int64_t ldw, const uint64_t* dseeds, const uint64_t* dstreams, elfihip_romc** out);
+int elfihip_romc_free(elfihip_romc* h);
+/* f[p] = f_{prob[p]}(theta[p]) for P pairs; theta (P, 2) (device form: pitch ldt), prob (P).  One wavefront walks the pairs
+ * of one problem. */
+int elfihip_romc_objective(elfihip_romc* h, int64_t P, const double* theta, const int64_t* prob, double* f);
+int elfihip_romc_objective_dev(elfihip_romc* h, int64_t P, const double* dtheta, int64_t ldt, const int64_t* dprob, double* df);
+/* Every problem's minimum from its start x0 (n1, 2), one wavefront per problem: SciPy's _minimize_neldermead as
+ * scipy.optimize.minimize(fun, x0, method='Nelder-Mead') runs it -- the initial simplex x0 and per coordinate x0_k 1.05 (0.00025
+ * where x0_k is zero); reflection 2 c - w, expansion 3 c - 2 w, contraction 1.5 c - 0.5 w, inside contraction 0.5 c + 0.5 w,
+ * shrink b + 0.5 (v - b) with c the centroid of all vertices but the worst w and b the best; xatol = fatol = 1e-4; an
+ * evaluation beyond maxfev is refused and ends the iteration without counting it; the sort after every iteration keeps
+ * ties in order.  SciPy's defaults are maxiter = maxfev = 200 D; a limit SciPy would leave infinite is given as INT32_MAX
+ * (the smaller of the two is at most 2^20).  status as the enum above; a value that is not finite ends the problem.
+ * At a solved point the Hessian by central second differences with the steps h_k = 2^-13 max(1, |x_k|):
+ *   H_kk = ((f(x + h_k e_k) - f0) + (f(x - h_k e_k) - f0)) / (h_k h_k),   f0 = f_min,
+ *   H_01 = H_10 = ((f(++) - f(+-)) - (f(-+) - f(--))) / ((4 h_0) h_1);
+ * NaN for a problem that was not solved.  x_min (n1, 2), f_min (n1), hess (n1, 2, 2), nfev / nit (n1) SciPy's counts (the
+ * eight evaluations of the Hessian are not in nfev). */
+int elfihip_romc_solve(elfihip_romc* h, const double* x0, int maxiter, int maxfev, double* x_min, double* f_min, double* hess,
+                       int32_t* nfev, int32_t* nit, int32_t* status);
+int elfihip_romc_solve_dev(elfihip_romc* h, const double* dx0, int64_t ldx0, int maxiter, int maxfev, double* dx_min, int64_t ldx,
+                           double* df_min, double* dhess, int32_t* dnfev, int32_t* dnit, int32_t* dstatus);
+/* The bounding boxes of R accepted problems: prob (R), centre (R, 2), hess (R, 2, 2).
+ * Rotation: a cyclic Jacobi sweep of the symmetric part a = H_00, d = H_11, b = (H_01 + H_10) 0.5 -- for b != 0:
+ *   tau = (d - a) / (2 b), t = 1 / (tau + sqrt(1 + tau tau)) for tau >= 0, else -1 / (-tau + sqrt(1 + tau tau)),
+ *   c = 1 / sqrt(1 + t t), s = t c, lambda = (a - t b, d + t b), rotation = [[c, s], [-s, c]] (columns: the eigenvectors)
+ * -- and the identity when an entry of H or an eigenvalue is not finite or min |lambda| <= max |lambda| D eps (NumPy's
+ * matrix_rank rule, which the reference's _find_rotation_vector applies).
+ * Limits: the reference's line_search (romc.py:1971-2015) operation for operation along + and - column d from the centre,
+ * one wavefront per (region, direction, side): limits (R, 2, 2) = [direction][-left offset, right offset], nfev (R, 2, 2)
+ * the evaluations of each search (at most K (rep_lim + 2)).  1 <= K <= 64, 0 <= rep_lim <= 2^20, eta > 0. */
+int elfihip_romc_regions(elfihip_romc* h, int64_t R, const int64_t* prob, const double* centre, const double* hess, double eps_region,
+                         int K, double eta, int rep_lim, double* rotation, double* limits, int32_t* nfev);
+int elfihip_romc_regions_dev(elfihip_romc* h, int64_t R, const int64_t* dprob, const double* dcentre, const double* dhess,
+                             double eps_region, int K, double eta, int rep_lim, double* drotation, double* dlimits, int32_t* dnfev);
+/* n2 points per region, uniform in its box, and the region's objective there: with u_jk the 53-bit uniform of the first two
+ * words of Philox counter 2 j + k of stream (seed, stream + r), r the region's position in the call,
+ *   t_k = u_jk (limits[r][k][1] - limits[r][k][0]) + limits[r][k][0],   theta[r][j][i] = (rot[i][0] t_0 + rot[i][1] t_1) + centre[i]
+ * theta (R, n2, 2) (device form: pitch ldth per point), f (R, n2). */
+int elfihip_romc_sample(elfihip_romc* h, int64_t R, const int64_t* prob, const double* centre, const double* rotation,
+                        const double* limits, int64_t n2, uint64_t seed, uint64_t stream, double* theta, double* f);
+int elfihip_romc_sample_dev(elfihip_romc* h, int64_t R, const int64_t* dprob, const double* dcentre, const double* drotation,
+                            const double* dlimits, int64_t n2, uint64_t seed, uint64_t stream, double* dtheta, int64_t ldth, double* df);
+/* count[b] = sum over the R regions of 1[f_{prob[r]}(theta_b) <= eps] (RomcPosterior._sum_over_indicators); with contain = 1
+ * the point must also lie in the box (_sum_over_regions_indicators, NDimBoundingBox.contains):
+ *   y_k = (ri[k][0] p_0 + ri[k][1] p_1) + (ri[k][0] (-c_0) + ri[k][1] (-c_1)),   limits[r][k][0] <= y_k <= limits[r][k][1]
+ * with ri = rotation_inv (R, 2, 2); centre, rotation_inv and limits may be NULL with contain = 0.  theta (BS, 2) (device
+ * form: pitch ldt), count (BS) int32, combined with integer atomics: the result does not depend on scheduling. */
+int elfihip_romc_count(elfihip_romc* h, int64_t BS, const double* theta, int64_t R, const int64_t* prob, double eps, int contain,
+                       const double* centre, const double* rotation_inv, const double* limits, int32_t* count);
+int elfihip_romc_count_dev(elfihip_romc* h, int64_t BS, const double* dtheta, int64_t ldt, int64_t R, const int64_t* dprob, double eps,
+                           int contain, const double* dcentre, const double* drotation_inv, const double* dlimits, int32_t* dcount);
+
 /* ------------------------------------------------------------------- multi-GPU exchange (one process per GPU)
  * Replaces the pickled returns of ELFI's batch farm (elfi/client.py:268-274; the per-batch farm-out of
  * elfi/methods/parameter_inference.py:283-292): the ranks' small per-round results travel device to device over RCCL
