@@ -50,7 +50,8 @@ from .bolfi import HipBOLFI, hip_bolfi_class  # noqa: F401
 from . import chains, fused_models, multistart, priors  # noqa: F401
 from .maxvar_acquisition import HipExpIntVar, HipMaxVar, HipRandMaxVar  # noqa: F401
 from .synlik import (HipBSL, hip_bsl_class, log_SL_stdev, robust_likelihood, select_penalty,  # noqa: F401
-                     semi_loglik, semiparametric_likelihood, standard_likelihood, syn_loglik, unbiased_likelihood)
+                     semi_loglik, semiparametric_likelihood, slice_gamma, slice_gamma_mean, slice_gamma_variance,
+                     standard_likelihood, syn_loglik, unbiased_likelihood)
 from .logratio import HipLogisticRegression, hip_logistic_regression_class, log_ratio  # noqa: F401
 from .bolfire import HipBOLFIRE, HipBOLFIREPosterior, hip_bolfire_class  # noqa: F401
 from .twostage import (HipTwoStageSelection, hip_two_stage_selection_class, knn_entropy, mrsse,  # noqa: F401

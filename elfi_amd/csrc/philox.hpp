@@ -28,6 +28,14 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   out[3] = c3;
 }
 
+// the 53-bit uniform in [0, 1) of the first two words of counter idx of stream (seed, stream): what a ROMC region's sample
+// (romc.hip) and a slice sampler's draw (slice_gamma.hip) take, one counter each
+__device__ __forceinline__ double uniform53_first(uint64_t seed, uint64_t stream, uint64_t idx) {
+  uint32_t w[4];
+  philox4x32_10((uint32_t)idx, (uint32_t)(idx >> 32), (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), w);
+  return (double)(((uint64_t)w[0] << 21) | (w[1] >> 11)) * 0x1.0p-53;
+}
+
 // standard normals number 2p and 2p+1 of stream (seed, stream)
 __device__ __forceinline__ void normal_pair(uint64_t seed, uint64_t stream, uint64_t p, double& z0, double& z1) {
   uint32_t r[4];

@@ -412,13 +412,6 @@ struct RoSampleArgs {
   double* f;       // (R, n2)
 };
 
-// the 53-bit uniform in [0, 1) of the first two words of counter idx of stream (seed, stream)
-__device__ __forceinline__ double ro_uniform53(uint64_t seed, uint64_t stream, uint64_t idx) {
-  uint32_t w[4];
-  philox4x32_10((uint32_t)idx, (uint32_t)(idx >> 32), (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), w);
-  return (double)(((uint64_t)w[0] << 21) | (w[1] >> 11)) * 0x1.0p-53;
-}
-
 __global__ __launch_bounds__(RO_THREADS) void ro_sample_kernel(RoSampleArgs A) {
   __shared__ double s_w[RO_MAX_L], s_x[RO_MAX_L];
   const int lane = threadIdx.x;
@@ -431,8 +424,8 @@ __global__ __launch_bounds__(RO_THREADS) void ro_sample_kernel(RoSampleArgs A) {
   const double l0 = A.limits[r * 4], w0 = A.limits[r * 4 + 1] - l0, l1 = A.limits[r * 4 + 2], w1 = A.limits[r * 4 + 3] - l1;
   for (int64_t base = 0; base < A.n2; base += RO_THREADS) {
     const int64_t j = base + lane;
-    const double t0 = ro_uniform53(A.seed, A.stream + (uint64_t)r, 2ull * (uint64_t)j) * w0 + l0;
-    const double t1 = ro_uniform53(A.seed, A.stream + (uint64_t)r, 2ull * (uint64_t)j + 1ull) * w1 + l1;
+    const double t0 = uniform53_first(A.seed, A.stream + (uint64_t)r, 2ull * (uint64_t)j) * w0 + l0;
+    const double t1 = uniform53_first(A.seed, A.stream + (uint64_t)r, 2ull * (uint64_t)j + 1ull) * w1 + l1;
     const double a = (r00 * t0 + r01 * t1) + c0, b = (r10 * t0 + r11 * t1) + c1;
     const int cnt = (int)(A.n2 - base < RO_THREADS ? A.n2 - base : RO_THREADS);
     double fv = NAN;

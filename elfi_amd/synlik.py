@@ -7,6 +7,7 @@
     elfi_amd.select_penalty(model, 500, theta, ['S1', 'S2'], shrinkage='warton')   # ONE call for M x 31 (the default penalties)
     semi = elfi_amd.semiparametric_likelihood()                               # semiBSL: KDE marginals + Gaussian copula
     elfi_amd.select_penalty(model, 500, theta, ['S1', 'S2'], likelihood=semi) # the same ONE call for the semiparametric form
+    bsl = elfi_amd.HipBSL(model, 500, likelihood=elfi_amd.robust_likelihood('variance'), gamma_sampler='device')   # R-BSL-V
 
 `syn_loglik` is the thin mirror of `elfihip_syn_loglik` (csrc/synlik.hip): G groups of n summary rows, K prefixes of
 every group and P Warton penalties in one launch.  The factories carry the reference's names and call signatures
@@ -17,15 +18,22 @@ semiparametric likelihood of An, Nott & Drovandi (pdf_methods.py:46-59, 179-264)
 `log_SL_stdev` / `select_penalty` (pre_sample_methods.py:102-143, 215-318) draw the same
 child seeds through `model.generate` as the reference and stack the M matrices as M groups.
 
+`slice_gamma` mirrors `elfihip_slice_gamma` (csrc/slice_gamma.hip): one slice-sampler sweep over the adjustment
+parameters gamma of G robust chains' states in one launch; `slice_gamma_mean` / `slice_gamma_variance` carry the
+reference's signatures (slice_gamma_mean.py:35, slice_gamma_variance.py:31) and leave the caller's RandomState where the
+reference's functions would; `HipBSL(..., gamma_sampler='device')` puts them into the chain.
+
 Not on the device: graphical-lasso shrinkage, the whitened semiparametric likelihood (wsemiBSL),
-estimate_whitening_matrix, the slice samplers for gamma.  They raise or stay the reference's; nothing falls back quietly.
+estimate_whitening_matrix.  They raise or stay the reference's; nothing falls back quietly.
 """
+import ctypes as C
 import sys
 from functools import partial
 
 import numpy as np
 
 from . import _lib
+from .priors import SLICE_GAMMA_STREAM_BASE
 
 MAX_FEATURES = 64
 MAX_SEMI_ROWS = 16384       # rows per group of the semiparametric likelihood: one column is held in LDS
@@ -327,6 +335,122 @@ def select_penalty(model, n_sim, theta, feature_names, likelihood=None, lmdas=No
     return np.asarray(lmdas, dtype=float)[pick], spread[np.arange(len(pick)), pick]
 
 
+# ---- the slice samplers for gamma (slice_gamma_mean.py:35-138, slice_gamma_variance.py:31-115) ------------------------
+
+_ADJUSTMENTS = {'mean': 0, 'variance': 1}
+SLICE_OK, SLICE_OUT_OF_DRAWS, SLICE_NONFINITE = 0, 1, 2
+MAX_SLICE_ITER = 1 << 20
+
+
+def slice_gamma(ssy, loglik, gamma, sample_mean, sample_cov, adjustment, tau=0.5, w=1.0, max_iter=1000, draws=None,
+                seed=None, n_groups=None, return_info=False, ctx=None):
+    """One slice-sampler sweep over the m adjustment parameters of every one of G chains' states in one device call
+    (`elfihip_slice_gamma`, csrc/slice_gamma.hip: one wavefront per chain).
+
+    gamma (G, m), loglik (G), sample_mean (G, m), sample_cov (G, m, m); ssy (G, m) or (m) for all; without the leading
+    axis (and n_groups None): one problem.  adjustment: 'mean' | 'variance'.
+    draws: (G, n_u) (or (n_u) for one problem) doubles in [0, 1), consumed in the reference's order -- one per exponential,
+    one per uniform; or seed: the device generator's (Philox stream SLICE_GAMMA_STREAM_BASE + the chain's position).
+    Returns (gamma, loglik) -- a problem that ran out of draws or met a non-finite value has NaN -- and with return_info
+    also (used, evals, status): the draws consumed, the likelihood evaluations and SLICE_OK / SLICE_OUT_OF_DRAWS /
+    SLICE_NONFINITE per problem.
+    """
+    if adjustment not in _ADJUSTMENTS:
+        raise ValueError("adjustment must be 'mean' or 'variance', not %r" % (adjustment,))
+    g_in = np.asarray(gamma, dtype=np.float64)
+    single = g_in.ndim <= 1 and n_groups is None
+    g_in = np.ascontiguousarray(np.atleast_2d(g_in))
+    if g_in.ndim != 2:
+        raise ValueError('gamma must be (m) or (G, m)')
+    G, m = g_in.shape
+    if n_groups is not None and int(n_groups) != G:
+        raise ValueError('n_groups=%d but gamma has %d rows' % (n_groups, G))
+    if m < 1 or m > MAX_FEATURES:
+        raise ValueError('%d adjustment parameters: the device kernel takes 1 to %d' % (m, MAX_FEATURES))
+    try:
+        y = np.ascontiguousarray(np.broadcast_to(np.asarray(ssy, dtype=np.float64).reshape((-1, m)), (G, m)))
+        mean = np.ascontiguousarray(np.asarray(sample_mean, dtype=np.float64).reshape((G, m)))
+        cov = np.ascontiguousarray(np.asarray(sample_cov, dtype=np.float64).reshape((G, m, m)))
+        ll = np.ascontiguousarray(np.asarray(loglik, dtype=np.float64).reshape((G,)))
+    except ValueError:
+        raise ValueError('ssy, loglik, sample_mean and sample_cov do not have the shapes of %d problems of %d '
+                         'parameters' % (G, m)) from None
+    tau, w, max_iter = float(tau), float(w), int(max_iter)
+    if not (tau > 0 and np.isfinite(tau)):
+        raise ValueError('tau must be positive')
+    if not (w > 0 and np.isfinite(w)):
+        raise ValueError('w must be positive')
+    if max_iter < 0 or max_iter > MAX_SLICE_ITER:
+        raise ValueError('max_iter=%d: 0 to %d' % (max_iter, MAX_SLICE_ITER))
+    if (draws is None) == (seed is None):
+        raise ValueError('give either draws or seed')
+    U, n_u = None, 0
+    if draws is not None:
+        U = np.asarray(draws, dtype=np.float64)
+        if U.ndim == 1 and G == 1:
+            U = U.reshape(1, -1)
+        if U.ndim != 2 or U.shape[0] != G:
+            raise ValueError('draws must be (G, n_u)')
+        U = np.ascontiguousarray(U)
+        n_u = U.shape[1]
+    g_out = np.empty((G, m), dtype=np.float64)
+    ll_out = np.empty(G, dtype=np.float64)
+    used, evals = np.empty(G, dtype=np.int64), np.empty(G, dtype=np.int64)
+    status = np.empty(G, dtype=np.int32)
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_slice_gamma", _ADJUSTMENTS[adjustment], G, m, _lib.ptr(y), _lib.ptr(mean), _lib.ptr(cov), m,
+             _lib.ptr(g_in), _lib.ptr(ll), tau, w, max_iter, _lib.ptr(U), n_u, C.c_uint64(0 if seed is None else int(seed)),
+             C.c_uint64(SLICE_GAMMA_STREAM_BASE), _lib.ptr(g_out), _lib.ptr(ll_out), _lib.ptr(used), _lib.ptr(evals),
+             _lib.ptr(status))
+    if single:
+        g_out, ll_out, used, evals, status = g_out[0], ll_out[0], int(used[0]), int(evals[0]), int(status[0])
+    return (g_out, ll_out, used, evals, status) if return_info else (g_out, ll_out)
+
+
+def _first_draws(m):
+    """Length of the first draw buffer of the drop-ins: a coordinate takes one exponential and, typically, a few uniforms."""
+    return 8 * m + 16
+
+
+def _slice_gamma_drop_in(adjustment, ssy, loglik, gamma, sample_mean, sample_cov, tau, w, max_iter, random_state):
+    """The reference's call on the device, with the caller's generator kept on the reference's sequence: the draws are a
+    buffer of its random_sample doubles, and afterwards the generator has consumed exactly the doubles the sweep used."""
+    rs = np.random if random_state is None else random_state
+    g_in = np.asarray(gamma, dtype=np.float64).reshape(-1)
+    ll_in = np.asarray(loglik, dtype=np.float64).reshape(-1)
+    if ll_in.size != 1:
+        raise ValueError('loglik must be one number')
+    saved = rs.get_state()
+    n_u, most = _first_draws(g_in.size), g_in.size * (1 + max(int(max_iter), 0))
+    while True:
+        rs.set_state(saved)
+        n_u = max(1, min(n_u, most))
+        try:
+            g_out, ll_out, used, _, status = slice_gamma(ssy, ll_in, g_in, sample_mean, sample_cov, adjustment, tau=tau, w=w,
+                                                         max_iter=max_iter, draws=rs.random_sample(n_u), return_info=True)
+        finally:
+            rs.set_state(saved)
+        if status != SLICE_OUT_OF_DRAWS or n_u >= most:
+            break
+        n_u *= 4         # the longer buffer starts with the same doubles, so the sweep repeats its steps and goes on
+    rs.random_sample(used)
+    if status != SLICE_OK:
+        raise FloatingPointError('the %s-adjustment slice sampler met a covariance without a Cholesky factor or a target '
+                                 'that is not finite' % adjustment)
+    return g_out, np.float64(ll_out)
+
+
+def slice_gamma_mean(ssy, loglik, gamma, sample_mean, sample_cov, tau=0.5, w=1.0, max_iter=1000, random_state=None):
+    """slice_gamma_mean.slice_gamma_mean on the device: (gamma, loglik) after one sweep; random_state (None: NumPy's
+    global one) ends where the reference's would."""
+    return _slice_gamma_drop_in('mean', ssy, loglik, gamma, sample_mean, sample_cov, tau, w, max_iter, random_state)
+
+
+def slice_gamma_variance(ssy, loglik, gamma, sample_mean, sample_cov, tau=0.5, w=1.0, max_iter=1000, random_state=None):
+    """slice_gamma_variance.slice_gamma_variance on the device; as slice_gamma_mean."""
+    return _slice_gamma_drop_in('variance', ssy, loglik, gamma, sample_mean, sample_cov, tau, w, max_iter, random_state)
+
+
 # ---- elfi.BSL with the device likelihood as its default ----------------------------------------------------------------
 
 def _reference_bsl():
@@ -337,8 +461,9 @@ def _reference_bsl():
 
 
 def hip_bsl_class():
-    """The subclass of the imported ELFI's BSL (made once per reference class): the loop, the proposals, the gamma
-    samplers and the BslSample are the reference's; the default likelihood is the device one."""
+    """The subclass of the imported ELFI's BSL (made once per reference class): the loop, the proposals and the BslSample
+    are the reference's; the default likelihood is the device one, and with gamma_sampler='device' a robust chain's
+    gamma sweeps are too (the default, None, keeps the reference's slice samplers)."""
     BSL = _reference_bsl()
     cls = _CLASSES.get(BSL)
     if cls is not None:
@@ -347,9 +472,23 @@ def hip_bsl_class():
     class HipBSL(BSL):
         __doc__ = hip_bsl_class.__doc__
 
-        def __init__(self, model, n_sim_round, feature_names=None, likelihood=None, **kwargs):
+        def __init__(self, model, n_sim_round, feature_names=None, likelihood=None, gamma_sampler=None, **kwargs):
+            if gamma_sampler not in (None, 'device'):
+                raise ValueError("gamma_sampler must be None (the reference's slice samplers) or 'device', not %r"
+                                 % (gamma_sampler,))
+            if gamma_sampler == 'device' and not (isinstance(likelihood, partial) and 'adjustment' in likelihood.keywords):
+                raise ValueError("gamma_sampler='device' goes with a robust likelihood (robust_likelihood('mean' | "
+                                 "'variance')): no other has adjustment parameters to sample")
             super(HipBSL, self).__init__(model, n_sim_round, feature_names=feature_names,
                                          likelihood=likelihood or standard_likelihood(), **kwargs)
+            self.gamma_sampler_choice = gamma_sampler
+
+        def _resolve_gamma_sampler(self, tau, w, max_iter):
+            sampler, gamma0 = super(HipBSL, self)._resolve_gamma_sampler(tau, w, max_iter)
+            if self.gamma_sampler_choice == 'device':
+                sampler = {'mean': slice_gamma_mean, 'variance': slice_gamma_variance}[self.likelihood.keywords['adjustment']]
+                sampler = partial(sampler, tau=tau, w=w, max_iter=max_iter, random_state=self.random_state)
+            return sampler, gamma0
 
     HipBSL.__name__ = 'HipBSL'
     HipBSL.__qualname__ = 'HipBSL'

@@ -1415,6 +1415,50 @@ int elfihip_romc_count(elfihip_romc* h, int64_t BS, const double* theta, int64_t
 int elfihip_romc_count_dev(elfihip_romc* h, int64_t BS, const double* dtheta, int64_t ldt, int64_t R, const int64_t* dprob, double eps,
                            int contain, const double* dcentre, const double* drotation_inv, const double* dlimits, int32_t* dcount);
 
+/* ------------------------------------------------------------------- R-BSL: the slice samplers for gamma
+ * Replaces slice_gamma_mean / slice_gamma_variance (elfi/methods/bsl/slice_gamma_mean.py, slice_gamma_variance.py), which
+ * elfi.BSL calls between two likelihood evaluations of a misspecification-robust chain.  G independent problems in one
+ * launch, one wavefront each; problem g is one chain's state: y (m), mean (m), cov (m, m; only the lower triangle is read,
+ * rows at pitch ldc), gamma_in (m), loglik_in.  1 <= m <= 64, 0 <= max_iter <= 2^20, tau > 0, w > 0, ldc >= m, G >= 0;
+ * anything else is ELFIHIP_ERR_ARG before any launch.  y, mean, gamma_in and gamma_out are (G, m) without pitch.
+ *
+ * Statement, with std = sqrt(diag(cov)), loglik = loglik_in, ll_curr = loglik_in; for ii = 0 .. m - 1 in order:
+ *   e = -log(1 - d) of one draw d;  g = gamma[ii];  target = (loglik + prior(gamma)) - e
+ *   mean (0):      lower = g - w, upper = g + w;  i = 0, while i <= max_iter: loglik = L(lower), stop when
+ *                  loglik + prior(gamma | ii: lower) < target, else lower = lower - w, ++i;  the same with upper, + w
+ *   variance (1):  lower = 0, upper = g + w; only the upper bound steps out
+ *   shrink:        i = 0, while i < max_iter: prop = lower + (upper - lower) d of one draw d, loglik = L(prop); when
+ *                  loglik + prior(gamma | ii: prop) > target: gamma[ii] = prop, ll_curr = loglik, stop; else prop < g moves
+ *                  lower, anything else upper, ++i
+ * `loglik` is the value of the LAST likelihood evaluated so far (after a shrink loop that used up max_iter: the last
+ * rejected trial's), as in the reference.  L(x) = -1/2 ((m log 2 pi + log det C) + r' C^-1 r) with gamma[ii] = x and
+ *   mean:      r = y - (mean + std o gamma), C = cov;     prior = m log((1 / tau) / 2) - (1 / tau) sum |gamma_i|
+ *   variance:  r = y - mean, C = cov + diag((std o gamma)^2);   prior = sum (-(gamma_i / tau) - log tau), -inf below zero
+ * evaluated from one Cholesky factorisation per call (mean) or per coordinate (variance, of C without coordinate ii's own
+ * term) and a rank-one change per trial.  FMA contraction off, every sum in a fixed order, no atomics: a problem's result
+ * does not depend on G.
+ *
+ * Draws: doubles in [0, 1), one per exponential and one per uniform, in the order above -- RandomState.exponential(1) and
+ * RandomState.uniform(lower, upper) of the double random_sample() would return.  U (G, n_u): problem g takes U[g][0],
+ * U[g][1], ...; U == NULL (n_u is not looked at): draw k is the 53-bit uniform of the first two words of Philox counter k of
+ * stream (seed, stream + g).
+ *
+ * gamma_out (G, m), loglik_out (G) = ll_curr, used (G) the draws consumed, evals (G) the likelihood evaluations, status (G):
+ * with OUT_OF_DRAWS (the buffer ended: used = n_u) and NONFINITE (a Cholesky pivot that is not positive, or a target that is
+ * not finite -- SciPy raises, or goes on with -inf, there) the problem ends, gamma_out and loglik_out are NaN; the other
+ * problems of the call are not affected, and the call gives ELFIHIP_OK.  The host form returns when the work is done; the
+ * _dev form enqueues on the context's stream and returns without synchronising. */
+enum { ELFIHIP_SLICE_MEAN = 0, ELFIHIP_SLICE_VARIANCE = 1 };
+enum { ELFIHIP_SLICE_OK = 0, ELFIHIP_SLICE_OUT_OF_DRAWS = 1, ELFIHIP_SLICE_NONFINITE = 2 };
+int elfihip_slice_gamma(elfihip_ctx* ctx, int adjustment, int64_t G, int m, const double* y, const double* mean, const double* cov,
+                        int64_t ldc, const double* gamma_in, const double* loglik_in, double tau, double w, int64_t max_iter,
+                        const double* U, int64_t n_u, uint64_t seed, uint64_t stream, double* gamma_out, double* loglik_out,
+                        int64_t* used, int64_t* evals, int32_t* status);
+int elfihip_slice_gamma_dev(elfihip_ctx* ctx, int adjustment, int64_t G, int m, const double* dy, const double* dmean,
+                            const double* dcov, int64_t ldc, const double* dgamma_in, const double* dloglik_in, double tau,
+                            double w, int64_t max_iter, const double* dU, int64_t n_u, uint64_t seed, uint64_t stream,
+                            double* dgamma_out, double* dloglik_out, int64_t* dused, int64_t* devals, int32_t* dstatus);
+
 /* ------------------------------------------------------------------- multi-GPU exchange (one process per GPU)
  * Replaces the pickled returns of ELFI's batch farm (elfi/client.py:268-274; the per-batch farm-out of
  * elfi/methods/parameter_inference.py:283-292): the ranks' small per-round results travel device to device over RCCL
