@@ -45,9 +45,13 @@ struct GramArgs {
   int ninfo;
 };
 
+// X passes through LDS in chunks of at most GRAM_KC columns (2 * 64 * (GRAM_KC + 1) doubles at the most, whatever d is):
+// the k loop visits the columns in the order of the unchunked loop, so the accumulation order does not depend on the chunking.
+constexpr int GRAM_KC = 64;
+
 __global__ __launch_bounds__(256) void gram_kernel(GramArgs G) {
   extern __shared__ __align__(16) double sm[];
-  const int pitch = G.dp + 1;  // odd pitch in doubles: bank-conflict free for column walks
+  const int pitch = (G.dp < GRAM_KC ? G.dp : GRAM_KC) + 1;  // odd pitch in doubles: bank-conflict free for column walks
   double* Xi = sm;
   double* Xj = sm + 64 * pitch;
   // decode lower-triangular tile pair (ti >= tj) from the linear block index
@@ -61,12 +65,6 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs G) {
   const int64_t tj = b - ti * (ti + 1) / 2;
   if (ti >= nt) return;
   const int64_t i0 = ti * 64, j0 = tj * 64;
-  for (int e = threadIdx.x; e < 64 * G.dp; e += 256) {
-    int r = e / G.dp, c = e - r * G.dp;
-    Xi[r * pitch + c] = G.X[(i0 + r) * G.dp + c];
-    Xj[r * pitch + c] = G.X[(j0 + r) * G.dp + c];
-  }
-  __syncthreads();
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int wr = w >> 1, wc = w & 1;
   v4d acc[2][2];
@@ -74,18 +72,28 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs G) {
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int c = 0; c < 2; ++c) acc[a][c] = (v4d){0, 0, 0, 0};
-  for (int k0 = 0; k0 < G.dp; k0 += 4) {
-    double av[2], bv[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      av[a] = Xi[(wr * 32 + a * 16 + (l & 15)) * pitch + k0 + (l >> 4)];
-      bv[a] = Xj[(wc * 32 + a * 16 + (l & 15)) * pitch + k0 + (l >> 4)];
+  for (int c0 = 0; c0 < G.dp; c0 += GRAM_KC) {
+    const int kc = G.dp - c0 < GRAM_KC ? G.dp - c0 : GRAM_KC;   // a multiple of 4, as dp is
+    if (c0) __syncthreads();   // the previous chunk has been read by every wave
+    for (int e = threadIdx.x; e < 64 * kc; e += 256) {
+      int r = e / kc, c = e - r * kc;
+      Xi[r * pitch + c] = G.X[(i0 + r) * G.dp + c0 + c];
+      Xj[r * pitch + c] = G.X[(j0 + r) * G.dp + c0 + c];
     }
+    __syncthreads();
+    for (int k0 = 0; k0 < kc; k0 += 4) {
+      double av[2], bv[2];
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+      for (int a = 0; a < 2; ++a) {
+        av[a] = Xi[(wr * 32 + a * 16 + (l & 15)) * pitch + k0 + (l >> 4)];
+        bv[a] = Xj[(wc * 32 + a * 16 + (l & 15)) * pitch + k0 + (l >> 4)];
+      }
 #pragma unroll
-      for (int c = 0; c < 2; ++c)
-        acc[a][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[c], acc[a][c], 0, 0, 0);
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+          acc[a][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[c], acc[a][c], 0, 0, 0);
+    }
   }
 #pragma unroll
   for (int a = 0; a < 2; ++a)
@@ -1264,7 +1272,7 @@ static int gp_factorize_attempt(elfihip_gp* gp, double diag_add, int* info_out) 
     G.info = gp->info;
     G.ninfo = 1;
     const int64_t nt = np / 64;
-    const size_t lds = 2 * 64 * (size_t)(gp->dp + 1) * sizeof(double);
+    const size_t lds = 2 * 64 * (size_t)((gp->dp < GRAM_KC ? gp->dp : GRAM_KC) + 1) * sizeof(double);
     hipLaunchKernelGGL(gram_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), lds, st, G);
     ELFIHIP_TRY(launch_status(ctx, "gram_kernel"));
   }

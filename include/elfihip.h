@@ -1152,7 +1152,17 @@ int elfihip_gnk_summaries_dev(elfihip_ctx* ctx, const double* dZ, int64_t ldz, u
  * (X (n,d), y (n)) and, after elfihip_gp_factorize, L = chol(K + (noise + 1e-8) I),
  * L^-T and alpha = K^-1 y in device memory.  Host pointers in, host pointers out.
  */
-/* capacity: the largest n this GP will hold (rounded up to a multiple of 128). */
+/* capacity: the largest n this GP will hold (rounded up to a multiple of 128), 1 <= capacity <= 131072.
+ * d: the input dimension, 1 <= d <= 256 (anything else is ELFIHIP_ERR_ARG); the device rows are padded to
+ * dp = d rounded up to a multiple of 4.  Every entry point below works for every accepted d; which form a call takes
+ * depends on dp:
+ *   dp <= 24: the query points of a call of at most 16 points, and the evidence row of a one-point
+ *             elfihip_gp_append / elfihip_gp_extend, travel in the kernel arguments (no copy); calls with at least
+ *             min_points points (elfihip_gp_set_dense_threshold) take the dense form of the triangular products.
+ *   dp  > 24: query points and appended rows are uploaded (a prediction or LCB call of at most 128 points still reads its
+ *             points from pinned memory and gets its results without a copy); there is no dense form: every call streams the factor
+ *             in groups of at most 128 points.
+ * The Gram matrix of elfihip_gp_factorize stages X in chunks of 64 columns, so its LDS need does not grow with d. */
 int elfihip_gp_create(elfihip_ctx* ctx, int d, int64_t capacity, elfihip_gp** gp);
 int elfihip_gp_free(elfihip_gp* gp);
 /* kern.rbf.variance, kern.rbf.lengthscale, kern.bias.variance, Gaussian_noise.variance

@@ -27,9 +27,23 @@ def _fit(n, d, seed, hyper=None):
     return gp, logz, G.Posterior(X, y, h['var'], h['ls'], h['bias'], h['noise']), (X, y, bounds)
 
 
-@pytest.mark.parametrize('n,d', [(7, 1), (100, 2), (128, 3), (257, 2), (700, 10), (1300, 20), (400, 70)])
-def test_log_marginal_gradient_vs_oracle(hip_ctx, n, d):
-    gp, logz, ref, _ = _fit(n, d, seed=n + d)
+def _scaled_hyper(n, d, seed):
+    """The default hyper-parameters with the lengthscale multiplied by sqrt(d / 2): evidence points in [-2, 2]^d stay
+    correlated at any d (tests/test_gp_dimensions_gpu.py), so every coordinate of X reaches the gradient."""
+    X, y, bounds = G.synthetic_gp_problem(n, d, seed=seed)
+    h = dict(G.default_hyper(bounds, y))
+    h['ls'] *= np.sqrt(d / 2.0)
+    return h
+
+
+# (400, 70) with the default lengthscale 4/3: the largest off-diagonal k / var is 4e-12, d log Z / d ls 2.7e-11 -- K is the
+# identity to rounding and X does not matter; the case stays, and the scaled one beside it is the test of
+# kinv_grad_kernel's global-memory path (dp >= 48)
+@pytest.mark.parametrize('n,d,scaled', [pytest.param(n, d, False, id='%d-%d' % (n, d)) for n, d in
+                                        [(7, 1), (100, 2), (128, 3), (257, 2), (700, 10), (1300, 20), (400, 70)]]
+                         + [pytest.param(400, 70, True, id='400-70-scaled-lengthscale')])
+def test_log_marginal_gradient_vs_oracle(hip_ctx, n, d, scaled):
+    gp, logz, ref, _ = _fit(n, d, seed=n + d, hyper=_scaled_hyper(n, d, n + d) if scaled else None)
     lz, g = gp.nlml_grad()
     assert lz == logz
     assert abs(lz - ref.log_marginal) <= 1e-9 * abs(ref.log_marginal)
