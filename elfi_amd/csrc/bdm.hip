@@ -9,8 +9,8 @@
 // linear search over the cumulative cluster sizes.
 //
 // bd_sim_kernel: one wavefront per simulation, persistent: a wavefront takes its NEXT simulation from a counter in device
-// memory (the events per simulation vary 40-fold over the prior), by one atomic of the whole wavefront read back as a scalar,
-// as daycare.hip does and for its reason.  Everything that decides the control flow -- pop, cluster_end, the event, the chosen
+// memory (the events per simulation vary 40-fold over the prior), by one atomic of the whole wavefront read back as a scalar
+// (event_sim.hpp: wave_fetch, and its reason).  Everything that decides the control flow -- pop, cluster_end, the event, the chosen
 // cluster, the event count -- is the same in all 64 lanes, so the event loop has no divergent exit.
 //   N <= 64: lane l holds clusters[l] in a register, and with it the INCLUSIVE cumulative sum up to l.  An event changes one or
 //   two clusters by one, so the cumulative sums are kept, not recomputed: the lanes at or past the cluster add the change.  The
@@ -35,6 +35,7 @@
 #include <cmath>
 
 #include "dist_metrics.hpp"
+#include "event_sim.hpp"
 #include "np_sum.hpp"
 #include "philox.hpp"
 
@@ -42,7 +43,7 @@
 
 namespace elfihip {
 
-constexpr int BD_THREADS = 64;                   // one wavefront
+constexpr int BD_THREADS = SIM_THREADS;
 constexpr int BD_MAX_N = ELFIHIP_BDM_MAX_N;      // 4096 = 64 lanes x 64 slots
 constexpr int BD_LEAF = 128;                     // NumPy's pairwise leaf
 constexpr int BD_PAIR_GRIDS = 2;                 // bd_pair_kernel from this many full grids (32 wavefronts per CU) of simulations on
@@ -66,14 +67,6 @@ struct BdArgs {
   unsigned long long* counter;   // the next simulation, zero at launch
 };
 
-// the two uniforms of event k of simulation g
-__device__ __forceinline__ void bd_draw(uint64_t seed, uint64_t stream, uint64_t g, uint32_t k, double& ue, double& uc) {
-  uint32_t r[4];
-  philox4x32_10(k, (uint32_t)g, (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
-  ue = (double)(((uint64_t)r[0] << 21) | (r[1] >> 11)) * 0x1.0p-53;
-  uc = (double)(((uint64_t)r[2] << 21) | (r[3] >> 11)) * 0x1.0p-53;
-}
-
 // the value lane `src` holds (src the same in every lane), as a scalar
 __device__ __forceinline__ int bd_lane_int(int v, int src) {
   return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(src));
@@ -82,14 +75,6 @@ __device__ __forceinline__ double bd_lane_double(double v, int src) {
   const int s = __builtin_amdgcn_readfirstlane(src);
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), s), __builtin_amdgcn_readlane(__double2loint(v), s));
 }
-
-__device__ __forceinline__ int bd_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ bool bd_rate_ok(double r) { return r >= 0.0 && r < INFINITY; }
 
 // NumPy's pairwise sum of term(lo) .. term(lo + n - 1), by the whole wavefront: every call and every barrier is reached by all
 // 64 lanes, the lanes fill a leaf together and each adds it up in NumPy's order
@@ -119,14 +104,11 @@ __global__ __launch_bounds__(BD_THREADS) void bd_sim_kernel(BdArgs A) {
   const int cap = N + (A.mode == 1);
   const int blk_lo = lane * B, blk_hi = blk_lo + B < N ? blk_lo + B : N;   // this lane's slots [blk_lo, blk_hi), empty past N
   for (;;) {
-    // the next simulation: every lane takes part in the one atomic, the answer is a scalar (see daycare.hip)
-    const unsigned long long got = atomicAdd(A.counter, lane == 0 ? 1ull : 0ull);
-    const unsigned long long sim = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(got >> 32)) << 32) |
-                                   (unsigned)__builtin_amdgcn_readfirstlane((int)got);
+    const unsigned long long sim = wave_fetch(A.counter, lane, 1ull);   // the next simulation, a scalar
     if (sim >= (unsigned long long)A.n) break;
     const double alpha = A.alpha[sim], delta = A.delta[sim], tau = A.tau[sim];
     const double c0 = 0.0 + alpha, c1 = c0 + delta, c2 = c1 + tau, tot = c2;
-    const bool rates_ok = bd_rate_ok(alpha) && bd_rate_ok(delta) && bd_rate_ok(tau) && tot > 0.0 && tot < INFINITY;
+    const bool rates_ok = rate_ok(alpha) && rate_ok(delta) && rate_ok(tau) && tot > 0.0 && tot < INFINITY;
     const uint64_t g = A.first + sim;
     const double* urow = DRAWN ? nullptr : A.U + (int64_t)sim * A.ldu;
     // the state: own (small form: this lane's cluster; wide form: this lane's block sum), cum (the inclusive cumulative sum
@@ -151,7 +133,7 @@ __global__ __launch_bounds__(BD_THREADS) void bd_sim_kernel(BdArgs A) {
         double ue, uc;
         if constexpr (DRAWN) {
           const int slot = (int)(k & 63u);
-          if (slot == 0) bd_draw(A.seed, A.stream, g, k + 1u + (unsigned)lane, bue, buc);
+          if (slot == 0) uniform53_pair(A.seed, A.stream, k + 1u + (unsigned)lane, (uint32_t)g, bue, buc);   // (g << 32) | event
           ue = bd_lane_double(bue, slot);
           uc = bd_lane_double(buc, slot);
         } else {
@@ -276,8 +258,8 @@ __global__ __launch_bounds__(BD_THREADS) void bd_sim_kernel(BdArgs A) {
         cnt += v > 0u ? 1 : 0;
         sum += (int)v;
       }
-      cnt = bd_wave_sum(cnt);
-      sum = bd_wave_sum(sum);
+      cnt = wave_sum(cnt);
+      sum = wave_sum(sum);
       const double t2n = A.t2n;
       auto term = [&](int i) {
         const double q = (double)s_cl[i] / t2n;
@@ -314,16 +296,13 @@ __global__ __launch_bounds__(BD_THREADS) void bd_pair_kernel(BdArgs A) {
   const int lane = threadIdx.x, half = lane >> 5, l = lane & 31, h0 = half * 32, N = A.N;
   const int cap = N + (A.mode == 1);
   for (;;) {
-    // the next two simulations: every lane takes part in the one atomic, the answer is a scalar (see daycare.hip)
-    const unsigned long long got = atomicAdd(A.counter, lane == 0 ? 2ull : 0ull);
-    const unsigned long long base = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(got >> 32)) << 32) |
-                                    (unsigned)__builtin_amdgcn_readfirstlane((int)got);
+    const unsigned long long base = wave_fetch(A.counter, lane, 2ull);   // the next two simulations, a scalar
     if (base >= (unsigned long long)A.n) break;
     const bool valid = base + half < (unsigned long long)A.n;       // (an odd batch: the last wavefront's upper half is idle)
     const unsigned long long sim = valid ? base + half : base;
     const double alpha = A.alpha[sim], delta = A.delta[sim], tau = A.tau[sim];
     const double c0 = 0.0 + alpha, c1 = c0 + delta, c2 = c1 + tau, tot = c2;
-    const bool rates_ok = bd_rate_ok(alpha) && bd_rate_ok(delta) && bd_rate_ok(tau) && tot > 0.0 && tot < INFINITY;
+    const bool rates_ok = rate_ok(alpha) && rate_ok(delta) && rate_ok(tau) && tot > 0.0 && tot < INFINITY;
     const uint64_t g = A.first + sim;
     const double* urow = DRAWN ? nullptr : A.U + (int64_t)sim * A.ldu;
     int own = l == 0 ? 1 : 0, cum = 1, pop = 1, cend = 1, last = 0, st = rates_ok ? ELFIHIP_BDM_REACHED_N : ELFIHIP_BDM_INVALID;
@@ -338,7 +317,7 @@ __global__ __launch_bounds__(BD_THREADS) void bd_pair_kernel(BdArgs A) {
       double ue, uc;
       if constexpr (DRAWN) {
         const int slot = (int)(k & 31u);
-        if (slot == 0) bd_draw(A.seed, A.stream, g, k + 1u + (unsigned)l, bue, buc);
+        if (slot == 0) uniform53_pair(A.seed, A.stream, k + 1u + (unsigned)l, (uint32_t)g, bue, buc);
         ue = __shfl(bue, h0 + slot, 64);
         uc = __shfl(buc, h0 + slot, 64);
       } else {
@@ -423,7 +402,7 @@ __global__ __launch_bounds__(256) void bd_draws_kernel(uint64_t seed, uint64_t s
   for (int64_t el = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; el < total; el += stride) {
     const int64_t i = el / n_events, e = el - i * n_events;
     double ue, uc;
-    bd_draw(seed, stream, first + (uint64_t)i, (uint32_t)(e + 1), ue, uc);
+    uniform53_pair(seed, stream, (uint32_t)(e + 1), (uint32_t)(first + (uint64_t)i), ue, uc);
     U[i * ldu + 2 * e] = ue;
     U[i * ldu + 2 * e + 1] = uc;
   }
@@ -433,9 +412,7 @@ __global__ __launch_bounds__(256) void bd_draws_kernel(uint64_t seed, uint64_t s
 static int bd_shape_check(elfihip_ctx* ctx, int64_t first, int64_t n, int64_t n_events) {
   ELFIHIP_REQUIRE(ctx, n >= 1, "bad batch n=%lld: at least 1", (long long)n);
   ELFIHIP_REQUIRE(ctx, n_events >= 1 && n_events <= ELFIHIP_BDM_MAX_EVENTS, "%lld events: 1 to 2^30", (long long)n_events);
-  ELFIHIP_REQUIRE(ctx, first >= 0 && first <= (int64_t)0xffffffffLL && n <= (int64_t)0x100000000LL - first,
-                  "simulation indices first .. first + n - 1 must stay below 2^32");
-  return ELFIHIP_OK;
+  return check_sim_indices(ctx, first, n);
 }
 
 static int bd_model_check(elfihip_ctx* ctx, int64_t first, int64_t n, int N, int mode, int64_t max_events, const void* alpha,
@@ -448,28 +425,13 @@ static int bd_model_check(elfihip_ctx* ctx, int64_t first, int64_t n, int N, int
   return ELFIHIP_OK;
 }
 
-template <class KernelT>
-static int bd_launch_sim(elfihip_ctx* ctx, KernelT kernel, int instance, const BdArgs& A, int per_wave = 1) {
-  // a persistent grid: as many wavefronts as the device holds at once, never more than there are simulations
-  int& per_cu = ctx->bd_per_cu[instance];
-  if (per_cu == 0) {
-    int q = 0;
-    ELFIHIP_CHECK_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kernel, BD_THREADS, 0));
-    per_cu = std::max(1, std::min(q, 32));
-  }
-  const unsigned grid = (unsigned)std::min<int64_t>((A.n + per_wave - 1) / per_wave, (int64_t)ctx->cu_count * per_cu);
-  ELFIHIP_CHECK_HIP(ctx, hipMemsetAsync(A.counter, 0, sizeof(unsigned long long), ctx->stream));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(BD_THREADS), 0, ctx->stream, A);
-  return launch_status(ctx, "bd_sim_kernel");
-}
-
 static int bd_dev_impl(elfihip_ctx* ctx, const double* dU, int64_t ldu, uint64_t seed, uint64_t stream, int64_t first, int64_t n,
                        int N, int mode, int64_t max_events, const double* dalpha, const double* ddelta, const double* dtau,
                        double t2_n, const double* obs, int32_t* dCl, int64_t ldc, int32_t* dstatus, int64_t* devents, double* dT,
                        int64_t ldt, double* dD) {
   ELFIHIP_TRY(bd_model_check(ctx, first, n, N, mode, max_events, dalpha, ddelta, dtau, obs, dD));
   ELFIHIP_REQUIRE(ctx, (!dU || ldu >= 2 * max_events) && (!dCl || ldc >= N) && (!dT || ldt >= 2), "leading dimension below the row length");
-  ELFIHIP_CHECK_HIP(ctx, ctx->bd.reserve(256));
+  ELFIHIP_CHECK_HIP(ctx, ctx->sim.reserve(SIM_HEAD));
   BdArgs A;
   A.U = dU;
   A.ldu = ldu;
@@ -493,13 +455,17 @@ static int bd_dev_impl(elfihip_ctx* ctx, const double* dU, int64_t ldu, uint64_t
   A.T = dT;
   A.ldt = ldt;
   A.D = dD;
-  A.counter = ctx->bd.as<unsigned long long>();
+  A.counter = ctx->sim.as<unsigned long long>();
   // two simulations per wavefront pay off once the device is full and lose before (N = 20, truth: 0.56 x the time at 10^5
   // simulations, 0.61 x at 10^4, 1.21 x at 500; from the prior 0.65 x, 1.17 x, 1.52 x -- DESIGN.md): from two full grids on
   if (N <= 32 && n >= BD_PAIR_GRIDS * (int64_t)ctx->cu_count * 32)
-    return dU ? bd_launch_sim(ctx, bd_pair_kernel<false>, 4, A, 2) : bd_launch_sim(ctx, bd_pair_kernel<true>, 5, A, 2);
-  if (N <= BD_THREADS) return dU ? bd_launch_sim(ctx, bd_sim_kernel<false, false>, 0, A) : bd_launch_sim(ctx, bd_sim_kernel<true, false>, 1, A);
-  return dU ? bd_launch_sim(ctx, bd_sim_kernel<false, true>, 2, A) : bd_launch_sim(ctx, bd_sim_kernel<true, true>, 3, A);
+    return dU ? launch_persistent(ctx, bd_pair_kernel<false>, "bd_pair_kernel", (n + 1) / 2, A)
+              : launch_persistent(ctx, bd_pair_kernel<true>, "bd_pair_kernel", (n + 1) / 2, A);
+  if (N <= BD_THREADS)
+    return dU ? launch_persistent(ctx, bd_sim_kernel<false, false>, "bd_sim_kernel", n, A)
+              : launch_persistent(ctx, bd_sim_kernel<true, false>, "bd_sim_kernel", n, A);
+  return dU ? launch_persistent(ctx, bd_sim_kernel<false, true>, "bd_sim_kernel", n, A)
+            : launch_persistent(ctx, bd_sim_kernel<true, true>, "bd_sim_kernel", n, A);
 }
 
 static int bd_draws_impl(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int64_t n_events, double* dU,
@@ -512,8 +478,6 @@ static int bd_draws_impl(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64
   hipLaunchKernelGGL(bd_draws_kernel, dim3(grid), dim3(256), 0, ctx->stream, seed, stream, (uint64_t)first, n, n_events, dU, ldu);
   return launch_status(ctx, "bd_draws_kernel");
 }
-
-static inline size_t bd_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace elfihip
 
@@ -539,8 +503,8 @@ int elfihip_bdm_clusters(elfihip_ctx* ctx, const double* U, uint64_t seed, uint6
   DeviceGuard g(ctx->device);
   const size_t nn = (size_t)n, nu = U ? nn * 2 * (size_t)max_events : 0, pb = nn * sizeof(double);
   ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((nu + 3 * nn) * sizeof(double)));
-  const size_t o_d = bd_align(2 * pb), o_e = o_d + bd_align(pb), o_c = o_e + bd_align(nn * sizeof(int64_t));
-  const size_t o_s = o_c + bd_align(nn * (size_t)N * sizeof(int32_t));
+  const size_t o_d = align256(2 * pb), o_e = o_d + align256(pb), o_c = o_e + align256(nn * sizeof(int64_t));
+  const size_t o_s = o_c + align256(nn * (size_t)N * sizeof(int32_t));
   ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(o_s + nn * sizeof(int32_t)));
   char* out = ctx->out.as<char>();
   double *dU = ctx->in.as<double>(), *dpar = dU + nu;

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/elfihip.h"
@@ -80,14 +81,13 @@ struct elfihip_ctx {
   elfihip::DevBuf stat;   // workgroup partials of the fused adaptive-distance pass (adaptive.hip; topk.hip owns `scratch`)
   elfihip::DevBuf sel;    // twostage.hip: a block of subset distances and its survivors; the partial sums of the entropy
                           // adjust.hip: the tile factors, the tile sums, the jobs' means and coefficients
-  elfihip::DevBuf lv;     // gillespie.hip: the counter simulations are dealt from, and the observations when the caller keeps none
-  elfihip::DevBuf dc;     // daycare.hip: the counter pairs are dealt from, carriage masks and summaries the caller keeps none of, the sorted observed rows
-  int dc_per_cu[2] = {0, 0};         // daycare.hip: resident workgroups per CU of dc_sim_kernel<DRAWN>, asked for once
-  elfihip::DevBuf sa;     // scratch_assay.hip: the counter simulations are dealt from
-  int sa_per_cu[2] = {0, 0};         // scratch_assay.hip: resident workgroups per CU of sa_sim_kernel<DRAWN>, asked for once
-  elfihip::DevBuf bd;     // bdm.hip: the counter simulations are dealt from
-  int bd_per_cu[6] = {0, 0, 0, 0, 0, 0};   // bdm.hip: resident workgroups per CU of bd_sim_kernel<DRAWN, WIDE> and bd_pair_kernel<DRAWN>, asked for once
-  int lv_per_cu[4] = {0, 0, 0, 0};   // gillespie.hip: resident workgroups per CU of lv_sim_kernel<DRAWN, NOISE>, asked for once
+  // The event-driven simulators (event_sim.hpp; gillespie.hip, daycare.hip, scratch_assay.hip, bdm.hip) share one work buffer:
+  // the counter work units are dealt from at offset 0, a 256-byte head, then the calling model's own work space (gillespie.hip:
+  // the observations when the caller keeps none; daycare.hip: the sorted observed rows, and the status, carriage masks and
+  // summaries the caller keeps none of).  One buffer is as safe as one per model: the calls on a context are ordered by its
+  // stream, nothing in it outlives the call that wrote it, and DevBuf::reserve frees synchronously (hipFree waits for the device).
+  elfihip::DevBuf sim;
+  std::vector<std::pair<const void*, int>> sim_per_cu;   // a persistent kernel instance's address, its resident workgroups per CU
   // the distances the last host-form distance call returned, kept on the device for the sampler state
   // (elfihip_kept_distances / elfihip_reject_push_kept): (keep_n, keep_cols) row-major; the epoch names the call
   elfihip::DevBuf keep;

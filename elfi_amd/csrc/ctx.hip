@@ -165,10 +165,7 @@ int elfihip_ctx_destroy(elfihip_ctx* ctx) {
     ctx->scratch.release();
     ctx->stat.release();
     ctx->sel.release();
-    ctx->lv.release();
-    ctx->dc.release();
-    ctx->sa.release();
-    ctx->bd.release();
+    ctx->sim.release();
     ctx->keep.release();
     ctx->rows.release();
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

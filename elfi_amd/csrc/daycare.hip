@@ -9,7 +9,7 @@
 //     ss_shannon, ss_strains, ss_prevalence, ss_prevalence_multi, distance                             daycare.py:199-312
 //
 // dc_sim_kernel: one wavefront per (simulation, centre) pair, persistent: a wavefront whose pair ends takes the NEXT pair
-// from a counter in device memory (one atomic per pair; event counts under the priors range from tens to over 10^4).  A
+// from a counter in device memory (event_sim.hpp: one atomic per pair; event counts under the priors range from tens to over 10^4).  A
 // lane is individual `lane` (its strains as the bits of `mask`) AND strain `lane` (its carriers as the bits of `car`):
 // n_ind, n_strains <= 64.  The hazard of (i, s) is 1 where i carries s and c_i g_s elsewhere, so an event costs a lane
 // n_ind + n_strains + n_ind + n_strains steps instead of n_ind n_strains hazards: the strain lanes sum P_s over the carriers'
@@ -20,8 +20,8 @@
 // bounded (events by max_events, pairs by the counter), no wavefront waits for another, and which wavefront ran a pair when
 // does not enter its result: the draws of event k of centre c of simulation i are Philox counter ((c << 22) | k, i).
 // dc_summary_kernel: one wavefront per pair over the masks written; Shannon's sum in NumPy's pairwise order (np_sum.hpp).
-// dc_dist_kernel: rows of k summaries x m centres divided by the observed maxima, one lane Shell-sorts one row in LDS (the
-// per-row sort of gnk.hip), |x - y| against the sorted observed row summed left to right.
+// dc_dist_kernel: rows of k summaries x m centres divided by the observed maxima, one lane Shell-sorts one row in LDS
+// (lane_sort.hpp), |x - y| against the sorted observed row summed left to right.
 // FMA contraction is off.  The statement of the model is in include/elfihip.h (elfihip_daycare_summaries) and, in NumPy, in
 // tests/daycare_ref.py.
 #include "common.hpp"
@@ -29,6 +29,8 @@
 #include <algorithm>
 #include <cmath>
 
+#include "event_sim.hpp"
+#include "lane_sort.hpp"
 #include "np_sum.hpp"
 #include "philox.hpp"
 
@@ -36,7 +38,7 @@
 
 namespace elfihip {
 
-constexpr int DC_THREADS = 64;        // one wavefront
+constexpr int DC_THREADS = SIM_THREADS;
 constexpr int DC_EVENT_BITS = 22;     // Philox counter word 0: (centre << 22) | event;  max_events <= 2^21, n_dcc <= 2^10
 constexpr int DC_SUMMARIES = ELFIHIP_DAYCARE_SUMMARIES;
 constexpr size_t DC_DIST_LDS = 48 * 1024;
@@ -59,19 +61,6 @@ struct DcArgs {
   double f[ELFIHIP_DAYCARE_MAX_STRAINS];   // the strains' prevalence in the community
 };
 
-// the two 53-bit integers of Philox counter ((c << 22) | k, i) of (seed, stream)
-__device__ __forceinline__ void dc_words(uint64_t seed, uint64_t stream, uint64_t i, uint32_t c, uint32_t k, uint64_t& a, uint64_t& b) {
-  uint32_t r[4];
-  philox4x32_10((c << DC_EVENT_BITS) | k, (uint32_t)i, (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed,
-                (uint32_t)(seed >> 32), r);
-  a = ((uint64_t)r[0] << 21) | (r[1] >> 11);
-  b = ((uint64_t)r[2] << 21) | (r[3] >> 11);
-}
-__device__ __forceinline__ double dc_exponential(uint64_t a) { return -log((double)(a + 1) * 0x1.0p-53); }
-__device__ __forceinline__ double dc_uniform(uint64_t b) { return (double)b * 0x1.0p-53; }
-
-__device__ __forceinline__ bool dc_rate_ok(double r) { return r >= 0.0 && r < INFINITY; }
-
 template <bool DRAWN>
 __global__ __launch_bounds__(DC_THREADS) void dc_sim_kernel(DcArgs A) {
   __shared__ double s_invk[DC_THREADS], s_g[DC_THREADS], s_r[DC_THREADS];
@@ -80,15 +69,7 @@ __global__ __launch_bounds__(DC_THREADS) void dc_sim_kernel(DcArgs A) {
   const unsigned long long pairs = (unsigned long long)A.n * (unsigned long long)A.n_dcc;
   const double fs = lane < n_strains ? A.f[lane] : 0.0;
   for (;;) {
-    // ---- the next pair ----
-    // Every lane takes part in the one atomic (lane 0 adds 1, the others 0: the compiler folds them into one instruction)
-    // and the answer is read back from lane 0 as a scalar, so that every branch on it -- this loop's exit, the invalid
-    // simulation's `continue` -- is a branch of the whole wavefront.  With `if (lane == 0)` around the atomic the compiler
-    // joins that test to the `if (lane == 0)` of the marks below and sends the other 63 lanes round the loop without lane
-    // 0: a broadcast from lane 0 then reads nothing, they take pair 0 again and the loop never ends.
-    const unsigned long long got = atomicAdd(A.counter, lane == 0 ? 1ull : 0ull);
-    const unsigned long long p = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(got >> 32)) << 32) |
-                                 (unsigned)__builtin_amdgcn_readfirstlane((int)got);
+    const unsigned long long p = wave_fetch(A.counter, lane, 1ull);   // the next pair, a scalar
     if (p >= pairs) break;
     const int64_t sim = (int64_t)(p / (unsigned)A.n_dcc);
     const uint32_t centre = (uint32_t)(p - (unsigned long long)sim * (unsigned)A.n_dcc);
@@ -97,7 +78,7 @@ __global__ __launch_bounds__(DC_THREADS) void dc_sim_kernel(DcArgs A) {
     double t = 0.0;
     int k = 0;
     bool reached = false;
-    if (!(dc_rate_ok(t1) && dc_rate_ok(t2) && dc_rate_ok(t3))) {    // (uniform) the whole simulation is invalid
+    if (!(rate_ok(t1) && rate_ok(t2) && rate_ok(t3))) {    // (uniform) the whole simulation is invalid
       if (lane < A.n_obs) A.M[p * A.ldm + lane] = 0ull;
       if (lane == 0) {
         A.status[p] = ELFIHIP_DAYCARE_INVALID;
@@ -111,10 +92,11 @@ __global__ __launch_bounds__(DC_THREADS) void dc_sim_kernel(DcArgs A) {
       ++k;
       double e, u;
       if constexpr (DRAWN) {
+        const uint64_t g = A.first + (uint64_t)sim;
         uint64_t a, b;
-        dc_words(A.seed, A.stream, A.first + (uint64_t)sim, centre, (uint32_t)k, a, b);
-        e = dc_exponential(a);
-        u = dc_uniform(b);
+        words53(A.seed, A.stream, (centre << DC_EVENT_BITS) | (uint32_t)k, (uint32_t)g, a, b);
+        e = unit_exponential(a);
+        u = unit_co(b);
       } else {
         e = A.E[p * A.lde + (k - 1)];
         u = A.U[p * A.ldu + (k - 1)];
@@ -179,10 +161,11 @@ __global__ __launch_bounds__(256) void dc_draws_kernel(uint64_t seed, uint64_t s
   for (int64_t el = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; el < total; el += stride) {
     const int64_t p = el / n_events, i = p / n_dcc;
     const int k = (int)(el - p * n_events) + 1;
+    const uint64_t g = first + (uint64_t)i;
     uint64_t a, b;
-    dc_words(seed, stream, first + (uint64_t)i, (uint32_t)(p - i * n_dcc), (uint32_t)k, a, b);
-    E[p * lde + (k - 1)] = dc_exponential(a);
-    U[p * ldu + (k - 1)] = dc_uniform(b);
+    words53(seed, stream, ((uint32_t)(p - i * n_dcc) << DC_EVENT_BITS) | (uint32_t)k, (uint32_t)g, a, b);
+    E[p * lde + (k - 1)] = unit_exponential(a);
+    U[p * ldu + (k - 1)] = unit_co(b);
   }
 }
 
@@ -237,26 +220,6 @@ __global__ __launch_bounds__(DC_THREADS) void dc_summary_kernel(DcSumArgs A) {
 }
 
 // ---- the distance -------------------------------------------------------------------------------------------------------
-// np.sort's order: a NaN is greater than every number
-__device__ __forceinline__ bool dc_after(double a, double b) { return a > b || (a != a && b == b); }
-
-// Shell sort in place (Knuth's gaps 1, 4, 13, ...), NaNs last as np.sort leaves them
-__device__ __forceinline__ void dc_sort(double* y, int m) {
-  int g = 1;
-  while (g < m / 3) g = 3 * g + 1;
-  for (; g >= 1; g /= 3) {
-    for (int i = g; i < m; ++i) {
-      const double x = y[i];
-      int j = i;
-      while (j >= g && dc_after(y[j - g], x)) {
-        y[j] = y[j - g];
-        j -= g;
-      }
-      y[j] = x;
-    }
-  }
-}
-
 // the observed rows, once per call: one workgroup per summary: the row's maximum (1 where it is 0), the row divided by it, sorted
 __global__ __launch_bounds__(DC_THREADS) void dc_obs_kernel(const double* __restrict__ obs, int m, double* __restrict__ ys,
                                                             double* __restrict__ om) {
@@ -271,7 +234,7 @@ __global__ __launch_bounds__(DC_THREADS) void dc_obs_kernel(const double* __rest
   for (int c = tid; c < m; c += DC_THREADS) tile[c] = row[c] / o;
   __syncthreads();
   if (tid == 0) {
-    dc_sort(tile, m);
+    shell_sort(tile, m, nan_last_after);
     om[blockIdx.x] = o;
   }
   __syncthreads();
@@ -294,7 +257,7 @@ __global__ __launch_bounds__(DC_THREADS) void dc_dist_kernel(const double* __res
     __syncthreads();
     if (tid < rows) {
       double* y = tile + (size_t)tid * Lp;
-      dc_sort(y, m);
+      shell_sort(y, m, nan_last_after);
       const double* yo = ys + (size_t)(tid % k) * m;
       double acc = 0.0;
       for (int c = 0; c < m; ++c) acc += fabs(y[c] - yo[c]);
@@ -311,8 +274,6 @@ __global__ __launch_bounds__(DC_THREADS) void dc_dist_kernel(const double* __res
 }
 
 // ---- launches -----------------------------------------------------------------------------------------------------------
-static inline size_t dc_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // obs (k, m) host values -> the sorted, normalised rows and the maxima at `work` (device: raw k m, sorted k m, maxima k),
 // then D (n) of the rows of dX
 static int dc_distance_launch(elfihip_ctx* ctx, const double* dX, int64_t ldx, int64_t n, int k, int m, const double* obs,
@@ -345,34 +306,15 @@ static int dc_distance_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t ldx,
                                 double* dD) {
   ELFIHIP_TRY(dc_distance_check(ctx, n, k, m, obs));
   ELFIHIP_REQUIRE(ctx, dX && dD && ldx >= (int64_t)k * m, "NULL pointer or leading dimension below the row length");
-  const size_t head = 256;
-  ELFIHIP_CHECK_HIP(ctx, ctx->dc.reserve(head + (2 * (size_t)k * m + k) * sizeof(double)));
-  return dc_distance_launch(ctx, dX, ldx, n, k, m, obs, reinterpret_cast<double*>(ctx->dc.as<char>() + head), dD);
-}
-
-template <class KernelT>
-static int dc_launch_sim(elfihip_ctx* ctx, KernelT kernel, int instance, const DcArgs& A) {
-  // a persistent grid: as many wavefronts as the device holds at once, never more than there are pairs
-  int& per_cu = ctx->dc_per_cu[instance];
-  if (per_cu == 0) {
-    int q = 0;
-    ELFIHIP_CHECK_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kernel, DC_THREADS, 0));
-    per_cu = std::max(1, std::min(q, 32));
-  }
-  const int64_t pairs = A.n * A.n_dcc;
-  const unsigned grid = (unsigned)std::min<int64_t>(pairs, (int64_t)ctx->cu_count * per_cu);
-  ELFIHIP_CHECK_HIP(ctx, hipMemsetAsync(A.counter, 0, sizeof(unsigned long long), ctx->stream));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(DC_THREADS), 0, ctx->stream, A);
-  return launch_status(ctx, "dc_sim_kernel");
+  ELFIHIP_CHECK_HIP(ctx, ctx->sim.reserve(SIM_HEAD + (2 * (size_t)k * m + k) * sizeof(double)));
+  return dc_distance_launch(ctx, dX, ldx, n, k, m, obs, reinterpret_cast<double*>(ctx->sim.as<char>() + SIM_HEAD), dD);
 }
 
 static int dc_shape_check(elfihip_ctx* ctx, int64_t first, int64_t n, int n_dcc, int64_t n_events) {
   ELFIHIP_REQUIRE(ctx, n >= 1 && n <= ELFIHIP_DAYCARE_MAX_BATCH, "bad batch n=%lld: 1 to 2^31 - 1", (long long)n);
   ELFIHIP_REQUIRE(ctx, n_dcc >= 1 && n_dcc <= ELFIHIP_DAYCARE_MAX_DCC, "%d centres: 1 to %d", n_dcc, ELFIHIP_DAYCARE_MAX_DCC);
   ELFIHIP_REQUIRE(ctx, n_events >= 1 && n_events <= ELFIHIP_DAYCARE_MAX_EVENTS, "max_events %lld: 1 to 2^21", (long long)n_events);
-  ELFIHIP_REQUIRE(ctx, first >= 0 && first <= (int64_t)0xffffffffLL && n <= (int64_t)0x100000000LL - first,
-                  "simulation indices first .. first + n - 1 must stay below 2^32");
-  return ELFIHIP_OK;
+  return check_sim_indices(ctx, first, n);
 }
 
 static int dc_dev_impl(elfihip_ctx* ctx, const double* dE, int64_t lde, const double* dU, int64_t ldu, uint64_t seed,
@@ -398,12 +340,12 @@ static int dc_dev_impl(elfihip_ctx* ctx, const double* dE, int64_t lde, const do
   // the counter, the observed rows' work space, and whatever the kernels hand each other that the caller does not keep
   const size_t pairs = (size_t)n * n_dcc, km = (size_t)DC_SUMMARIES * n_dcc;
   const bool want_s = dS || dD;
-  const size_t o_obs = 256, o_st = o_obs + dc_align((2 * km + DC_SUMMARIES) * sizeof(double));
-  const size_t o_m = o_st + (dstatus ? 0 : dc_align(pairs * sizeof(int32_t)));
-  const size_t o_s = o_m + (dM ? 0 : dc_align(pairs * n_obs * sizeof(uint64_t)));
-  const size_t end = o_s + (dS || !dD ? 0 : dc_align((size_t)n * km * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, ctx->dc.reserve(end));
-  char* base = ctx->dc.as<char>();
+  const size_t o_obs = SIM_HEAD, o_st = o_obs + align256((2 * km + DC_SUMMARIES) * sizeof(double));
+  const size_t o_m = o_st + (dstatus ? 0 : align256(pairs * sizeof(int32_t)));
+  const size_t o_s = o_m + (dM ? 0 : align256(pairs * n_obs * sizeof(uint64_t)));
+  const size_t end = o_s + (dS || !dD ? 0 : align256((size_t)n * km * sizeof(double)));
+  ELFIHIP_CHECK_HIP(ctx, ctx->sim.reserve(end));
+  char* base = ctx->sim.as<char>();
   DcArgs A;
   A.E = dE;
   A.U = dU;
@@ -428,12 +370,12 @@ static int dc_dev_impl(elfihip_ctx* ctx, const double* dE, int64_t lde, const do
   A.T = dT;
   A.status = dstatus ? dstatus : reinterpret_cast<int*>(base + o_st);
   A.events = reinterpret_cast<long long*>(devents);
-  A.counter = ctx->dc.as<unsigned long long>();
+  A.counter = ctx->sim.as<unsigned long long>();
   for (int s = 0; s < ELFIHIP_DAYCARE_MAX_STRAINS; ++s) A.f[s] = s < n_strains ? (freq ? freq[s] : 0.1) : 0.0;
   if (dE)
-    ELFIHIP_TRY(dc_launch_sim(ctx, dc_sim_kernel<false>, 0, A));
+    ELFIHIP_TRY(launch_persistent(ctx, dc_sim_kernel<false>, "dc_sim_kernel", (int64_t)pairs, A));
   else
-    ELFIHIP_TRY(dc_launch_sim(ctx, dc_sim_kernel<true>, 1, A));
+    ELFIHIP_TRY(launch_persistent(ctx, dc_sim_kernel<true>, "dc_sim_kernel", (int64_t)pairs, A));
   if (!want_s) return ELFIHIP_OK;
   DcSumArgs B;
   B.M = A.M;

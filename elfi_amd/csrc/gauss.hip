@@ -74,12 +74,10 @@ __global__ __launch_bounds__(256) void randn_rows_kernel(uint64_t seed, uint64_t
 // Philox counter e / 2 -- the words normal_pair() turns into a Box-Muller pair.  Every transform keeps the reference's
 // operation order (multiply and add round separately, as NumPy's do).
 __device__ __forceinline__ void uniform_pair(uint64_t seed, uint64_t stream, uint64_t p, double& u0, double& u1) {
-  uint32_t r[4];
-  philox4x32_10((uint32_t)p, (uint32_t)(p >> 32), (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed,
-                (uint32_t)(seed >> 32), r);
-  const uint64_t a = ((uint64_t)r[0] << 21) | (r[1] >> 11), b = ((uint64_t)r[2] << 21) | (r[3] >> 11);
-  u0 = (double)a * 0x1.0p-53;
-  u1 = (double)b * 0x1.0p-53;
+  uint64_t a, b;
+  words53(seed, stream, p, a, b);
+  u0 = unit_co(a);
+  u1 = unit_co(b);
 }
 
 // (plain operators: this file is compiled with fp contract off, the __dmul_rn / __dadd_rn header wrappers are not -- their

@@ -18,7 +18,8 @@
 // a simulation when does not enter its result: the draws of event k of simulation i are Philox counter (i << 32) | k.
 // The state of a simulation is three rates, two stocks, the time and two counters; nothing of the trajectory is kept --
 // observation i is emitted by the first event at or past its time, from that event and the state before it, straight to
-// device memory (a few hundred bytes per simulation against thousands of events of arithmetic).
+// device memory (a few hundred bytes per simulation against thousands of events of arithmetic).  The launch -- a persistent
+// grid sized by the instance's occupancy, the counter zeroed -- is event_sim.hpp's, the draws are philox.hpp's.
 // lv_summary_kernel: one lane per simulation over the observations written, NumPy's pairwise sums (np_sum.hpp), FMA
 // contraction off: bit-identical to the reference's summary functions except for the device's log in the two log-variance
 // columns.  The two are separate launches because their shapes differ: the simulation is latency-bound, wants every
@@ -31,6 +32,7 @@
 #include <cmath>
 
 #include "dist_metrics.hpp"
+#include "event_sim.hpp"
 #include "np_sum.hpp"
 #include "philox.hpp"
 
@@ -38,7 +40,7 @@
 
 namespace elfihip {
 
-constexpr int LV_THREADS = 64;        // one wavefront
+constexpr int LV_THREADS = SIM_THREADS;
 constexpr int LV_SUMMARIES = ELFIHIP_LV_SUMMARIES;
 constexpr double LV_INT_LIMIT = 2147483648.0;
 
@@ -60,20 +62,8 @@ struct LvArgs {
   unsigned long long* counter;   // the next simulation index, zero at launch
 };
 
-// the two 53-bit integers of Philox counter (i << 32) | k of (seed, stream)
-__device__ __forceinline__ void lv_words(uint64_t seed, uint64_t stream, uint64_t i, uint32_t k, uint64_t& a, uint64_t& b) {
-  uint32_t r[4];
-  philox4x32_10(k, (uint32_t)i, (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
-  a = ((uint64_t)r[0] << 21) | (r[1] >> 11);
-  b = ((uint64_t)r[2] << 21) | (r[3] >> 11);
-}
-__device__ __forceinline__ double lv_exponential(uint64_t a) { return -log((double)(a + 1) * 0x1.0p-53); }
-__device__ __forceinline__ double lv_uniform(uint64_t b) { return (double)b * 0x1.0p-53; }
-
 // what an int32 slot keeps of v: truncated toward zero, -0 as +0; NaN where the cast is undefined
 __device__ __forceinline__ double lv_store(double v) { return fabs(v) < LV_INT_LIMIT ? trunc(v) + 0.0 : NAN; }
-
-__device__ __forceinline__ bool lv_rate_ok(double r) { return r >= 0.0 && r < INFINITY; }
 
 template <bool DRAWN, bool NOISE>
 __global__ __launch_bounds__(LV_THREADS) void lv_sim_kernel(LvArgs A) {
@@ -110,7 +100,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_sim_kernel(LvArgs A) {
           k = 0;
           io = 1;
           yrow = A.Y + idx * A.ldy;
-          const bool valid = lv_rate_ok(r1) && lv_rate_ok(r2) && lv_rate_ok(r3) && lv_rate_ok(sg) && x >= 0.0 &&
+          const bool valid = rate_ok(r1) && rate_ok(r2) && rate_ok(r3) && rate_ok(sg) && x >= 0.0 &&
                              x < LV_INT_LIMIT && y >= 0.0 && y < LV_INT_LIMIT;
           if (valid) {
             yrow[0] = x;
@@ -135,9 +125,9 @@ __global__ __launch_bounds__(LV_THREADS) void lv_sim_kernel(LvArgs A) {
       double e, u;
       if constexpr (DRAWN) {
         uint64_t a, b;
-        lv_words(A.seed, A.stream, A.first + (uint64_t)idx, (uint32_t)k, a, b);
-        e = lv_exponential(a);
-        u = lv_uniform(b);
+        words53(A.seed, A.stream, (uint32_t)k, (uint32_t)(A.first + (uint64_t)idx), a, b);   // counter (i << 32) | k
+        e = unit_exponential(a);
+        u = unit_co(b);
       } else {
         e = A.E[idx * A.lde + (k - 1)];
         u = A.U[idx * A.ldu + (k - 1)];
@@ -201,9 +191,9 @@ __global__ __launch_bounds__(256) void lv_draws_kernel(uint64_t seed, uint64_t s
     const int64_t i = el / n_events;
     const int k = (int)(el - i * n_events) + 1;
     uint64_t a, b;
-    lv_words(seed, stream, first + (uint64_t)i, (uint32_t)k, a, b);
-    E[i * lde + (k - 1)] = lv_exponential(a);
-    U[i * ldu + (k - 1)] = lv_uniform(b);
+    words53(seed, stream, (uint32_t)k, (uint32_t)(first + (uint64_t)i), a, b);
+    E[i * lde + (k - 1)] = unit_exponential(a);
+    U[i * ldu + (k - 1)] = unit_co(b);
   }
 }
 
@@ -272,23 +262,6 @@ __global__ __launch_bounds__(LV_THREADS) void lv_summary_kernel(LvSumArgs A) {
 }
 
 // ---- launches -----------------------------------------------------------------------------------------------------------
-template <class KernelT>
-static int lv_launch_sim(elfihip_ctx* ctx, KernelT kernel, int instance, const LvArgs& A) {
-  // a persistent grid: as many wavefronts as the device holds at once (the kernel's registers decide), never more than
-  // there are groups of 64 simulations; the occupancy of an instance is asked for once per context
-  int& per_cu = ctx->lv_per_cu[instance];
-  if (per_cu == 0) {
-    int q = 0;
-    ELFIHIP_CHECK_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kernel, LV_THREADS, 0));
-    per_cu = std::max(1, std::min(q, 32));
-  }
-  const int64_t groups = (A.n + LV_THREADS - 1) / LV_THREADS;
-  const unsigned grid = (unsigned)std::min<int64_t>(groups, (int64_t)ctx->cu_count * per_cu);
-  ELFIHIP_CHECK_HIP(ctx, hipMemsetAsync(A.counter, 0, sizeof(unsigned long long), ctx->stream));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(LV_THREADS), 0, ctx->stream, A);
-  return launch_status(ctx, "lv_sim_kernel");
-}
-
 static int lv_dev_impl(elfihip_ctx* ctx, const double* dE, int64_t lde, const double* dU, int64_t ldu, const double* dZ,
                        int64_t ldz, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int n_obs, double time_end,
                        int64_t max_events, const double* dr1, const double* dr2, const double* dr3, const double* dprey,
@@ -299,8 +272,7 @@ static int lv_dev_impl(elfihip_ctx* ctx, const double* dE, int64_t lde, const do
                   ELFIHIP_SERIES_MAX_OBS);
   ELFIHIP_REQUIRE(ctx, max_events >= 1 && max_events <= ELFIHIP_LV_MAX_EVENTS, "max_events %lld: 1 to 2^30", (long long)max_events);
   ELFIHIP_REQUIRE(ctx, std::isfinite(time_end) && time_end > 0.0, "time_end must be finite and positive");
-  ELFIHIP_REQUIRE(ctx, first >= 0 && first <= (int64_t)0xffffffffLL && n <= (int64_t)0x100000000LL - first,
-                  "simulation indices first .. first + n - 1 must stay below 2^32");
+  ELFIHIP_TRY(check_sim_indices(ctx, first, n));
   ELFIHIP_REQUIRE(ctx, (dE == nullptr) == (dU == nullptr), "E and U are given together or not at all");
   ELFIHIP_REQUIRE(ctx, !dZ || dsigma, "noise draws without sigma");
   ELFIHIP_REQUIRE(ctx, !dD || obs, "a distance needs the observed summaries");
@@ -309,8 +281,8 @@ static int lv_dev_impl(elfihip_ctx* ctx, const double* dE, int64_t lde, const do
                            (!dY || ldy >= 2 * n_obs) && (!dS || lds >= LV_SUMMARIES),
                   "leading dimension below the row length");
   // the counter, and the observations when the caller does not want them but the summaries need them
-  const size_t head = 256, ybytes = dY ? 0 : (size_t)n * 2 * n_obs * sizeof(double);
-  ELFIHIP_CHECK_HIP(ctx, ctx->lv.reserve(head + ybytes));
+  const size_t ybytes = dY ? 0 : (size_t)n * 2 * n_obs * sizeof(double);
+  ELFIHIP_CHECK_HIP(ctx, ctx->sim.reserve(SIM_HEAD + ybytes));
   LvArgs A;
   A.E = dE;
   A.U = dU;
@@ -332,22 +304,24 @@ static int lv_dev_impl(elfihip_ctx* ctx, const double* dE, int64_t lde, const do
   A.max_events = (int)max_events;
   A.time_end = time_end;
   A.step = time_end / (double)(n_obs - 1);      // np.linspace's step
-  A.Y = dY ? dY : reinterpret_cast<double*>(ctx->lv.as<char>() + head);
+  A.Y = dY ? dY : reinterpret_cast<double*>(ctx->sim.as<char>() + SIM_HEAD);
   A.ldy = dY ? ldy : 2 * (int64_t)n_obs;
   A.T = dT;
   A.status = dstatus;
   A.events = reinterpret_cast<long long*>(devents);
-  A.counter = ctx->lv.as<unsigned long long>();
+  A.counter = ctx->sim.as<unsigned long long>();
+  // a lane per simulation: never more wavefronts than there are groups of 64 simulations
+  const int64_t groups = (n + LV_THREADS - 1) / LV_THREADS;
   if (dE) {
     if (dsigma)
-      ELFIHIP_TRY(lv_launch_sim(ctx, lv_sim_kernel<false, true>, 1, A));
+      ELFIHIP_TRY(launch_persistent(ctx, lv_sim_kernel<false, true>, "lv_sim_kernel", groups, A));
     else
-      ELFIHIP_TRY(lv_launch_sim(ctx, lv_sim_kernel<false, false>, 0, A));
+      ELFIHIP_TRY(launch_persistent(ctx, lv_sim_kernel<false, false>, "lv_sim_kernel", groups, A));
   } else {
     if (dsigma)
-      ELFIHIP_TRY(lv_launch_sim(ctx, lv_sim_kernel<true, true>, 3, A));
+      ELFIHIP_TRY(launch_persistent(ctx, lv_sim_kernel<true, true>, "lv_sim_kernel", groups, A));
     else
-      ELFIHIP_TRY(lv_launch_sim(ctx, lv_sim_kernel<true, false>, 2, A));
+      ELFIHIP_TRY(launch_persistent(ctx, lv_sim_kernel<true, false>, "lv_sim_kernel", groups, A));
   }
   if (!dS && !dD) return ELFIHIP_OK;
   LvSumArgs B;
@@ -371,8 +345,7 @@ static int lv_draws_impl(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64
                          double* dE, int64_t lde, double* dU, int64_t ldu) {
   ELFIHIP_REQUIRE(ctx, n >= 1 && n_events >= 1 && n_events <= ELFIHIP_LV_MAX_EVENTS, "bad shape n=%lld n_events=%lld",
                   (long long)n, (long long)n_events);
-  ELFIHIP_REQUIRE(ctx, first >= 0 && first <= (int64_t)0xffffffffLL && n <= (int64_t)0x100000000LL - first,
-                  "simulation indices first .. first + n - 1 must stay below 2^32");
+  ELFIHIP_TRY(check_sim_indices(ctx, first, n));
   ELFIHIP_REQUIRE(ctx, dE && dU && lde >= n_events && ldu >= n_events, "NULL pointer or leading dimension below the row length");
   const unsigned grid = (unsigned)std::min<int64_t>((n * n_events + 255) / 256, (int64_t)ctx->cu_count * 16);
   hipLaunchKernelGGL(lv_draws_kernel, dim3(grid), dim3(256), 0, ctx->stream, seed, stream, (uint64_t)first, n, (int)n_events, dE,

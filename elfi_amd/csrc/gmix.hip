@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void gm_rvs_kernel(GmRvsArgs G) {
     uint32_t r[4];
     philox4x32_10((uint32_t)i, (uint32_t)((uint64_t)i >> 32), (uint32_t)G.stream, (uint32_t)(G.stream >> 32), (uint32_t)G.seed,
                   (uint32_t)(G.seed >> 32), r);
-    const double u = (double)(((uint64_t)r[0] << 21) | (r[1] >> 11)) * 0x1.0p-53;
+    const double u = unit_co(word53(r[0], r[1]));
     int64_t lo = 0, hi = G.N - 1;   // first index with cumw > u
     while (lo < hi) {
       const int64_t mid = (lo + hi) >> 1;

@@ -16,7 +16,7 @@
 // evaluates the quantile function in the reference's order of operations and puts the value into its column in LDS --
 // and COLUMNS only once there is something to sort: one lane owns one (simulation, dimension) column, 64 simulations per
 // tile at dim = 1 and 32 at dim = 2 (fewer only where that many columns exceed the LDS), Shell-sorts it in place with NaNs
-// last, reads the seven octiles at the host's (lo, hi, t) positions (np.percentile's linear rule, as mg1_kernel reads its
+// last (lane_sort.hpp), reads the seven octiles at the host's (lo, hi, t) positions (np.percentile's linear rule, as mg1_kernel reads its
 // quantiles) and forms the robust statistics from them.  Columns have the odd pitch of series.hip: the 32 lanes of a
 // ds_read_b64 group touch 32 different bank pairs at every step of the sort.  FMA contraction is off: everything after the
 // series is bit-identical to NumPy on the same series; the series itself goes through the device's exp and pow and is
@@ -32,6 +32,7 @@
 
 #include "dist_launch.hpp"
 #include "dist_metrics.hpp"
+#include "lane_sort.hpp"
 #include "philox.hpp"
 
 #pragma clang fp contract(off)
@@ -67,9 +68,6 @@ struct GnkArgs {
   double t[GNK_NOCT];
   double obs[GNK_OBS_INLINE];
 };
-
-// np.sort's order: a NaN is greater than every number
-__device__ __forceinline__ bool gnk_after(double a, double b) { return a > b || (a != a && b == b); }
 
 __global__ __launch_bounds__(GNK_THREADS) void gnk_kernel(GnkArgs A) {
   extern __shared__ __align__(16) double tile[];
@@ -160,22 +158,7 @@ __global__ __launch_bounds__(GNK_THREADS) void gnk_kernel(GnkArgs A) {
     __syncthreads();
     // ---- sort and read: lanes take columns ----
     double* y = tile + (size_t)(tid < cols ? tid : 0) * Lp;
-    if (tid < cols) {
-      // Shell sort in place (Knuth's gaps 1, 4, 13, ...), NaNs last as np.sort leaves them
-      int g = 1;
-      while (g < nobs / 3) g = 3 * g + 1;
-      for (; g >= 1; g /= 3) {
-        for (int i = g; i < nobs; ++i) {
-          const double x = y[i];
-          int j = i;
-          while (j >= g && gnk_after(y[j - g], x)) {
-            y[j] = y[j - g];
-            j -= g;
-          }
-          y[j] = x;
-        }
-      }
-    }
+    if (tid < cols) shell_sort(y, nobs, nan_last_after);   // NaNs last, as np.sort leaves them
     if (A.Ys || (A.D && A.which == ELFIHIP_GNK_SORTED)) {   // (uniform) the sorted columns leave in whole rows, coalesced
       __syncthreads();
       if (A.Ys)

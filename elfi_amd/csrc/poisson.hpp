@@ -3,8 +3,8 @@
 // elfihip_poisson_dev into memory or inside a fused example kernel (series.hip: Ricker).  tests/ricker_ref.py states the
 // same rule in NumPy.
 //
-// Attempt j = 0, 1, ... of element e reads Philox counter e of stream (seed, stream + j): u1 = ((r0 << 21) | (r1 >> 11))
-// 2^-53 and u2 the same of words 2, 3, both in [0, 1).
+// Attempt j = 0, 1, ... of element e reads Philox counter e of stream (seed, stream + j): u1 = word53(r0, r1) 2^-53
+// and u2 the same of words 2, 3, both in [0, 1) (philox.hpp: uniform53_pair).
 //   lam NaN, lam < 0, lam > 2^53   NaN (NumPy's RandomState.poisson raises ValueError for the whole batch instead)
 //   lam == 0                       0, no draw
 //   0 < lam < 10                   inversion on u1 of attempt 0: p = F = exp(-lam), k = 0; while u1 > F: k += 1, p = p (lam /
@@ -25,15 +25,6 @@
 
 namespace elfihip {
 
-// the two 53-bit uniforms in [0, 1) of Philox counter e of stream (seed, stream)
-__device__ __forceinline__ void uniform53_pair(uint64_t seed, uint64_t stream, uint64_t e, double& u1, double& u2) {
-  uint32_t r[4];
-  philox4x32_10((uint32_t)e, (uint32_t)(e >> 32), (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed,
-                (uint32_t)(seed >> 32), r);
-  u1 = (double)(((uint64_t)r[0] << 21) | (r[1] >> 11)) * 0x1.0p-53;
-  u2 = (double)(((uint64_t)r[2] << 21) | (r[3] >> 11)) * 0x1.0p-53;
-}
-
 // (forced inline: as a call its registers are added to the caller's, which halves the Ricker kernel's wavefronts per SIMD)
 __device__ __forceinline__ double poisson_draw(double lam, uint64_t seed, uint64_t stream, uint64_t e) {
 #pragma clang fp contract(off)
@@ -41,7 +32,7 @@ __device__ __forceinline__ double poisson_draw(double lam, uint64_t seed, uint64
   if (lam == 0.0) return 0.0;
   double u1, u2;
   if (lam < 10.0) {
-    uniform53_pair(seed, stream, e, u1, u2);
+    uniform53_pair(seed, stream, (uint32_t)e, (uint32_t)(e >> 32), u1, u2);
     double p = exp(-lam), F = p;
     int k = 0;
     while (u1 > F && k < ELFIHIP_POISSON_MAX_K) {
@@ -57,7 +48,7 @@ __device__ __forceinline__ double poisson_draw(double lam, uint64_t seed, uint64
   const double invalpha = 1.1239 + 1.1328 / (b - 3.4);
   const double vr = 0.9277 - 3.6224 / (b - 2.0);
   for (int j = 0; j < ELFIHIP_POISSON_MAX_ATTEMPTS; ++j) {
-    uniform53_pair(seed, stream + (uint64_t)j, e, u1, u2);
+    uniform53_pair(seed, stream + (uint64_t)j, (uint32_t)e, (uint32_t)(e >> 32), u1, u2);
     const double U = u1 - 0.5, V = u2, us = 0.5 - fabs(U);
     const double k = floor((((2.0 * a) / us + b) * U + lam) + 0.43);
     if (us >= 0.07 && V <= vr) return k;

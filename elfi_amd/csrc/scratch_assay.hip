@@ -18,8 +18,8 @@
 // Summaries: ds[j] = the cells that differ between frames j and j + 1, then the cell count of frame n_obs.
 //
 // sa_sim_kernel: one wavefront per simulation, persistent: a wavefront takes its NEXT simulation from a counter in device memory
-// (the events per simulation vary 20-fold over the prior), by one atomic of the whole wavefront read back as a scalar, as
-// daycare.hip does and for its reason.  The grid lies in LDS as one BYTE per cell (1 KB), lane l owns cells 16 l .. 16 l + 15:
+// (the events per simulation vary 20-fold over the prior), by one atomic of the whole wavefront read back as a scalar
+// (event_sim.hpp: wave_fetch, and its reason).  The grid lies in LDS as one BYTE per cell (1 KB), lane l owns cells 16 l .. 16 l + 15:
 // every iteration it packs them to 16 bits, a wave prefix sum of the popcounts places its cells in the row-major list (LDS,
 // 16-bit linear indices, 2 KB).  The draw pass is parallel -- lane takes slots lane + 64 j over a wave-uniform trip count (at most
 // 16), checks what it read, and the selected slots are compacted IN SLOT ORDER into a queue (LDS, candidate | direction << 10, 2
@@ -39,13 +39,14 @@
 #include <algorithm>
 #include <cmath>
 
+#include "event_sim.hpp"
 #include "philox.hpp"
 
 #pragma clang fp contract(off)
 
 namespace elfihip {
 
-constexpr int SA_THREADS = 64;                          // one wavefront
+constexpr int SA_THREADS = SIM_THREADS;
 constexpr int SA_MAX = ELFIHIP_ASSAY_MAX_CELLS;         // 1024 = 64 lanes x 16 cells
 constexpr int SA_WORDS = SA_MAX / 32;
 constexpr int SA_SLOT_BITS = 10;                        // Philox counter word 0: ((2 t + f) << 10) | slot
@@ -75,19 +76,13 @@ __device__ __forceinline__ void sa_draw(uint64_t seed, uint64_t stream, uint64_t
   philox4x32_10(((uint32_t)(2 * t + f) << SA_SLOT_BITS) | (uint32_t)k, (uint32_t)g, (uint32_t)stream, (uint32_t)(stream >> 32),
                 (uint32_t)seed, (uint32_t)(seed >> 32), r);
   c = (int)__umulhi(r[0], (uint32_t)num_cells);
-  p = (double)(((uint64_t)r[1] << 21) | (r[2] >> 11)) * 0x1.0p-53;
+  p = unit_co(word53(r[1], r[2]));
   m = r[3] >> 30;
 }
 
 // four cells, one byte each (0 or 1) <-> four bits
 __device__ __forceinline__ unsigned sa_pack4(unsigned w) { return ((w * 0x01020408u) >> 24) & 0xFu; }
 __device__ __forceinline__ unsigned sa_spread4(unsigned b) { return (b & 1u) | ((b & 2u) << 7) | ((b & 4u) << 14) | ((b & 8u) << 21); }
-
-__device__ __forceinline__ int sa_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 template <bool DRAWN>
 __global__ __launch_bounds__(SA_THREADS) void sa_sim_kernel(SaArgs A) {
@@ -97,10 +92,7 @@ __global__ __launch_bounds__(SA_THREADS) void sa_sim_kernel(SaArgs A) {
   const unsigned init16 = (A.init[lane >> 1] >> ((lane & 1) * 16)) & 0xFFFFu;
   const unsigned long long below = (1ull << lane) - 1ull;
   for (;;) {
-    // the next simulation: every lane takes part in the one atomic, the answer is a scalar (see daycare.hip)
-    const unsigned long long got = atomicAdd(A.counter, lane == 0 ? 1ull : 0ull);
-    const unsigned long long sim = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(got >> 32)) << 32) |
-                                   (unsigned)__builtin_amdgcn_readfirstlane((int)got);
+    const unsigned long long sim = wave_fetch(A.counter, lane, 1ull);   // the next simulation, a scalar
     if (sim >= (unsigned long long)A.n) break;
     const double pm = A.pm[sim], pp = A.pp[sim];
     const uint64_t g = A.first + sim;
@@ -120,7 +112,7 @@ __global__ __launch_bounds__(SA_THREADS) void sa_sim_kernel(SaArgs A) {
       if (t == next_obs) {             // the grid after iteration t - 1 is frame t / obs_every
         ++frame;
         next_obs += A.obs_every;
-        const int ds = sa_wave_sum(__popc(prev ^ cur));
+        const int ds = wave_sum(__popc(prev ^ cur));
         if (lane == 0) S[frame - 1] = (double)ds;
         const unsigned up = (unsigned)__shfl_down((int)cur, 1, 64);
         if (frames && !(lane & 1)) frames[frame * SA_WORDS + (lane >> 1)] = cur | (up << 16);
@@ -203,7 +195,7 @@ __global__ __launch_bounds__(SA_THREADS) void sa_sim_kernel(SaArgs A) {
         for (int j = lane; j < (n_obs + 1) * SA_WORDS; j += SA_THREADS) frames[j] = 0u;
       made[0] = made[1] = 0;
     } else {
-      const int count = sa_wave_sum(__popc(prev));
+      const int count = wave_sum(__popc(prev));
       if (lane == 0) S[n_obs] = (double)count;
     }
     if (lane == 0) {
@@ -242,9 +234,7 @@ static int sa_shape_check(elfihip_ctx* ctx, int64_t first, int64_t n, int n_iter
   ELFIHIP_REQUIRE(ctx, n >= 1 && n <= ELFIHIP_ASSAY_MAX_BATCH, "bad batch n=%lld: 1 to 2^31 - 1", (long long)n);
   ELFIHIP_REQUIRE(ctx, cells >= 1 && cells <= ELFIHIP_ASSAY_MAX_CELLS, "%lld cells: 1 to %d", (long long)cells, ELFIHIP_ASSAY_MAX_CELLS);
   ELFIHIP_REQUIRE(ctx, n_iter >= 1 && n_iter <= ELFIHIP_ASSAY_MAX_ITER, "%d iterations: 1 to 2^21", n_iter);
-  ELFIHIP_REQUIRE(ctx, first >= 0 && first <= (int64_t)0xffffffffLL && n <= (int64_t)0x100000000LL - first,
-                  "simulation indices first .. first + n - 1 must stay below 2^32");
-  return ELFIHIP_OK;
+  return check_sim_indices(ctx, first, n);
 }
 
 static int sa_model_check(elfihip_ctx* ctx, int64_t first, int64_t n, int nrows, int ncols, int n_iter, int obs_every,
@@ -259,21 +249,6 @@ static int sa_model_check(elfihip_ctx* ctx, int64_t first, int64_t n, int nrows,
   return ELFIHIP_OK;
 }
 
-template <class KernelT>
-static int sa_launch_sim(elfihip_ctx* ctx, KernelT kernel, int instance, const SaArgs& A) {
-  // a persistent grid: as many wavefronts as the device holds at once, never more than there are simulations
-  int& per_cu = ctx->sa_per_cu[instance];
-  if (per_cu == 0) {
-    int q = 0;
-    ELFIHIP_CHECK_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kernel, SA_THREADS, 0));
-    per_cu = std::max(1, std::min(q, 32));
-  }
-  const unsigned grid = (unsigned)std::min<int64_t>(A.n, (int64_t)ctx->cu_count * per_cu);
-  ELFIHIP_CHECK_HIP(ctx, hipMemsetAsync(A.counter, 0, sizeof(unsigned long long), ctx->stream));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SA_THREADS), 0, ctx->stream, A);
-  return launch_status(ctx, "sa_sim_kernel");
-}
-
 static int sa_dev_impl(elfihip_ctx* ctx, const int32_t* dC, const double* dP, const uint8_t* dM, uint64_t seed, uint64_t stream,
                        int64_t first, int64_t n, int nrows, int ncols, int n_iter, int obs_every, const uint8_t* init,
                        const double* dpm, const double* dpp, double* dS, int64_t lds, int32_t* dstatus, int64_t* devents,
@@ -281,7 +256,7 @@ static int sa_dev_impl(elfihip_ctx* ctx, const int32_t* dC, const double* dP, co
   ELFIHIP_TRY(sa_model_check(ctx, first, n, nrows, ncols, n_iter, obs_every, init, dC, dP, dM, dpm, dpp, dS));
   const int n_obs = n_iter / obs_every;
   ELFIHIP_REQUIRE(ctx, lds >= n_obs + 1, "leading dimension below the row length");
-  ELFIHIP_CHECK_HIP(ctx, ctx->sa.reserve(256));
+  ELFIHIP_CHECK_HIP(ctx, ctx->sim.reserve(SIM_HEAD));
   SaArgs A;
   A.C = dC;
   A.P = dP;
@@ -304,10 +279,11 @@ static int sa_dev_impl(elfihip_ctx* ctx, const int32_t* dC, const double* dP, co
   A.status = dstatus;
   A.events = reinterpret_cast<long long*>(devents);
   A.frames = dframes;
-  A.counter = ctx->sa.as<unsigned long long>();
+  A.counter = ctx->sim.as<unsigned long long>();
   for (int w = 0; w < SA_WORDS; ++w) A.init[w] = 0u;
   for (int c = 0; c < A.cells; ++c) A.init[c >> 5] |= (unsigned)init[c] << (c & 31);
-  return dC ? sa_launch_sim(ctx, sa_sim_kernel<false>, 0, A) : sa_launch_sim(ctx, sa_sim_kernel<true>, 1, A);
+  return dC ? launch_persistent(ctx, sa_sim_kernel<false>, "sa_sim_kernel", n, A)
+            : launch_persistent(ctx, sa_sim_kernel<true>, "sa_sim_kernel", n, A);
 }
 
 static int sa_draws_impl(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int n_iter, int cells,
@@ -320,8 +296,6 @@ static int sa_draws_impl(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64
                      dP, dM);
   return launch_status(ctx, "sa_draws_kernel");
 }
-
-static inline size_t sa_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace elfihip
 
@@ -347,10 +321,10 @@ int elfihip_assay_summaries(elfihip_ctx* ctx, const int32_t* C, const double* P,
   DeviceGuard g(ctx->device);
   const size_t nn = (size_t)n, nd = C ? nn * (size_t)n_iter * 2 * (size_t)(nrows * ncols) : 0, ns = nn * (size_t)(n_iter / obs_every + 1);
   const size_t nf = frames ? ns * SA_WORDS : 0;
-  const size_t i_c = sa_align((nd + 2 * nn) * sizeof(double)), i_m = i_c + sa_align(nd * sizeof(int32_t));
+  const size_t i_c = align256((nd + 2 * nn) * sizeof(double)), i_m = i_c + align256(nd * sizeof(int32_t));
   ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(i_m + nd));
-  const size_t o_e = sa_align(ns * sizeof(double)), o_f = o_e + sa_align(2 * nn * sizeof(int64_t));
-  const size_t o_s = o_f + sa_align(nf * sizeof(uint32_t));
+  const size_t o_e = align256(ns * sizeof(double)), o_f = o_e + align256(2 * nn * sizeof(int64_t));
+  const size_t o_s = o_f + align256(nf * sizeof(uint32_t));
   ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(o_s + nn * sizeof(int32_t)));
   char *in = ctx->in.as<char>(), *out = ctx->out.as<char>();
   double *dP = ctx->in.as<double>(), *dpar = dP + nd;
@@ -395,7 +369,7 @@ int elfihip_assay_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_
     ELFIHIP_REQUIRE(ctx, num_cells[r] >= 0 && num_cells[r] <= cells, "num_cells[%lld] = %d: 0 to %d", (long long)r, num_cells[r], cells);
   DeviceGuard g(ctx->device);
   ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(rows * sizeof(int32_t)));
-  const size_t o_c = sa_align(nd * sizeof(double)), o_m = o_c + sa_align(nd * sizeof(int32_t));
+  const size_t o_c = align256(nd * sizeof(double)), o_m = o_c + align256(nd * sizeof(int32_t));
   ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(o_m + nd));
   char* out = ctx->out.as<char>();
   double* dP = ctx->out.as<double>();

@@ -26,7 +26,7 @@
 // eight independent accumulators per lane, FMA contraction off, so that series, summaries and quantiles are BIT-IDENTICAL to
 // the reference's NumPy on the same draws.  LDS rows have an odd pitch: the 32 lanes of a read group touch 32 different
 // 8-byte banks at every step.  What bounds the lanes in flight is LDS -- a simulation keeps its whole series there (it is
-// reduced twice and, for M/G/1, sorted) -- so at n_obs = 100 three tiles are resident per CU; they are independent
+// reduced twice and, for M/G/1, sorted: lane_sort.hpp) -- so at n_obs = 100 three tiles are resident per CU; they are independent
 // workgroups, and one fills its draws (ALU-bound) while another walks its recurrence (latency-bound).
 //
 // Draws made here are the library's counter-based stream (philox.hpp): the ARCH noise matrix (n, n_obs + 2) holds, row-major,
@@ -42,6 +42,7 @@
 
 #include "dist_launch.hpp"
 #include "dist_metrics.hpp"
+#include "lane_sort.hpp"
 #include "np_sum.hpp"
 #include "philox.hpp"
 #include "poisson.hpp"
@@ -55,15 +56,6 @@ constexpr size_t SERIES_LDS = 160 * 1024;
 constexpr int ARCH_MAX_LAGS = ELFIHIP_ARCH_MAX_LAGS;
 constexpr int ARCH_MAX_M = 2 + ARCH_MAX_LAGS + ARCH_MAX_LAGS * (ARCH_MAX_LAGS - 1) / 2;
 constexpr int MG1_MAX_Q = ELFIHIP_MG1_MAX_QUANTILES;
-
-// the two 53-bit words of Philox counter p of stream (seed, stream)
-__device__ __forceinline__ void words53(uint64_t seed, uint64_t stream, uint64_t p, uint64_t& a, uint64_t& b) {
-  uint32_t r[4];
-  philox4x32_10((uint32_t)p, (uint32_t)(p >> 32), (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed,
-                (uint32_t)(seed >> 32), r);
-  a = ((uint64_t)r[0] << 21) | (r[1] >> 11);
-  b = ((uint64_t)r[2] << 21) | (r[3] >> 11);
-}
 
 // NumPy's sum of n terms by the lane that owns the row; rows of more than 128 terms take the recursive form
 template <bool WIDE, class F>
@@ -315,7 +307,7 @@ __global__ __launch_bounds__(SERIES_THREADS) void mg1_kernel(Mg1Args A) {
           const int64_t e = 2 * p + h;
           if (e >= e0 && e < e1) {
             const int off = (int)(e - e0), r = off / nobs, i = off - r * nobs;
-            const double ex = -log((double)(we[h] + 1) * 0x1.0p-53), un = (double)wv[h] * 0x1.0p-53;
+            const double ex = unit_exponential(we[h]), un = unit_co(wv[h]);
             te[r * Lp + i] = ex;
             tv[r * Lp + i] = un;
             if (A.Eo) A.Eo[(row0 + r) * A.ldeo + i] = ex;
@@ -352,21 +344,9 @@ __global__ __launch_bounds__(SERIES_THREADS) void mg1_kernel(Mg1Args A) {
     }
     __syncthreads();
     if (tid < rows) {
-      // Shell sort in place (Knuth's gaps 1, 4, 13, ...): the sorted values are what np.quantile's partition leaves at the
-      // positions it reads
-      int g = 1;
-      while (g < nobs / 3) g = 3 * g + 1;
-      for (; g >= 1; g /= 3) {
-        for (int i = g; i < nobs; ++i) {
-          const double x = y[i];
-          int j = i;
-          while (j >= g && y[j - g] > x) {
-            y[j] = y[j - g];
-            j -= g;
-          }
-          y[j] = x;
-        }
-      }
+      // sorted in place (lane_sort.hpp): the sorted values are what np.quantile's partition leaves at the positions it reads;
+      // the plain comparison, a row with a NaN is overwritten below
+      shell_sort(y, nobs, [](double a, double b) { return a > b; });
       double* q = A.Q + gi * A.ldq;
       double acc = 0.0;   // (Op<ELFIHIP_EUCLIDEAN, W>::init())
       for (int k = 0; k < A.nq; ++k) {

@@ -10,8 +10,8 @@
 //                     Z = (W / (cos TH / tan aTH + sin TH)) ((cos aTH + sin aTH tan TH) / W) ^ (1 / alpha)
 //                     the variate is Z scale
 //   stable_draw(alpha, scale, seed, stream, e) reads Philox counter e of stream (seed, stream):
-//     TH = u1 pi + (-pi / 2), u1 = ((r0 << 21) | (r1 >> 11)) 2^-53 in [0, 1)            (SciPy: uniform.rvs(loc, scale))
-//     W  = -log(u2),          u2 = (((r2 << 21) | (r3 >> 11)) + 1) 2^-53 in (0, 1]
+//     TH = u1 pi + (-pi / 2), u1 = word53(r0, r1) 2^-53 in [0, 1)                        (SciPy: uniform.rvs(loc, scale))
+//     W  = -log(u2),          u2 = (word53(r2, r3) + 1) 2^-53 in (0, 1]                  (philox.hpp: unit_co, unit_exponential)
 //   so element e is the same number wherever it is drawn: by elfihip_stable_dev into memory or inside toad.hip.
 // The skewed law and the S0 parameterisation are stable_general below (the stochastic-volatility example, sv.hip, uses them).
 #pragma once
@@ -44,11 +44,9 @@ __device__ __forceinline__ double stable_transform(double alpha, double scale, d
 // the angle and the exponential of Philox counter e of stream (seed, stream)
 __device__ __forceinline__ void stable_angle_expo(uint64_t seed, uint64_t stream, uint64_t e, double& TH, double& W) {
 #pragma clang fp contract(off)
-  uint32_t r[4];
-  philox4x32_10((uint32_t)e, (uint32_t)(e >> 32), (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed,
-                (uint32_t)(seed >> 32), r);
-  const uint64_t a = ((uint64_t)r[0] << 21) | (r[1] >> 11), b = ((uint64_t)r[2] << 21) | (r[3] >> 11);
-  const double u1 = (double)a * 0x1.0p-53, u2 = (double)(b + 1) * 0x1.0p-53;
+  uint64_t a, b;
+  words53(seed, stream, e, a, b);
+  const double u1 = unit_co(a), u2 = unit_oc(b);
   TH = u1 * ELFIHIP_PI + (-ELFIHIP_HALF_PI);
   W = -log(u2);
 }

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(TOAD_THREADS) void toad_kernel(const ToadArgs A) {
         uint32_t w[4];
         philox4x32_10((uint32_t)e, (uint32_t)(e >> 32), (uint32_t)s1, (uint32_t)(s1 >> 32), (uint32_t)A.seed,
                       (uint32_t)(A.seed >> 32), w);
-        U = (double)(((uint64_t)w[0] << 21) | (w[1] >> 11)) * 0x1.0p-53;
+        U = unit_co(word53(w[0], w[1]));
         r = (int)__umulhi(w[2], (uint32_t)i);
       }
       const double dx = valid ? stable_transform(alpha, gamma, TH, W) : __builtin_nan("");

@@ -16,7 +16,7 @@
 // compare-exchange is one 64-bit comparison; a caller pads its n values to P with the image of +inf, which the network
 // leaves behind them.  NaN has no place in that order: callers drop it first (as np.nanquantile does).
 //
-// One lane sorting one short column (gnk.hip, series.hip: M/G/1, daycare.hip) stays the form for columns of a few dozen
+// One lane sorting one short column (lane_sort.hpp: gnk.hip, series.hip: M/G/1, daycare.hip) stays the form for columns of a few dozen
 // values, many per workgroup; this one is for ONE column of thousands per workgroup (toad.hip: 4 092 displacements).
 #pragma once
 
