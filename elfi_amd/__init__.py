@@ -19,7 +19,7 @@ from .distance import (AdaptiveDistanceState, HipDiscrepancy, HipDistance, cdist
 
 from .gmix import GMDistribution  # noqa: F401
 from .weighted import weighted_sample_quantile, weighted_var  # noqa: F401
-from .gp import GPHandle, HipGPRegression  # noqa: F401
+from .gp import GPHandle, HipGPRegression, stochastic_optimization  # noqa: F401
 from .selection import RunningBest, merge_batch, smallest_k  # noqa: F401
 from .sampler import HipRejection, hip_rejection_class  # noqa: F401
 from .distance import adaptive_batch, randn_rows  # noqa: F401

@@ -7,7 +7,7 @@
 
 `HipBOLFI` IS the reference's `elfi.BOLFI` (elfi/methods/inference/bolfi.py:386-580, on top of BayesianOptimization
 :24-383) -- a subclass made from the class of the ELFI the running program has imported (as `HipRejection` and the SMC
-classes are), so batches, pools, the update / acquire loop, `extract_result`, plotting and the result objects stay the
+classes are), so batches, pools, the update / acquire loop, plotting and the result objects stay the
 reference's.  What changes:
 
   * `__init__` (bolfi.py:28-113): `target_model` defaults to `HipGPRegression` instead of `GPyRegression`, and the default
@@ -21,6 +21,10 @@ reference's.  What changes:
     Arguments, defaults, checks, error texts, the choice of initial points, the per-chain seeds `get_sub_seed(seed, ii)`,
     the order of random draws inside a chain, the printed diagnostics and the returned `BolfiSample` are the reference's:
     chain ii equals what `mcmc.nuts(..., seed=get_sub_seed(self.seed, ii))` returns on the same surrogate.
+  * `extract_result` (bolfi.py:180-199, run at the end of every `fit` / `infer`): the reference finds `x_min` with SciPy's
+    differential evolution over `target_model.predict_mean`, one full GP prediction per trial vector.  Here `x_min` is
+    `target_model.minimize_mean(seed=self.seed)`: the same search (SciPy's defaults, deferred updates, Philox draws) whole
+    on the device over the mean alone.  Outputs and the other fields of the `OptimizationResult` are the reference's.
 """
 import sys
 
@@ -47,6 +51,7 @@ def hip_bolfi_class():
     if cls is not None:
         return cls
     ModelPrior, BolfiSample, mcmc = mod.ModelPrior, mod.BolfiSample, mod.mcmc
+    arr2d_to_batch, OptimizationResult = mod.arr2d_to_batch, mod.OptimizationResult
 
     class HipBOLFI(BOLFI):
         __doc__ = __doc__
@@ -68,6 +73,17 @@ def hip_bolfi_class():
                 prior = ModelPrior(self.model, parameter_names=self.target_model.parameter_names)
                 self.acquisition_method = HipLCBSC(self.target_model, prior=prior, noise_var=acq_noise_var,
                                                    exploration_rate=exploration_rate, seed=self.seed)
+
+        # -- bolfi.py:180-199 ---------------------------------------------------------------------------------
+        def extract_result(self):
+            if not isinstance(self.target_model, HipGPRegression) or self.target_model.n_evidence == 0:
+                return super(HipBOLFI, self).extract_result()
+            x_min, _ = self.target_model.minimize_mean(seed=self.seed)
+            names = self.target_model.parameter_names
+            batch_min = arr2d_to_batch(x_min, names)
+            outputs = arr2d_to_batch(self.target_model.X, names)
+            outputs[self.target_name] = self.target_model.Y
+            return OptimizationResult(x_min=batch_min, outputs=outputs, **self._extract_result_kwargs())
 
         # -- bolfi.py:442-462 ---------------------------------------------------------------------------------
         def extract_posterior(self, threshold=None):

@@ -96,6 +96,10 @@ struct elfihip_gp {
   // machine) and the trace level written to stderr (0 = none)
   int acq_host_threads = 0;
   int acq_trace = 0;
+  // mean-only evaluation and the search for the mean's minimiser (gp_min.hip): staged points and means; bounds, the two
+  // populations, their energies and the search's state; generations per read of the converged flag (0 = default)
+  elfihip::DevBuf ws_min, ws_de;
+  int min_chunk = 0;
   unsigned* tri_cnt = nullptr;   // 2 x (cap / 32) arrival counters of the fused triangular products (gp_predict.hip)
   // dense predictor (gp_dense.hip): workspace and pinned staging of calls with many points
   int dense_tm = 0;        // row-tile height of the dense form: 0 = by size, else 64 / 32 / 16 (ELFIHIP_DENSE_TM, tests)

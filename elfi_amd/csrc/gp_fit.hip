@@ -1432,6 +1432,8 @@ int elfihip_gp_free(elfihip_gp* gp) {
   gp->ws.release();
   gp->ws2.release();
   gp->ws_dense.release();
+  gp->ws_min.release();
+  gp->ws_de.release();
   gp->hyper_items.release();
   gp->sched_mem.release();
   delete gp;

@@ -27,6 +27,30 @@ from . import _lib
 
 logger = logging.getLogger(__name__)
 
+DE_MAX_POPULATION = 3840   # include/elfihip.h: elfihip_gp_minimize_mean
+
+
+def check_minimize_arguments(d, bounds, popsize=15, maxiter=1000, tol=0.01):
+    """The argument checks of the search for the mean's minimiser, made before any device call: (lower, upper) as arrays."""
+    try:
+        b = np.asarray([tuple(bb) for bb in bounds], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('bounds must be a sequence of (lower, upper) pairs')
+    if b.ndim != 2 or b.shape != (int(d), 2):
+        raise ValueError('bounds must have one (lower, upper) pair per input dimension ({})'.format(int(d)))
+    if not np.all(np.isfinite(b)) or not np.all(b[:, 0] < b[:, 1]):
+        raise ValueError('bounds must be finite with lower < upper in every dimension')
+    if int(popsize) != popsize or popsize < 1:
+        raise ValueError('popsize must be a positive integer')
+    if int(popsize) * int(d) > DE_MAX_POPULATION:
+        raise ValueError('popsize x dimension = {} exceeds the population limit {}'.format(int(popsize) * int(d),
+                                                                                           DE_MAX_POPULATION))
+    if int(maxiter) != maxiter or maxiter < 0:
+        raise ValueError('maxiter must be a non-negative integer')
+    if not tol >= 0:
+        raise ValueError('tol must be non-negative')
+    return np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+
 
 class GPHandle:
     """Owner of one elfihip_gp (device-resident evidence, factor and alpha)."""
@@ -151,6 +175,36 @@ class GPHandle:
                                                 _lib.ptr(mu), _lib.ptr(var)))
         return mu, var
 
+    def predict_mean(self, x):
+        """The mean alone, (S, 1): O(n d) per point, no pass over the factor (include/elfihip.h: elfihip_gp_predict_mean)."""
+        x = self._xs(x)
+        S = x.shape[0]
+        mu = np.empty((S, 1))
+        self._check(self.lib.elfihip_gp_predict_mean(self.h, _lib.ptr(x), S, _lib.ptr(mu)))
+        return mu
+
+    def set_minimize_chunk(self, generations=0):
+        """Generations minimize_mean enqueues between two reads of the converged flag (0: default); the result does not
+        depend on it."""
+        self._check(self.lib.elfihip_gp_set_minimize_chunk(self.h, int(generations)))
+
+    def minimize_mean(self, bounds, seed=0, stream=0, popsize=15, maxiter=1000, tol=0.01, polish=True):
+        """Differential evolution for the mean's minimiser inside `bounds`, whole on the device (include/elfihip.h:
+        elfihip_gp_minimize_mean).  Returns (x (d,), f, info, population (NP, d) in unit coordinates, energies (NP,));
+        info = dict(generations, evaluations, converged, polish_accepted)."""
+        lo, hi = check_minimize_arguments(self.d, bounds, popsize, maxiter, tol)
+        NP = max(5, int(popsize) * self.d)
+        x, f = np.empty(self.d), C.c_double()
+        info = np.zeros(4, dtype=np.int64)
+        pop, en = np.empty((NP, self.d)), np.empty(NP)
+        mask = (1 << 64) - 1
+        self._check(self.lib.elfihip_gp_minimize_mean(self.h, _lib.ptr(lo), _lib.ptr(hi), int(seed) & mask,
+                                                      int(stream) & mask, int(popsize), int(maxiter), float(tol),
+                                                      int(bool(polish)), _lib.ptr(x), C.byref(f), _lib.ptr(info),
+                                                      _lib.ptr(pop), _lib.ptr(en)))
+        return x, f.value, dict(generations=int(info[0]), evaluations=int(info[1]), converged=bool(info[2]),
+                                polish_accepted=bool(info[3])), pop, en
+
     def predict_grad(self, x):
         x = self._xs(x)
         S = x.shape[0]
@@ -246,6 +300,30 @@ class GPHandle:
 
 
 # ---- the small part of the GPy object graph that ELFI code touches ---------------------------
+def stochastic_optimization(fun, bounds, maxiter=1000, polish=True, seed=0):
+    """stochastic_optimization of the reference (elfi/methods/bo/utils.py:9-37): same signature, same return value
+    (x, f).  When `fun` is the bound `predict_mean` of a fitted HipGPRegression and `bounds` are that model's, the search
+    runs on the device (HipGPRegression.minimize_mean).  For ANY other callable (or other bounds) this calls the imported
+    ELFI's own function, unchanged -- SciPy's differential evolution on the host."""
+    model = getattr(fun, '__self__', None)
+    if (isinstance(model, HipGPRegression) and getattr(fun, '__func__', None) is HipGPRegression.predict_mean
+            and model._gp is not None and _same_bounds(bounds, model.bounds)):
+        return model.minimize_mean(seed=seed, maxiter=maxiter, polish=polish)
+    mod = sys.modules.get('elfi.methods.bo.utils')
+    if mod is None:
+        raise ImportError("stochastic_optimization of a host callable is the running program's ELFI function: "
+                          "`import elfi` first")
+    return mod.stochastic_optimization(fun, bounds, maxiter=maxiter, polish=polish, seed=seed)
+
+
+def _same_bounds(a, b):
+    try:
+        a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    except (TypeError, ValueError):
+        return False
+    return a.shape == b.shape and np.array_equal(a, b)
+
+
 class _Param:
     """Stands in for a paramz Param: float(p), p[0], p.values."""
 
@@ -435,6 +513,28 @@ class HipGPRegression:
 
     def predict_mean(self, x):
         return self.predict(x)[0]
+
+    def minimize_mean(self, seed=0, maxiter=1000, polish=True, popsize=15, tol=0.01, return_info=False,
+                      return_state=False):
+        """The minimiser of the posterior mean inside the model's bounds, (x (input_dim,), f): what
+        stochastic_optimization(self.predict_mean, self.bounds, ...) (elfi/methods/bo/utils.py:9-37) searches for, by a
+        differential evolution that runs whole on the device over the mean alone (include/elfihip.h:
+        elfihip_gp_minimize_mean; SciPy's defaults in their deferred form on Philox draws -- another, equally valid
+        search than SciPy's for the same point).  return_info adds dict(generations, evaluations, converged,
+        polish_accepted); return_state adds (population in unit coordinates (NP, input_dim), energies (NP,))."""
+        check_minimize_arguments(self.input_dim, self.bounds, popsize, maxiter, tol)
+        if self._gp is None:
+            raise RuntimeError('no evidence yet: the mean of an unfitted model has no minimiser to search for')
+        from .priors import GP_MINIMIZE_STREAM_BASE
+        x, f, info, pop, en = self._handle.minimize_mean(self.bounds, seed=0 if seed is None else seed,
+                                                         stream=GP_MINIMIZE_STREAM_BASE, popsize=popsize, maxiter=maxiter,
+                                                         tol=tol, polish=polish)
+        out = (x, f)
+        if return_info:
+            out += (info,)
+        if return_state:
+            out += ((pop, en),)
+        return out
 
     def predictive_gradients(self, x):
         """(grad_mean, grad_var) at x, each (n, input_dim).  gpy_regression.py:179-223."""

@@ -32,6 +32,7 @@ SIMULATOR_STREAM_BASE = 0x53494D0000000000  # "SIM"
 PROPOSAL_STREAM_BASE = 0x474D525653000000   # "GMRVS"; + 2 x the redraw round
 ROMC_STREAM_BASE = 0x524F4D4300000000       # "ROMC"; + the region's position in the posterior
 SLICE_GAMMA_STREAM_BASE = 0x534C494345000000  # "SLICE"; + the problem's position in the call
+GP_MINIMIZE_STREAM_BASE = 0x44454D494E000000  # "DEMIN": the search for the GP mean's minimiser (HipGPRegression.minimize_mean)
 
 
 def _seed_of(random_state):

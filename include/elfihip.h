@@ -1293,6 +1293,61 @@ int elfihip_gp_lcb_minimize(elfihip_gp* gp, const double* starts, int64_t S, con
  * device / host milliseconds), 2 = + active points and device time of every round, 0 = nothing. */
 int elfihip_gp_set_acq_options(elfihip_gp* gp, int host_threads, int trace);
 
+/* GPyRegression.predict_mean alone (gpy_regression.py:98-147, the mean of :127-140): mu_s = sum_i (k(x_s, X_i) + s_b) alpha_i
+ * for S host points Xs (S, d) row-major, mu (S).  No triangular product and none of the prediction scratch is touched: O(n d)
+ * per point.  The terms are those of elfihip_gp_predict -- r2 = (|x|^2 + |X_i|^2) - 2 x.X_i clipped at 0,
+ * k = s_f exp(r2 (-1 / 2 l^2)), |x|^2 summed on the host in ascending order of the dimension -- in a FIXED order of
+ * summation that depends on n alone: one workgroup of 256 threads per point; thread t adds the terms i = t, t + 256,
+ * t + 512, ... in ascending order; the 64 lanes of each wave are added by the xor butterfly (distances 32, 16, 8, 4, 2, 1);
+ * the four waves as ((w0 + w1) + w2) + w3.  So one call with S points gives the bits of S calls with one point, and the
+ * result differs from elfihip_gp_predict's mean (256-row blocks, then the blocks in order) by the order of n additions:
+ * at most 2 n 2^-53 sum_i |alpha_i| (s_f + s_b).  Every accepted d (1 ... 256); S from 0 to 2^31 - 1 (one workgroup per
+ * point in one launch; ELFIHIP_ERR_ARG beyond). */
+int elfihip_gp_predict_mean(elfihip_gp* gp, const double* Xs, int64_t S, double* mu);
+
+/* The global minimiser of the GP mean inside the box [lower, upper] by differential evolution on the device: what
+ * stochastic_optimization (elfi/methods/bo/utils.py:9-37; SciPy's differential_evolution with a latin-hypercube start and
+ * polish) computes for BayesianOptimization.extract_result (elfi/methods/inference/bolfi.py:180-199), one GP prediction per
+ * trial vector.  Here a generation is ONE launch (workgroup i makes member i's trial, evaluates the mean at it as
+ * elfihip_gp_predict_mean does, and selects), the populations alternate between two device buffers, and the host reads the
+ * converged flag once per chunk of generations (elfihip_gp_set_minimize_chunk); launches after convergence pass the
+ * population through.
+ *
+ * The algorithm is SciPy's defaults (strategy best1bin, dither (0.5, 1), recombination 0.7, init latinhypercube) in their
+ * DEFERRED form (updating='deferred'); tests/de_ref.py states it in NumPy:
+ *   population   NP = max(5, popsize d) members in unit coordinates; unit p maps to x = (lo + hi) / 2 + (p - 1/2) |hi - lo|.
+ *                Start: member i, dimension j = (perm_j(i) + u_ij) / NP, perm_j the stable argsort of NP uniforms.
+ *   generation g = 1, 2, ...: one dither F = 1/2 + u / 2.  For member i: r0 = floor(u (NP - 1)), plus one if >= i;
+ *                r1 = floor(u (NP - 2)), plus one if >= min(i, r0), then plus one if >= max(i, r0) -- so r0 != r1, both != i;
+ *                fill point floor(u d); trial_j = b_j + F (p_r0,j - p_r1,j) where j is the fill point or u_j < 0.7, else
+ *                p_i,j; b the member of lowest energy (lowest index on ties); a coordinate outside [0, 1] is redrawn
+ *                uniformly (SciPy's _ensure_constraint).  All NP trials are evaluated on the generation's OLD population;
+ *                a trial replaces its member when its energy is <= the member's.
+ *   stop         after generation g >= 1 when std(E) <= tol |mean(E)| (population standard deviation), or after maxiter
+ *                generations.
+ *   polish       elfihip_gp_lcb_minimize from the best member with beta = 0 (the mean and its analytic gradient, L-BFGS-B);
+ *                accepted only if the mean-only evaluation gives it a lower energy than the best member.
+ *   random       draw (generation g, member i, slot s) = the 53-bit uniform ((r0 << 21) | (r1 >> 11)) 2^-53 of the first
+ *   numbers      two words of Philox4x32-10 at counter (i (2 d + 4) + s, g, stream) under key seed (64-bit values: low
+ *                word first).  Slots: 0, 1 the indices r0, r1; 2 the fill point; 3 + j the crossover of dimension j;
+ *                3 + d + j its redraw; 3 + 2 d the dither (member 0's slot is the generation's).  Generation 0 is the
+ *                start: slot 3 + j the uniform perm_j orders by, slot 3 + d + j the u_ij.  No draw depends on how many
+ *                redraws happened.
+ * A non-finite energy ends the call with ELFIHIP_ERR_STATE.  Limits (ELFIHIP_ERR_ARG before any launch): popsize >= 1,
+ * popsize d <= 3840, maxiter >= 0, tol >= 0, lower < upper, all finite.
+ * x_out (d) and f_out: the minimiser and the mean there (mean-only evaluation).  info_out (4, or NULL): generations made,
+ * point evaluations (NP (generations + 1) + those of the polish), converged (0 / 1), polish accepted (0 / 1).  pop_out
+ * (NP, d) and energies_out (NP), each or NULL: the final unit population and its energies -- with maxiter = 0 the start
+ * population.
+ * Decided difference from the reference: SciPy updates immediately, draws from MT19937, and the number of its draws
+ * depends on the data; a run here is another, equally valid search for the same quantity. */
+int elfihip_gp_minimize_mean(elfihip_gp* gp, const double* lower, const double* upper, uint64_t seed, uint64_t stream,
+                             int popsize, int maxiter, double tol, int polish, double* x_out, double* f_out,
+                             int64_t* info_out, double* pop_out, double* energies_out);
+/* Generations enqueued between two reads of the converged flag (0: the default, 8; at most 1024).  The result does not
+ * depend on it. */
+int elfihip_gp_set_minimize_chunk(elfihip_gp* gp, int generations);
+
 /* ExpIntVar (elfi/methods/bo/acquisition.py:629-821) needs the GP's posterior covariance between its M
  * integration points and each candidate: cov(p_i, q) = k(p_i, q) - k(p_i, X) K^-1 k(X, q), which the
  * reference forms per evaluate() call with cho_factor + cho_solve of the n x n matrix (:800-808).
