@@ -77,10 +77,18 @@ struct elfihip_ctx {
   bool step_lds_enabled = false;      // step_kernel's dynamic-LDS limit has been raised (gp_fit.hip)
   std::string err;
   // staging buffers for the host entry points
-  elfihip::DevBuf in, out, par, scratch;
-  elfihip::DevBuf stat;   // workgroup partials of the fused adaptive-distance pass (adaptive.hip; topk.hip owns `scratch`)
-  elfihip::DevBuf sel;    // twostage.hip: a block of subset distances and its survivors; the partial sums of the entropy
-                          // adjust.hip: the tile factors, the tile sums, the jobs' means and coefficients
+  elfihip::DevBuf in, out, par;
+  // `scratch` and `sel` are work space that a call borrows: the calls of a context are ordered by its stream, a user reserves
+  // what it needs (DevBuf::reserve may move the buffer: no address is cached across calls) and initialises what it reads, and
+  // nothing in them outlives the call that wrote it -- with one exception, the time-out flag of the resident selection
+  // (SelWork::err in `scratch`, topk_resident_err_dev), which the selection's caller reads in stream order before any other
+  // user of `scratch` is enqueued.
+  //   scratch  topk.hip (SelWork / SelState: histograms, the barrier counter, the flag), welford.hip, wstats.hip, gmix.hip,
+  //            synlik.hip, semibsl.hip, kliep.hip
+  //   sel      twostage.hip: a block of subset distances and its survivors; the partial sums of the entropy
+  //            adjust.hip: the tile factors, the tile sums, the jobs' means and coefficients
+  elfihip::DevBuf scratch, sel;
+  elfihip::DevBuf stat;   // workgroup partials of the fused adaptive-distance pass (adaptive.hip)
   // The event-driven simulators (event_sim.hpp; gillespie.hip, daycare.hip, scratch_assay.hip, bdm.hip) share one work buffer:
   // the counter work units are dealt from at offset 0, a 256-byte head, then the calling model's own work space (gillespie.hip:
   // the observations when the caller keeps none; daycare.hip: the sorted observed rows, and the status, carriage masks and

@@ -922,9 +922,10 @@ int elfihip_topk_smallest(elfihip_ctx* ctx, const double* D, int64_t n, int64_t 
   for (int attempt = 0; attempt < 2; ++attempt) {
     ELFIHIP_TRY(topk_dev_impl(ctx, dD, n, stride, k, dv, di, attempt == 1));
     unsigned int err = 0;
-    if (attempt == 0)  // the resident form's barrier time-out flag (offset of SelWork::err in the scratch buffer)
-      ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(&err, reinterpret_cast<const char*>(ctx->scratch.p) + offsetof(SelWork, err),
-                                            sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    // the resident form's barrier time-out flag.  The nine-launch form (topk_form 1) has none: its scratch holds a SelState,
+    // which on a fresh context ends before SelWork::err and on a used one has other contents there
+    const void* flag = attempt == 0 ? topk_resident_err_dev(ctx) : nullptr;
+    if (flag) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(&err, flag, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
     ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(vals, dv, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(idx, di, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));

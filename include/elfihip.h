@@ -79,7 +79,11 @@ const char* elfihip_last_error(const elfihip_ctx* ctx);
  * the context's own stream.  The own stream is NON-BLOCKING: it is not ordered against
  * the null stream or any other stream, so a caller that fills device buffers elsewhere
  * (the *_dev entry points) either adopts that stream here or synchronises it before the
- * call; the *_dev entry points themselves are asynchronous on the context's stream. */
+ * call; the *_dev entry points themselves are asynchronous on the context's stream.
+ * They are not the only ones: elfihip_gp_factorize, elfihip_gp_extend and
+ * elfihip_gp_nlml_grad wait for a ticket, not for the stream, and return while rows of
+ * alpha are still being written on it.  A caller that switches streams synchronises the
+ * old one first (as tests/stream_order.py: adopted_stream does); this call does not. */
 int elfihip_ctx_set_stream(elfihip_ctx* ctx, void* hip_stream);
 int elfihip_ctx_synchronize(elfihip_ctx* ctx);
 /* Device properties the roofline needs: CU count, clock (kHz), memory clock (kHz),
