@@ -56,6 +56,8 @@ struct elfihip_gp {
   int* info = nullptr;      // device, one word: 1-based index of the first non-positive pivot, 0 if none
   double* h_fit = nullptr;  // pinned, device-visible: sum log L_ii, z'z and the pivot report of the latest rebuild;
                             // words 15 / 14: tickets of the latest rebuild / hyper-gradient (host_wait_ticket)
+  double* h_ard = nullptr;  // pinned, device-visible, d words: the per-dimension sums of the latest ARD hyper-gradient
+                            // (gp_hyper.hip; made on the first elfihip_gp_nlml_grad_ard, behind the same ticket word 14)
   unsigned long long fit_ticket = 0, hyper_ticket = 0;
   // integration points of ExpIntVar (elfihip_gp_set_integration_points): V_P = L^-1 K(X, P) stored k-major
   double* VP = nullptr;     // (np, m_pad)

@@ -1423,6 +1423,7 @@ int elfihip_gp_free(elfihip_gp* gp) {
   if (gp->info) (void)hipFree(gp->info);
   if (gp->h_stage) (void)hipHostFree(gp->h_stage);
   if (gp->h_fit) (void)hipHostFree(gp->h_fit);
+  if (gp->h_ard) (void)hipHostFree(gp->h_ard);
   for (auto e : gp->pev)
     if (e) (void)hipEventDestroy(e);
   if (gp->VP) (void)hipFree(gp->VP);

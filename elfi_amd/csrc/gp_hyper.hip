@@ -15,6 +15,9 @@
 // the tile (a d-long dot product per entry, noise next to the n/2-long one just finished), so
 // K^-1 is never written to memory unless the caller asks for it (GPy's `woodbury_inv`).
 // Flops: n^3/3 on v_mfma_f64_16x16x4_f64; HBM: WT read once per tile row pair through L2/MALL.
+// With one lengthscale per input dimension (ARD; elfihip_gp_nlml_grad_ard) the lengthscale's sum is also wanted split by
+// dimension, sum(dL/dK * K_rbf * (X_ic - X_jc)^2): d more contractions in the same epilogue, in a second instantiation
+// of the kernel.
 #include <algorithm>
 #include <vector>
 
@@ -39,12 +42,20 @@ struct HyperArgs {
   const double* x2;
   const double* alpha;
   double* Kinv;   // optional (cap, lda) output, lower tiles
-  double* part;   // (items, 4) partial sums of every (tile, k chunk)
+  double* part;   // (items, 4) partial sums of every (tile, k chunk); ARD: (items, 4 + dp), the d per-dimension sums behind the four
   int64_t lda, n, np;
   int dp, x_in_lds;
   double var, neg_half_inv_ls2;
+  int d, red_off;   // ARD only: input dimension; where the reduction scratch starts in LDS (doubles), beyond the two X blocks
 };
 
+// ARD: the same tile with the per-dimension contractions behind the four sums (elfihip_gp_nlml_grad_ard) --
+//     part[4 + c] = sum_ij dL/dK_ij K_rbf,ij (X_ic - X_jc)^2,   c < d.
+// d reaches 256, so the sums cannot all live in registers: once the four sums are taken, the tile entry a thread holds is
+// overwritten with E = wt D K_rbf (0 outside the triangle) and the dimensions are the OUTER loop, one accumulator at a
+// time.  X is still read while the waves reduce, so the scratch lies beyond the X blocks (H.red_off): 16 doubles of the
+// four sums, then (4 waves, d).  ARD = false is the kernel elfihip_gp_nlml_grad has always launched.
+template <bool ARD>
 __global__ __launch_bounds__(256) void kinv_grad_kernel(HyperArgs H) {
   extern __shared__ __align__(16) double lds[];
   const int64_t b = blockIdx.x;
@@ -120,9 +131,38 @@ __global__ __launch_bounds__(256) void kinv_grad_kernel(HyperArgs H) {
           s_ls += wt * D * krbf * r2;
           s_bias += wt * D;
           if (gi == gj) s_noise += D;
+          if constexpr (ARD) acc.c[i][j][r] = wt * D * krbf;
+        } else if constexpr (ARD) {
+          acc.c[i][j][r] = 0.0;
         }
       }
     }
+  double* red = lds;
+  if constexpr (ARD) {
+    red = lds + H.red_off;
+    double* wsum = red + 16;
+    const int d = H.d;
+    for (int c = 0; c < d; ++c) {   // (columns d..dp-1 of X are zero: nothing to add)
+      double xj[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) xj[j] = xj_base[(wc * 64 + j * 16 + (l & 15)) * pitch + c];
+      double s = 0.0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const double a = xi_base[(wr * 64 + i * 16 + (l >> 4) + 4 * r) * pitch + c];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const double t = a - xj[j];
+            s = fma(acc.c[i][j][r] * t, t, s);
+          }
+        }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      if (l == 0) wsum[w * d + c] = s;
+    }
+  }
   // fixed-order workgroup reduction: butterfly inside the wave, then the four waves in order
   __syncthreads();
   double v[4] = {s_var, s_ls, s_bias, s_noise};
@@ -130,12 +170,19 @@ __global__ __launch_bounds__(256) void kinv_grad_kernel(HyperArgs H) {
   for (int q = 0; q < 4; ++q) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, 64);
-    if (l == 0) lds[w * 4 + q] = v[q];
+    if (l == 0) red[w * 4 + q] = v[q];
   }
   __syncthreads();
+  const int stride = ARD ? 4 + H.dp : 4;
   if (threadIdx.x < 4) {
     const int q = threadIdx.x;
-    H.part[b * 4 + q] = ((lds[q] + lds[4 + q]) + lds[8 + q]) + lds[12 + q];
+    H.part[b * stride + q] = ((red[q] + red[4 + q]) + red[8 + q]) + red[12 + q];
+  }
+  if constexpr (ARD) {
+    const double* wsum = red + 16;
+    const int d = H.d;
+    for (int c = threadIdx.x; c < d; c += 256)
+      H.part[b * stride + 4 + c] = ((wsum[c] + wsum[d + c]) + wsum[2 * d + c]) + wsum[3 * d + c];
   }
 }
 
@@ -159,7 +206,40 @@ __global__ __launch_bounds__(256) void hyper_reduce_kernel(const double* part, i
   if (threadIdx.x == 0) post_ticket(red + 12, ticket);   // (red = h_fit + 2: word 14; lanes 0-3 are one wave: their stores precede the fence)
 }
 
-static int hyper_grad_impl(elfihip_gp* gp, bool store_kinv, double* grad) {
+// The ARD form's final reduction: out[q] = sum over items of part[item][q] for the nq = 4 + d sums, fixed order, one
+// workgroup.  The 256 threads are (256 / qw) item slices x qw sums (qw: the power of two >= nq, at most 256): a thread adds
+// every (256 / qw)-th item of its sum, the slices are folded as a tree, and for nq > 256 the sums are taken in rounds.
+// The four sums go to red[2..5] (h_fit words 4..7, where the isotropic form leaves them), the d sums to dim[0..d-1].
+__global__ __launch_bounds__(256) void hyper_reduce_ard_kernel(const double* part, int64_t nitems, int stride, int nq, int qw,
+                                                               double* red, double* dim, unsigned long long ticket) {
+  __shared__ double s[256];
+  const int t = threadIdx.x, ql = t & (qw - 1), sl = t / qw, ns = 256 / qw;
+  for (int q0 = 0; q0 < nq; q0 += qw) {
+    const int q = q0 + ql;
+    double a = 0.0;
+    if (q < nq)
+      for (int64_t it = sl; it < nitems; it += ns) a += part[it * stride + q];
+    s[t] = a;
+    __syncthreads();
+    for (int off = ns >> 1; off > 0; off >>= 1) {
+      if (sl < off) s[t] += s[t + off * qw];
+      __syncthreads();
+    }
+    if (sl == 0 && q < nq) {
+      if (q < 4)
+        red[2 + q] = s[t];
+      else
+        dim[q - 4] = s[t];
+    }
+    __syncthreads();
+  }
+  // the results were stored by up to four waves: each makes its own visible to the host, and only then is the ticket posted
+  __threadfence_system();
+  __syncthreads();
+  if (t == 0) post_ticket(red + 12, ticket);
+}
+
+static int hyper_grad_impl(elfihip_gp* gp, bool store_kinv, double* grad, double* grad_dim = nullptr) {
   elfihip_ctx* ctx = gp->ctx;
   if (!gp->factored)
     return fail(ctx, ELFIHIP_ERR_STATE, "GP is not factorised (call elfihip_gp_factorize first)");
@@ -197,7 +277,17 @@ static int hyper_grad_impl(elfihip_gp* gp, bool store_kinv, double* grad) {
   std::stable_sort(items.begin(), items.end(),
                    [](const HyperItem& a, const HyperItem& c) { return a.k1 - a.k0 > c.k1 - c.k0; });
   const int64_t nitems = cached ? gp->hyper_items_n : (int64_t)items.size();
-  const size_t part_bytes = (size_t)nitems * 4 * sizeof(double);
+  const bool ard = grad_dim != nullptr;
+  const int stride = ard ? 4 + gp->dp : 4;
+  const size_t part_bytes = (size_t)nitems * stride * sizeof(double);
+  if (ard && !gp->h_ard) {   // pinned like h_fit: the d sums are read after the ticket, without a copy
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&gp->h_ard), (size_t)gp->d * sizeof(double),
+                                 hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) {
+      gp->h_ard = nullptr;
+      return fail(ctx, ELFIHIP_ERR_NOMEM, "pinned area of the per-dimension sums: %s", hipGetErrorString(e));
+    }
+  }
   ELFIHIP_CHECK_HIP(ctx, gp->ws.reserve(part_bytes));
   // the work list depends on the padded size only: uploaded once per size (a search evaluates ~100 gradients at one size)
   const int64_t list_key = store_kinv ? -np : np;
@@ -227,11 +317,28 @@ static int hyper_grad_impl(elfihip_gp* gp, bool store_kinv, double* grad) {
   const size_t xlds = 2 * (size_t)NB * (gp->dp + 1) * sizeof(double);
   H.x_in_lds = xlds <= 96 * 1024;
   if (H.x_in_lds && xlds > lds) lds = xlds;
-  ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kinv_grad_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  H.d = gp->d;
+  H.red_off = H.x_in_lds ? (int)(xlds / sizeof(double)) : 0;
+  if (ard) {   // scratch of the reduction behind the X blocks: 16 + (4 waves, d) doubles (X in LDS means d <= 44: 92160 + 1536
+               // bytes at most; else the 8320 bytes at d = 256 fit the GEMM's staging area)
+    const size_t need = ((size_t)H.red_off + 16 + 4 * (size_t)gp->d) * sizeof(double);
+    if (need > lds) lds = need;
+  }
+  const void* kern = ard ? reinterpret_cast<const void*>(kinv_grad_kernel<true>)
+                         : reinterpret_cast<const void*>(kinv_grad_kernel<false>);
+  ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   prof_mark(gp, 0);
-  hipLaunchKernelGGL(kinv_grad_kernel, dim3((unsigned)nitems), dim3(256), lds, st, H);
-  hipLaunchKernelGGL(hyper_reduce_kernel, dim3(1), dim3(256), 0, st, H.part, nitems, gp->h_fit + 2, ++gp->hyper_ticket);   // pinned: no copy
+  if (ard) {
+    const int nq = 4 + gp->d;
+    int qw = 1;
+    while (qw < nq && qw < 256) qw <<= 1;
+    hipLaunchKernelGGL(kinv_grad_kernel<true>, dim3((unsigned)nitems), dim3(256), lds, st, H);
+    hipLaunchKernelGGL(hyper_reduce_ard_kernel, dim3(1), dim3(256), 0, st, H.part, nitems, stride, nq, qw, gp->h_fit + 2,
+                       gp->h_ard, ++gp->hyper_ticket);
+  } else {
+    hipLaunchKernelGGL(kinv_grad_kernel<false>, dim3((unsigned)nitems), dim3(256), lds, st, H);
+    hipLaunchKernelGGL(hyper_reduce_kernel, dim3(1), dim3(256), 0, st, H.part, nitems, gp->h_fit + 2, ++gp->hyper_ticket);   // pinned: no copy
+  }
   prof_mark(gp, 1);
   ELFIHIP_TRY(launch_status(ctx, "kinv_grad_kernel"));
   if (gp->profile)   // (event times are read below)
@@ -250,10 +357,18 @@ static int hyper_grad_impl(elfihip_gp* gp, bool store_kinv, double* grad) {
     grad[2] = s[2];
     grad[3] = s[3];
   }
+  if (ard) {
+    const double ls3 = gp->ls * gp->ls * gp->ls;
+    for (int c = 0; c < gp->d; ++c) grad_dim[c] = gp->h_ard[c] / ls3;
+  }
   return ELFIHIP_OK;
 }
 
 int form_kinv_impl(elfihip_gp* gp) { return hyper_grad_impl(gp, true, nullptr); }
+
+static double log_marginal_of(const elfihip_gp* gp) {
+  return 0.5 * (-(double)gp->n * 1.8378770664093453 /* log(2 pi) */ - gp->logdet - gp->yKy);
+}
 
 }  // namespace elfihip
 
@@ -266,8 +381,16 @@ int elfihip_gp_nlml_grad(elfihip_gp* gp, double* log_marginal, double* grad) {
   ELFIHIP_REQUIRE(gp->ctx, grad != nullptr, "grad is NULL");
   DeviceGuard g(gp->ctx->device);
   ELFIHIP_TRY(hyper_grad_impl(gp, false, grad));
-  if (log_marginal)
-    *log_marginal = 0.5 * (-(double)gp->n * 1.8378770664093453 /* log(2 pi) */ - gp->logdet - gp->yKy);
+  if (log_marginal) *log_marginal = log_marginal_of(gp);
+  return ELFIHIP_OK;
+}
+
+int elfihip_gp_nlml_grad_ard(elfihip_gp* gp, double* log_marginal, double* grad, double* grad_dim) {
+  if (!gp) return fail(nullptr, ELFIHIP_ERR_ARG, "gp is NULL");
+  ELFIHIP_REQUIRE(gp->ctx, grad != nullptr && grad_dim != nullptr, "grad or grad_dim is NULL");
+  DeviceGuard g(gp->ctx->device);
+  ELFIHIP_TRY(hyper_grad_impl(gp, false, grad, grad_dim));
+  if (log_marginal) *log_marginal = log_marginal_of(gp);
   return ELFIHIP_OK;
 }
 

@@ -269,6 +269,14 @@ class GPHandle:
         self._check(self.lib.elfihip_gp_nlml_grad(self.h, C.byref(lz), _lib.ptr(g)))
         return lz.value, g
 
+    def nlml_grad_ard(self):
+        """(log marginal likelihood, d logZ / d (var, ls, bias, noise), (d,) the lengthscale's derivative split by input
+        dimension) at the current factorisation (include/elfihip.h: elfihip_gp_nlml_grad_ard)."""
+        lz = C.c_double()
+        g, gd = np.empty(4), np.empty(self.d)
+        self._check(self.lib.elfihip_gp_nlml_grad_ard(self.h, C.byref(lz), _lib.ptr(g), _lib.ptr(gd)))
+        return lz.value, g, gd
+
     def form_kinv(self):
         self._check(self.lib.elfihip_gp_form_kinv(self.h))
 
@@ -299,6 +307,121 @@ class GPHandle:
         return x, f, it, ne.value
 
 
+class DiagonalScaling:
+    """One lengthscale per input dimension (ARD) over a handle that knows a single one -- the transform, written once.
+
+    An RBF kernel with lengthscales l_c is the RBF kernel with lengthscale 1 on u = x / l.  This mix-in sits in front of
+    a handle with GPHandle's methods (ScaledGPHandle: the device object; tests: a NumPy stand-in), talks to it in u with
+    ls = 1 and presents ORIGINAL coordinates to every caller: points, evidence and bounds go in divided by l; locations
+    come back multiplied by l; gradients w.r.t. x come back divided by l (d/dx = (1/l) d/du); the gradient of the log
+    prior goes in multiplied by l (grad_u log p = l grad_x log p).  Posterior values, the log marginal likelihood and
+    unit-box coordinates do not depend on the scale.  A new l re-scales the evidence: the handle below gets it again,
+    from the copy kept here in original coordinates."""
+
+    ell = None      # (d,) lengthscales; ones until set_hyper gives others
+    _Xo = None      # evidence in original coordinates, (n, d) and (n, 1)
+    _yo = None
+
+    def _scale(self):
+        if self.ell is None:
+            self.ell = np.ones(self.d)
+        return self.ell
+
+    def _u(self, x):
+        return np.asarray(x, dtype=np.float64).reshape(-1, self.d) / self._scale()
+
+    def _ubounds(self, bounds):
+        """(bounds in u, lower and upper in x): a location that comes back is clipped to the box it was asked for in,
+        since (b / l) l need not be b in the last bit."""
+        lo, hi = check_minimize_arguments(self.d, bounds)
+        return list(zip(lo / self._scale(), hi / self.ell)), lo, hi
+
+    def set_hyper(self, var, ls, bias, noise):
+        """ls: (d,) lengthscales, or one number for all of them."""
+        ell = np.array(np.broadcast_to(np.asarray(ls, dtype=np.float64).reshape(-1), (self.d,)))
+        if not np.all(ell > 0):
+            raise ValueError('lengthscales must be positive')
+        rescale = not np.array_equal(ell, self._scale())
+        self.ell = ell
+        super().set_hyper(var, 1.0, bias, noise)
+        if rescale and self._Xo is not None:
+            super().set_data(self._Xo / ell, self._yo)     # the evidence below belongs to the old scale
+
+    def _keep(self, X, y, fresh):
+        X = np.array(X, dtype=np.float64).reshape(-1, self.d)
+        y = np.array(y, dtype=np.float64).reshape(-1, 1)
+        if fresh or self._Xo is None:
+            self._Xo, self._yo = X, y
+        else:
+            self._Xo, self._yo = np.concatenate([self._Xo, X]), np.concatenate([self._yo, y])
+        return X / self._scale(), y
+
+    def set_data(self, X, y):
+        return super().set_data(*self._keep(X, y, True))
+
+    def append(self, X, y):
+        return super().append(*self._keep(X, y, False))
+
+    def extend(self, X, y):
+        return super().extend(*self._keep(X, y, False))
+
+    def get(self, which):
+        out = super().get(which)
+        return out * self._scale() if which == 3 else out
+
+    def predict(self, x, noiseless=False):
+        return super().predict(self._u(x), noiseless=noiseless)
+
+    def predict_mean(self, x):
+        return super().predict_mean(self._u(x))
+
+    def predict_grad(self, x):
+        mu, var, dmu, dvar = super().predict_grad(self._u(x))
+        return mu, var, dmu / self.ell, dvar / self.ell
+
+    def minimize_mean(self, bounds, **kw):
+        ub, lo, hi = self._ubounds(bounds)
+        out = super().minimize_mean(ub, **kw)    # (x, f, info, population in unit coordinates, energies)
+        return (np.clip(out[0] * self.ell, lo, hi),) + tuple(out[1:])
+
+    def set_integration_points(self, points):
+        return super().set_integration_points(self._u(points))
+
+    def cross_cov(self, x):
+        return super().cross_cov(self._u(x))
+
+    def maxvar(self, x, eps, prior_pdf, prior_grad_logpdf):
+        glog = np.asarray(prior_grad_logpdf, dtype=np.float64).reshape(-1, self.d) * self._scale()
+        val, grad = super().maxvar(self._u(x), eps, prior_pdf, glog)
+        return val, grad / self.ell
+
+    def expintvar(self, x, eps, w_int, mean_int, var_int):
+        return super().expintvar(self._u(x), eps, w_int, mean_int, var_int)
+
+    def lcb(self, x, beta, with_grad=True):
+        val, grad = super().lcb(self._u(x), beta, with_grad)
+        return val, None if grad is None else grad / self.ell
+
+    def nlml_grad(self):
+        """(log marginal likelihood, d logZ / d (var, l_1 .. l_d, bias, noise)): d logZ / d l_c = grad_dim[c] / l_c."""
+        lz, g, gd = super().nlml_grad_ard()
+        return lz, np.concatenate([g[:1], gd / self._scale(), g[2:]])
+
+    def kernel_matrix(self, A, B=None):
+        return super().kernel_matrix(self._u(A), None if B is None else self._u(B))
+
+    def lcb_minimize(self, starts, bounds, beta, maxiter=1000):
+        """The search runs in the scaled coordinates (bounds and starts divided by l): a valid L-BFGS-B search of the same
+        surface, not the iterates of a search in x."""
+        ub, lo, hi = self._ubounds(bounds)
+        x, f, it, ne = super().lcb_minimize(self._u(starts), ub, beta, maxiter=maxiter)
+        return np.clip(x * self.ell, lo, hi), f, it, ne
+
+
+class ScaledGPHandle(DiagonalScaling, GPHandle):
+    """GPHandle for an RBF kernel with one lengthscale per input dimension: the device object holds x / l under ls = 1."""
+
+
 # ---- the small part of the GPy object graph that ELFI code touches ---------------------------
 def stochastic_optimization(fun, bounds, maxiter=1000, polish=True, seed=0):
     """stochastic_optimization of the reference (elfi/methods/bo/utils.py:9-37): same signature, same return value
@@ -325,10 +448,10 @@ def _same_bounds(a, b):
 
 
 class _Param:
-    """Stands in for a paramz Param: float(p), p[0], p.values."""
+    """Stands in for a paramz Param: float(p), p[0], p.values (the lengthscales of an ARD kernel: d values)."""
 
     def __init__(self, value):
-        self.values = np.array([float(value)])
+        self.values = np.array(value, dtype=np.float64).reshape(-1)
 
     def __float__(self):
         return float(self.values[0])
@@ -387,7 +510,7 @@ class _GPShim:
     @property
     def param_array(self):
         h = self._m._hyper
-        return np.array([h['var'], h['ls'], h['bias'], h['noise']])
+        return np.concatenate([np.ravel(h[k]) for k in ('var', 'ls', 'bias', 'noise')]).astype(np.float64)
 
     @property
     def posterior(self):
@@ -401,9 +524,10 @@ class _GPShim:
 
     def __str__(self):
         h = self._m._hyper
-        return ("HipGPRegression  n=%d  log-marginal=%.6g\n  rbf.variance %.6g\n  rbf.lengthscale %.6g\n"
+        ls = '%.6g' % h['ls'] if np.ndim(h['ls']) == 0 else '(%s)' % ', '.join('%.6g' % v for v in h['ls'])
+        return ("HipGPRegression  n=%d  log-marginal=%.6g\n  rbf.variance %.6g\n  rbf.lengthscale %s\n"
                 "  bias.variance %.6g\n  Gaussian_noise.variance %.6g" %
-                (self.num_data, self._m._log_marginal, h['var'], h['ls'], h['bias'], h['noise']))
+                (self.num_data, self._m._log_marginal, h['var'], ls, h['bias'], h['noise']))
 
 
 _REFERENCE_SUBCLASSES = {}
@@ -442,6 +566,7 @@ class HipGPRegression:
         return object.__new__(cls)
 
     _hip_origin = None
+    ard = False     # (an object pickled before the keyword existed is isotropic)
 
     def __reduce__(self):
         # pickle / copy by the importable class: the two-base class is re-derived where the object is rebuilt
@@ -477,6 +602,9 @@ class HipGPRegression:
         self.parameter_names = parameter_names
         self.input_dim = input_dim
         self.bounds = bounds
+        # ard=True: one lengthscale per parameter ([GPy-upstream] RBF(input_dim, ARD=True)); `_hyper['ls']` is then a tuple
+        # of input_dim floats (a tuple, so that dictionaries of hyper-parameters still compare with ==), shown as an array
+        self.ard = bool(gp_params.pop('ard', False))
         self.gp_params = gp_params
         self.optimizer = optimizer
         self.max_opt_iters = max_opt_iters
@@ -583,13 +711,23 @@ class HipGPRegression:
         # GPy's own defaults (variance 1, lengthscale 1 [GPy-upstream]); set_prior does not move the
         # values.  Only the noise gets a data-driven start (:255).
         noise_var = self.gp_params.get('noise_var') or np.max(y)**2. / 100.
-        return dict(var=1.0, ls=1.0, bias=1.0, noise=float(noise_var))
+        return dict(var=1.0, ls=self._ls_value(1.0), bias=1.0, noise=float(noise_var))
+
+    def _ls_value(self, ls):
+        """A lengthscale argument as `_hyper` stores it: a float, or for an ARD model a tuple of input_dim floats (from one
+        number for all dimensions or from input_dim values); ValueError for any other length."""
+        v = np.asarray(ls, dtype=np.float64).reshape(-1)
+        want = self.input_dim if self.ard else 1
+        if v.size not in (1, want):
+            raise ValueError('ls has {} values; expected {}'.format(v.size, '1 or %d' % want if self.ard else 'one'))
+        return tuple(float(x) for x in np.broadcast_to(v, (want,))) if self.ard else float(v[0])
 
     def _init_gp(self, x, y):
         self._kernel_is_default = self.gp_params.get('noise_var') is None
         self._hyper = self._default_hyper(y)
         # Gamma priors from_EV(E, V=E) -> shape a = E^2/V = E, rate b = E/V = 1
-        # (gpy_regression.py:270-278) on lengthscale, rbf variance and bias variance; none on the noise
+        # (gpy_regression.py:270-278) on lengthscale, rbf variance and bias variance; none on the noise.  An ARD model's
+        # lengthscales each carry the lengthscale's prior ([GPy-upstream] set_prior on a vector parameter is elementwise)
         self._priors = {k: (E, 1.0) for k, E in self._prior_expectations(y).items()}
         self._X = np.empty((0, self.input_dim))
         self._Y = np.empty((0, 1))
@@ -601,7 +739,7 @@ class HipGPRegression:
             return False
         cap = max(512, int(2 ** np.ceil(np.log2(max(n, 1)))))
         old = self._handle
-        self._handle = GPHandle(self.input_dim, cap, ctx=_lib.default_context(self.device))
+        self._handle = (ScaledGPHandle if self.ard else GPHandle)(self.input_dim, cap, ctx=_lib.default_context(self.device))
         if self.acq_host_threads or self.acq_trace:
             self._handle.set_acq_options(self.acq_host_threads, self.acq_trace)
         if old is not None:
@@ -656,6 +794,8 @@ class HipGPRegression:
         their values) and rebuild the GP with them -- what `m._gp.rbf.variance = v` etc. followed by a refit do on a
         GPy model.  Until the next `optimize()` (an `update(..., optimize=True)` of the BOLFI loop) every update keeps
         these values.  Returns the hyper-parameters in use."""
+        if ls is not None:
+            ls = self._ls_value(ls)       # (a wrong number of lengthscales is an argument error, whatever the model's state)
         if self._gp is None:
             raise RuntimeError('no evidence yet: hyper-parameters belong to a GP that exists (call update first)')
         new = dict(self._hyper)
@@ -664,10 +804,10 @@ class HipGPRegression:
                 continue
             if k not in new:
                 raise ValueError("unknown hyper-parameter %r (expected var, ls, bias, noise)" % (k,))
-            new[k] = float(v)
+            new[k] = v if k == 'ls' else float(v)
         self._hyper = new
         self._refit()
-        return dict(self._hyper)
+        return self.hyperparameters
 
     @property
     def device_handle(self):
@@ -676,8 +816,11 @@ class HipGPRegression:
 
     @property
     def hyperparameters(self):
-        """dict(var, ls, bias, noise) in use (GPy: rbf.variance, rbf.lengthscale, bias.variance, Gaussian_noise.variance)."""
-        return None if self._gp is None else dict(self._hyper)
+        """dict(var, ls, bias, noise) in use (GPy: rbf.variance, rbf.lengthscale, bias.variance, Gaussian_noise.variance);
+        ls of an ARD model is an array of input_dim lengthscales."""
+        if self._gp is None:
+            return None
+        return dict(self._hyper, ls=np.array(self._hyper['ls'])) if self.ard else dict(self._hyper)
 
     def refit(self):
         """Rebuild the GP from all evidence with the current hyper-parameters (a full factorisation)."""

@@ -23,7 +23,11 @@ restated:
 Every objective / gradient evaluation is a full refit on the GPU through the C ABI
 (elfihip_gp_set_hyper + elfihip_gp_factorize + elfihip_gp_nlml_grad: Gram matrix, Cholesky,
 L^-T, and the K^-1 SYRK with the four kernel-derivative contractions fused into its epilogue);
-this module only holds the four-dimensional optimiser state.  "Parity unpinned": no reference
+this module only holds the four-dimensional optimiser state.  An ARD model (HipGPRegression(ard=True)) has one
+lengthscale per input dimension: its parameter vector is GPy's param_array, (variance, l_1 .. l_d, bias, noise) -- 3 + d
+numbers, every lengthscale under the lengthscale's Gamma prior -- and its gradient comes from elfihip_gp_nlml_grad_ard
+through the scaled handle (gp.py: DiagonalScaling).  An isotropic model's vector, order and numbers are what they were.
+"Parity unpinned": no reference
 test or fixture fixes the optimum; tests compare against the CPU oracle's
 restatement of the same algorithm and check descent / stationarity.
 """
@@ -33,6 +37,17 @@ from scipy.special import gammaln
 _LIM_VAL = 36.0
 _LOG_LIM_VAL = np.log(np.finfo(np.float64).max)
 NAMES = ('var', 'ls', 'bias', 'noise')
+
+
+def pack_hyper(h):
+    """The parameter vector of a dict of hyper-parameters, in GPy's order: (var, ls or l_1 .. l_d, bias, noise)."""
+    return np.concatenate([np.ravel(h[k]) for k in NAMES]).astype(np.float64)
+
+
+def unpack_hyper(theta, ard):
+    """Inverse of pack_hyper: floats, and for an ARD model the lengthscales as a tuple (gp.py: HipGPRegression._hyper)."""
+    theta = [float(t) for t in theta]
+    return dict(var=theta[0], ls=tuple(theta[1:-2]) if ard else theta[1], bias=theta[-2], noise=theta[-1])
 
 
 def logexp(phi):
@@ -69,7 +84,10 @@ class MarginalObjective:
         self._phi = None
         self._logz = None
         self._fail_count = 0
-        self._last_grad = np.zeros(4)
+        self.ard = bool(getattr(model, 'ard', False))
+        # the name each entry of the parameter vector takes its prior from
+        self.names = ('var',) + ('ls',) * (model.input_dim if self.ard else 1) + ('bias', 'noise')
+        self._last_grad = np.zeros(len(self.names))
         self.n_fits = 0
 
     def _fit(self, phi):
@@ -78,14 +96,14 @@ class MarginalObjective:
             return
         theta = logexp(phi)
         self._phi = None
-        self.handle.set_hyper(*theta)
+        self.handle.set_hyper(theta[0], theta[1:-2] if self.ard else theta[1], theta[-2], theta[-1])
         self._logz = self.handle.factorize()   # LinAlgError when K is not positive definite
         self._phi = phi.copy()
         self.n_fits += 1
 
     def _prior_terms(self, theta):
-        lp, dlp = 0.0, np.zeros(4)
-        for i, name in enumerate(NAMES):
+        lp, dlp = 0.0, np.zeros(len(self.names))
+        for i, name in enumerate(self.names):
             if name in self.priors:
                 a, b = self.priors[name]
                 t = theta[i]
@@ -232,7 +250,7 @@ def optimize_hyperparameters(model, max_iters=50):
     """MAP hyper-parameters for `model` (a fitted HipGPRegression); refits it at the optimum."""
     h0 = dict(model._hyper)
     obj = MarginalObjective(model)
-    phi0 = logexp_inv(np.array([h0[k] for k in NAMES]))
+    phi0 = logexp_inv(pack_hyper(h0))
     try:
         if model.optimizer == 'scg':
             phi, flog, nfev, status = scg(obj.f, obj.grad, phi0, maxiters=max_iters)
@@ -247,7 +265,7 @@ def optimize_hyperparameters(model, max_iters=50):
         model._refit()
         raise
     theta = logexp(phi)
-    model._hyper = dict(zip(NAMES, (float(t) for t in theta)))
+    model._hyper = unpack_hyper(theta, obj.ard)
     if obj._phi is not None and np.array_equal(obj._phi, np.asarray(phi, dtype=np.float64)):
         # the search's last evaluation WAS the optimum (SCG stops right after a successful step): the device GP holds that
         # very factorisation -- same hyper-parameters, bit for bit -- so the refit would only repeat it (one rebuild in

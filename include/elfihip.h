@@ -1254,6 +1254,15 @@ int elfihip_gp_profile(elfihip_gp* gp, int enable, double* phase_ms, int64_t* ph
  * Gaussian_noise.variance), grad[4], from dL/dK = 0.5 (alpha alpha^T - K^-1).  Priors and the
  * positivity transform are host-side scalars (elfi_amd/hyperopt.py).  Needs a factorised GP. */
 int elfihip_gp_nlml_grad(elfihip_gp* gp, double* log_marginal, double* grad);
+/* The same with the lengthscale's derivative split by input dimension, for an RBF kernel with one lengthscale per
+ * dimension (GPy: RBF(input_dim, ARD=True)).  grad[4] is what elfihip_gp_nlml_grad returns;
+ *     grad_dim[c] = sum_ij dL/dK_ij K_rbf,ij (X_ic - X_jc)^2 / lengthscale^3,   c < d,
+ * is d logZ / d (the lengthscale of dimension c alone) at the point where all of them equal the GP's lengthscale, so
+ * sum_c grad_dim[c] == grad[1] up to summation order.  The object itself stays isotropic: a caller with lengthscales l_c
+ * keeps the evidence as x / l with lengthscale 1 (elfi_amd/gp.py: ScaledGPHandle) and d logZ / d l_c is grad_dim[c] / l_c.
+ * The K^-1 tiles are those of elfihip_gp_nlml_grad; every tile's epilogue adds d contractions, reduced in a fixed order
+ * (two calls return the same bits).  Needs a factorised GP. */
+int elfihip_gp_nlml_grad_ard(elfihip_gp* gp, double* log_marginal, double* grad, double* grad_dim);
 /* Materialise K^-1 (GPy's posterior.woodbury_inv, read by gpy_regression.py:158) for
  * elfihip_gp_get(gp, 5, ...).  Not needed by predict / gradients / nlml_grad. */
 int elfihip_gp_form_kinv(elfihip_gp* gp);
