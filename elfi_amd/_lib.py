@@ -320,6 +320,8 @@ PROTOTYPES = {
     "elfihip_gp_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, c_void_pp]),
     "elfihip_gp_free": (C.c_int, [C.c_void_p]),
     "elfihip_gp_set_hyper": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "elfihip_gp_set_kernel": (C.c_int, [C.c_void_p, C.c_int]),
+    "elfihip_gp_get_kernel": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "elfihip_gp_set_data": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "elfihip_gp_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "elfihip_gp_factorize": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),

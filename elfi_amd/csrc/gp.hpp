@@ -3,6 +3,7 @@
 
 #include "common.hpp"
 
+#include <type_traits>
 #include <vector>
 
 namespace elfihip {
@@ -12,6 +13,70 @@ constexpr int FUSED_BELOW_NB = 97;  // block columns below which the fused-step 
                                     // 16.6 ms at n = 10240, 26.0 against 26.3 ms at 12288)
 constexpr double GP_JITTER = 1e-8;  // [GPy-upstream] ExactGaussianInference: Ky = K + (noise + 1e-8) I
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// ---- the covariance function, once ------------------------------------------------------------------------------------
+// Every site that evaluates the stationary part of the kernel needs two scalar functions of the squared distance r2 (formed
+// and clipped at 0 by the site), with a = sqrt(r2) / l:
+//     k(r2)                 the covariance
+//     g(r2) = dk / d(r2)    from which  grad_x k = 2 g (x - X),  dk/dl = -2 g r2 / l,  per ARD dimension -2 g D_c^2 / l_c
+//   kind 0 rbf       k = s_f exp(-r2 / 2l^2)                          g = -k / 2l^2
+//   kind 1 matern32  k = s_f (1 + sqrt3 a) exp(-sqrt3 a)              g = -(3 / 2l^2) s_f exp(-sqrt3 a)
+//   kind 2 matern52  k = s_f (1 + sqrt5 a + 5 a^2 / 3) exp(-sqrt5 a)  g = -(5 / 6l^2) s_f (1 + sqrt5 a) exp(-sqrt5 a)
+// g is finite at r = 0 for all three, and no site divides by r.  The sites carry g as the WEIGHT w = g / c, c = -1 / 2l^2
+// (the one constant the host hands over), because that is what their sums have always held for the RBF kernel, where w = k:
+// grad_x k = -(w / l^2) (x - X), dk/dl = w r2 / l^3.  Kernels are templates on the kind and the host picks the
+// instantiation (gp->kernel): the RBF instantiations keep the arithmetic they had before the other kinds existed.
+constexpr int KERNEL_RBF = 0, KERNEL_MATERN32 = 1, KERNEL_MATERN52 = 2;
+template <int KIND>
+struct CovFn {
+  static_assert(KIND >= KERNEL_RBF && KIND <= KERNEL_MATERN52, "unknown covariance function");
+  double var, c;   // s_f and c = -1 / 2l^2
+  __host__ __device__ __forceinline__ CovFn(double var_, double neg_half_inv_ls2) : var(var_), c(neg_half_inv_ls2) {}
+  // t = sqrt(nu2) a with nu2 = 3 or 5: sqrt(r2 nu2 / l^2), 0 at r2 = 0 (sqrt of an exact, clipped, non-negative number)
+  __host__ __device__ __forceinline__ double scaled_r(double r2) const {
+    return sqrt(r2 * ((KIND == KERNEL_MATERN32 ? -6.0 : -10.0) * c));
+  }
+  __host__ __device__ __forceinline__ double k(double r2) const {
+    if constexpr (KIND == KERNEL_RBF) {
+      return var * exp(r2 * c);
+    } else {
+      const double t = scaled_r(r2), e = var * exp(-t);
+      if constexpr (KIND == KERNEL_MATERN32) return (1.0 + t) * e;
+      return (1.0 + t + t * t * (1.0 / 3.0)) * e;
+    }
+  }
+  // k and the weight w = g / c = -2 l^2 dk/d(r2)
+  __host__ __device__ __forceinline__ void kw(double r2, double* k_out, double* w_out) const {
+    if constexpr (KIND == KERNEL_RBF) {
+      const double kv = var * exp(r2 * c);
+      *k_out = kv;
+      *w_out = kv;
+    } else {
+      const double t = scaled_r(r2), e = var * exp(-t);
+      if constexpr (KIND == KERNEL_MATERN32) {
+        *k_out = (1.0 + t) * e;
+        *w_out = 3.0 * e;
+      } else {
+        *k_out = (1.0 + t + t * t * (1.0 / 3.0)) * e;
+        *w_out = (5.0 / 3.0) * ((1.0 + t) * e);
+      }
+    }
+  }
+  __host__ __device__ __forceinline__ double g(double r2) const {
+    double kv, w;
+    kw(r2, &kv, &w);
+    return c * w;
+  }
+};
+// Host dispatch on the kind stored in the GP object: FN is a generic callable taking std::integral_constant<int, KIND>.
+template <typename FN>
+inline void dispatch_kernel(int kind, FN&& fn) {
+  switch (kind) {
+    case KERNEL_MATERN32: fn(std::integral_constant<int, KERNEL_MATERN32>()); break;
+    case KERNEL_MATERN52: fn(std::integral_constant<int, KERNEL_MATERN52>()); break;
+    default: fn(std::integral_constant<int, KERNEL_RBF>()); break;
+  }
+}
 }  // namespace elfihip
 
 struct elfihip_gp {
@@ -21,6 +86,7 @@ struct elfihip_gp {
   int64_t n = 0, np = 0;      // current evidence count, padded to a multiple of NB
   int64_t lda = 0;            // row pitch (doubles) of A and WT
   double var = 1, ls = 1, bias = 0, noise = 1;
+  int kernel = 0;             // covariance function (elfihip_gp_set_kernel): 0 rbf, 1 matern32, 2 matern52 (CovFn above)
   bool factored = false, has_kinv = false, wl_valid = false;
   bool kinv_sym = false;      // K^-1 complete (both triangles) and current: formed after a factorisation, bordered by extends
   // K^-1 lock-steps are VALIDATED once per K^-1 (formed after a full factorisation, then carried through extends by
@@ -128,6 +194,7 @@ inline void prof_add(elfihip_gp* gp, int phase, int from, int to) {
 }
 struct PredictWs {
   double *xs, *xs2, *kr, *kb, *part, *v, *u, *mu_part, *var_part, *g_part, *out;
+  double* kw;   // the gradient weights w = g / c beside kr (CovFn); the RBF kernel has w = k and kw == kr
   int nblk_k;   // blocks of the kstar kernel along i
   int nkc;      // k chunks
   int ngc;      // i chunks of the gradient kernel
@@ -178,8 +245,9 @@ int64_t dense_min_points(const elfihip_gp* gp);
 int form_kinv_impl(elfihip_gp* gp);
 // pieces of gp_predict.hip the dense path shares
 int ensure_wl_public(elfihip_gp* gp);
+// kw: where a Matern kind leaves its gradient weights (kstar_kernel); not touched for the RBF kernel
 void launch_kstar_passes(elfihip_gp* gp, const double* xs, const double* xs2, double* kr, double* kbt, double* mu_part,
-                         int nblk_k, unsigned npass);
+                         int nblk_k, unsigned npass, double* kw);
 void launch_finish_passes(elfihip_gp* gp, const double* mu_part, int nblk_k, const double* var_part, int nblk_v,
                           const double* g_part, int ngc, double* out, int s_left, int noiseless, double beta, int mode,
                           unsigned npass, double* host_out, unsigned long long* done_flags, unsigned long long done_value);

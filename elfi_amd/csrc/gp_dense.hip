@@ -170,7 +170,7 @@ struct DenseArgs {
   double* VT;           // [S_pad][np]
   double* var_part;     // [pass][nrb][16]
   // second product
-  const double* kr;     // [S_pad][np] kernel rows without the bias
+  const double* kr;     // [S_pad][np] weights of the gradient sums: the kernel rows without the bias (RBF), kw of kstar_kernel (Matern)
   const double* X;      // (np, dp)
   const double* alpha;
   const double* xs;     // [S_pad][dp]
@@ -346,7 +346,8 @@ static int predict_dense_round(elfihip_gp* gp, const double* Xs, int64_t S, int 
 int predict_dense_impl(elfihip_gp* gp, const double* Xs, int64_t S, int mode, int noiseless, double beta, double* mu,
                        double* var, double* dmu, double* dvar, double* val, double* grad) {
   const int d = gp->d;
-  int64_t cap = ((int64_t)512 << 20) / (24 * (gp->np > 0 ? gp->np : 1));
+  const int per_point = gp->kernel != KERNEL_RBF ? 32 : 24;   // bytes per point and row: a Matern kind keeps a fourth array (kw)
+  int64_t cap = ((int64_t)512 << 20) / (per_point * (gp->np > 0 ? gp->np : 1));
   cap = cap < 256 ? 256 : (cap > 4096 ? 4096 : cap);
   cap -= cap % 64;
   for (int64_t s0 = 0; s0 < S; s0 += cap) {
@@ -383,7 +384,8 @@ static int predict_dense_round(elfihip_gp* gp, const double* Xs, int64_t S, int 
   const size_t o_xs = take((size_t)S_pad * dp), o_xs2 = take((size_t)S_pad), o_kr = take((size_t)S_pad * np),
                o_kbt = take((size_t)S_pad * np), o_vt = take((size_t)S_pad * np),
                o_mu = take((size_t)npass * 16 * nblk_k), o_var = take((size_t)npass * nrb_max * 16),
-               o_g = take((size_t)npass * 16 * nrb_max * 2 * dp), o_out = take((size_t)npass * outsz);
+               o_g = take((size_t)npass * 16 * nrb_max * 2 * dp), o_out = take((size_t)npass * outsz),
+               o_kw = gp->kernel != KERNEL_RBF ? take((size_t)S_pad * np) : o_kr;   // gradient weights of a Matern kind
   ELFIHIP_CHECK_HIP(ctx, gp->ws_dense.reserve(off * sizeof(double)));
   double* base = gp->ws_dense.as<double>();
   // pinned staging: points + norms up, results down (one copy each way)
@@ -424,7 +426,8 @@ static int predict_dense_round(elfihip_gp* gp, const double* Xs, int64_t S, int 
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(base + o_xs, hx, n_in * sizeof(double), hipMemcpyHostToDevice, st));
   // (xs2 directly follows xs: S_pad * dp is a multiple of the workspace's 16-double granule)
   ELFIHIP_TRY(ensure_wl_public(gp));   // L^-1 row-wise is the FIRST product's matrix here
-  launch_kstar_passes(gp, base + o_xs, base + o_xs2, base + o_kr, base + o_kbt, base + o_mu, nblk_k, (unsigned)npass);
+  launch_kstar_passes(gp, base + o_xs, base + o_xs2, base + o_kr, base + o_kbt, base + o_mu, nblk_k, (unsigned)npass,
+                      base + o_kw);
   const int tm = gp->dense_tm > 0 ? gp->dense_tm : dense_tile_rows(gp, ncb);
   const int nrb = (int)(np / tm);
   DenseArgs D;
@@ -435,7 +438,7 @@ static int predict_dense_round(elfihip_gp* gp, const double* Xs, int64_t S, int 
   D.ncb = ncb;
   D.VT = base + o_vt;
   D.var_part = base + o_var;
-  D.kr = base + o_kr;
+  D.kr = base + o_kw;   // the epilogue weighs (x_s - X_i) with these: the kernel rows themselves for the RBF kernel
   D.X = gp->X;
   D.alpha = gp->alpha;
   D.xs = base + o_xs;

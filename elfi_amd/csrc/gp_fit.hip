@@ -30,7 +30,7 @@ namespace elfihip {
 
 // ------------------------------------------------------------------------- Gram matrix
 // K[i][j] for a 64x64 tile (lower tile pairs only), X.X^T on the matrix cores (k = padded d),
-// exp epilogue.  r^2 follows [GPy-upstream] Stationary._unscaled_dist: (|xi|^2 + |xj|^2) - 2 xi.xj,
+// covariance epilogue (CovFn<KIND>, gp.hpp: the RBF's exp or a Matern kind).  r^2 follows [GPy-upstream] Stationary._unscaled_dist: (|xi|^2 + |xj|^2) - 2 xi.xj,
 // clipped at 0, exactly 0 on the diagonal.  Rows/cols >= n are the identity (padding).
 // The y row block (rows np..np+127) is written by the tiles of the last tile row.
 struct GramArgs {
@@ -49,6 +49,7 @@ struct GramArgs {
 // the k loop visits the columns in the order of the unchunked loop, so the accumulation order does not depend on the chunking.
 constexpr int GRAM_KC = 64;
 
+template <int KIND>
 __global__ __launch_bounds__(256) void gram_kernel(GramArgs G) {
   extern __shared__ __align__(16) double sm[];
   const int pitch = (G.dp < GRAM_KC ? G.dp : GRAM_KC) + 1;  // odd pitch in doubles: bank-conflict free for column walks
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(256) void gram_kernel(GramArgs G) {
           double r2 = (G.x2[i] + G.x2[j]) + (-2.0 * acc[a][c][r]);
           r2 = r2 < 0.0 ? 0.0 : r2;   // (a NaN stays a NaN: it must reach the pivot test, not turn into distance 0)
           if (i == j) r2 = 0.0;
-          v = G.var * exp(r2 * G.neg_half_inv_ls2) + G.bias;
+          v = CovFn<KIND>(G.var, G.neg_half_inv_ls2).k(r2) + G.bias;
           if (i == j) v += G.diag_add;
         }
         G.A[i * G.lda + j] = v;
@@ -1273,7 +1274,9 @@ static int gp_factorize_attempt(elfihip_gp* gp, double diag_add, int* info_out) 
     G.ninfo = 1;
     const int64_t nt = np / 64;
     const size_t lds = 2 * 64 * (size_t)((gp->dp < GRAM_KC ? gp->dp : GRAM_KC) + 1) * sizeof(double);
-    hipLaunchKernelGGL(gram_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), lds, st, G);
+    dispatch_kernel(gp->kernel, [&](auto kind) {
+      hipLaunchKernelGGL(gram_kernel<decltype(kind)::value>, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), lds, st, G);
+    });
     ELFIHIP_TRY(launch_status(ctx, "gram_kernel"));
   }
   prof_mark(gp, 1);
@@ -1454,6 +1457,23 @@ int elfihip_gp_set_hyper(elfihip_gp* gp, double rbf_variance, double lengthscale
   gp->factored = false;
   gp->has_kinv = false;
   gp->kinv_sym = false;
+  return ELFIHIP_OK;
+}
+
+int elfihip_gp_set_kernel(elfihip_gp* gp, int kind) {
+  if (!gp) return fail(nullptr, ELFIHIP_ERR_ARG, "gp is NULL");
+  ELFIHIP_REQUIRE(gp->ctx, kind >= KERNEL_RBF && kind <= KERNEL_MATERN52, "kernel kind %d is not 0 (rbf), 1 (matern32) or 2 (matern52)",
+                  kind);
+  gp->kernel = kind;
+  gp->factored = false;
+  gp->has_kinv = false;
+  gp->kinv_sym = false;
+  return ELFIHIP_OK;
+}
+
+int elfihip_gp_get_kernel(const elfihip_gp* gp, int* kind) {
+  if (!gp || !kind) return fail(gp ? gp->ctx : nullptr, ELFIHIP_ERR_ARG, "gp or kind is NULL");
+  *kind = gp->kernel;
   return ELFIHIP_OK;
 }
 

@@ -9,6 +9,8 @@
 //     d logZ / d l   = sum(dL/dK * K_rbf * r^2) / l^3
 //     d logZ / d s_b = sum(dL/dK)
 //     d logZ / d s_n = trace(dL/dK)
+// For a Matern kind (CovFn, gp.hpp) K_rbf in the lengthscale's sum is the weight w = -2 l^2 dk/d(r^2): dk/dl = w r^2 / l^3 for
+// every kind, and w = k for the RBF kernel.
 // The factorisation already holds L^-T (upper triangular, gp_fit.hip), so K^-1 is one SYRK on
 // the matrix cores: tile (I, J), I >= J, is sum_{k >= I} WT[I][k] WT[J][k]^T.  The four
 // contractions are fused into that SYRK's epilogue -- K_rbf and r^2 are recomputed from X for
@@ -55,7 +57,7 @@ struct HyperArgs {
 // overwritten with E = wt D K_rbf (0 outside the triangle) and the dimensions are the OUTER loop, one accumulator at a
 // time.  X is still read while the waves reduce, so the scratch lies beyond the X blocks (H.red_off): 16 doubles of the
 // four sums, then (4 waves, d).  ARD = false is the kernel elfihip_gp_nlml_grad has always launched.
-template <bool ARD>
+template <bool ARD, int KIND>
 __global__ __launch_bounds__(256) void kinv_grad_kernel(HyperArgs H) {
   extern __shared__ __align__(16) double lds[];
   const int64_t b = blockIdx.x;
@@ -124,14 +126,15 @@ __global__ __launch_bounds__(256) void kinv_grad_kernel(HyperArgs H) {
           double r2 = (x2i + H.x2[gj]) + (-2.0 * dot[j]);
           r2 = r2 < 0.0 ? 0.0 : r2;
           if (gi == gj) r2 = 0.0;
-          const double krbf = H.var * exp(r2 * H.neg_half_inv_ls2);
+          double krbf, kwt;   // the covariance and the weight w = g / c of its lengthscale derivative (CovFn: w = k for the RBF kernel)
+          CovFn<KIND>(H.var, H.neg_half_inv_ls2).kw(r2, &krbf, &kwt);
           const double D = 0.5 * ((first_chunk ? ai * H.alpha[gj] : 0.0) - acc.c[i][j][r]);
           const double wt = gi == gj ? 1.0 : 2.0;  // the strict upper triangle mirrors the lower
           s_var += wt * D * krbf;
-          s_ls += wt * D * krbf * r2;
+          s_ls += wt * D * kwt * r2;
           s_bias += wt * D;
           if (gi == gj) s_noise += D;
-          if constexpr (ARD) acc.c[i][j][r] = wt * D * krbf;
+          if constexpr (ARD) acc.c[i][j][r] = wt * D * kwt;
         } else if constexpr (ARD) {
           acc.c[i][j][r] = 0.0;
         }
@@ -324,19 +327,26 @@ static int hyper_grad_impl(elfihip_gp* gp, bool store_kinv, double* grad, double
     const size_t need = ((size_t)H.red_off + 16 + 4 * (size_t)gp->d) * sizeof(double);
     if (need > lds) lds = need;
   }
-  const void* kern = ard ? reinterpret_cast<const void*>(kinv_grad_kernel<true>)
-                         : reinterpret_cast<const void*>(kinv_grad_kernel<false>);
+  const void* kern = nullptr;
+  dispatch_kernel(gp->kernel, [&](auto kind) {
+    constexpr int K = decltype(kind)::value;
+    kern = ard ? reinterpret_cast<const void*>(kinv_grad_kernel<true, K>) : reinterpret_cast<const void*>(kinv_grad_kernel<false, K>);
+  });
   ELFIHIP_CHECK_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   prof_mark(gp, 0);
   if (ard) {
     const int nq = 4 + gp->d;
     int qw = 1;
     while (qw < nq && qw < 256) qw <<= 1;
-    hipLaunchKernelGGL(kinv_grad_kernel<true>, dim3((unsigned)nitems), dim3(256), lds, st, H);
+    dispatch_kernel(gp->kernel, [&](auto kind) {
+      hipLaunchKernelGGL((kinv_grad_kernel<true, decltype(kind)::value>), dim3((unsigned)nitems), dim3(256), lds, st, H);
+    });
     hipLaunchKernelGGL(hyper_reduce_ard_kernel, dim3(1), dim3(256), 0, st, H.part, nitems, stride, nq, qw, gp->h_fit + 2,
                        gp->h_ard, ++gp->hyper_ticket);
   } else {
-    hipLaunchKernelGGL(kinv_grad_kernel<false>, dim3((unsigned)nitems), dim3(256), lds, st, H);
+    dispatch_kernel(gp->kernel, [&](auto kind) {
+      hipLaunchKernelGGL((kinv_grad_kernel<false, decltype(kind)::value>), dim3((unsigned)nitems), dim3(256), lds, st, H);
+    });
     hipLaunchKernelGGL(hyper_reduce_kernel, dim3(1), dim3(256), 0, st, H.part, nitems, gp->h_fit + 2, ++gp->hyper_ticket);   // pinned: no copy
   }
   prof_mark(gp, 1);

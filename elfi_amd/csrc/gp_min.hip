@@ -19,10 +19,11 @@ constexpr int DE_DEFAULT_CHUNK = 8;   // generations enqueued between two reads 
 constexpr double DE_CR = 0.7;         // SciPy's recombination constant
 
 // ---- the mean at the point held in LDS ---------------------------------------------------------------------------------
-// Terms as kstar_kernel (gp_predict.hip) forms them: r2 = (|x|^2 + |X_i|^2) - 2 x.X_i clipped at 0, k = s_f exp(r2 (-1/2l^2)),
+// Terms as kstar_kernel (gp_predict.hip) forms them: r2 = (|x|^2 + |X_i|^2) - 2 x.X_i clipped at 0, k = CovFn<KIND>::k(r2) (rbf: s_f exp(r2 (-1/2l^2))),
 // term_i = (k + s_b) alpha_i.  Summation order (fixed; it depends on n alone): thread t of the 256 adds the terms
 // i = t, t + 256, t + 512, ... in ascending order; the 64 lanes of a wave are then added by the xor
 // butterfly 32, 16, 8, 4, 2, 1; the four waves as ((w0 + w1) + w2) + w3.  Every thread returns the sum.
+template <int KIND>
 __device__ __forceinline__ double mean_at(const double* __restrict__ X, const double* __restrict__ x2,
                                           const double* __restrict__ alpha, int64_t n, int dp, double var,
                                           double neg_half_inv_ls2, double bias, const double* sx, double sx2, double* red) {
@@ -32,7 +33,7 @@ __device__ __forceinline__ double mean_at(const double* __restrict__ X, const do
     for (int c = 0; c < dp; ++c) dot += sx[c] * X[i * dp + c];
     double r2 = (sx2 + x2[i]) + (-2.0 * dot);
     r2 = r2 < 0.0 ? 0.0 : r2;
-    const double k = var * exp(r2 * neg_half_inv_ls2);
+    const double k = CovFn<KIND>(var, neg_half_inv_ls2).k(r2);
     const double contrib = (k + bias) * alpha[i];
     {
 #pragma clang fp contract(off)
@@ -48,6 +49,7 @@ __device__ __forceinline__ double mean_at(const double* __restrict__ X, const do
 }
 
 // mu[s] for the points xs (S, dp) zero padded, with their squared norms: one workgroup per point
+template <int KIND>
 __global__ __launch_bounds__(256) void mean_kernel(const double* X, const double* x2, const double* alpha, const double* xs,
                                                    const double* xs2, int64_t n, int dp, double var,
                                                    double neg_half_inv_ls2, double bias, double* mu) {
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(256) void mean_kernel(const double* X, const double
   const int64_t s = blockIdx.x;
   if ((int)threadIdx.x < dp) sx[threadIdx.x] = xs[s * dp + threadIdx.x];
   __syncthreads();
-  const double m = mean_at(X, x2, alpha, n, dp, var, neg_half_inv_ls2, bias, sx, xs2[s], red);
+  const double m = mean_at<KIND>(X, x2, alpha, n, dp, var, neg_half_inv_ls2, bias, sx, xs2[s], red);
   if (threadIdx.x == 0) mu[s] = m;
 }
 
@@ -115,6 +117,7 @@ __global__ __launch_bounds__(256) void de_start_kernel(DeArgs A, double* pop) {
 // Generation g (g = 0: the energies of the start population).  Workgroup i reads the whole previous generation (pin, Ein)
 // and writes member i of the next (pout, Eout): no workgroup reads what another writes in the same launch.  Every workgroup
 // forms the stop test and the best member from Ein by itself, in the same fixed order, so all take the same decision.
+template <int KIND>
 __global__ __launch_bounds__(256) void de_generation_kernel(DeArgs A, int g, const double* pin, const double* Ein,
                                                             double* pout, double* Eout) {
   __shared__ double sx[256];
@@ -233,7 +236,7 @@ __global__ __launch_bounds__(256) void de_generation_kernel(DeArgs A, int g, con
 #pragma clang fp contract(off)
     for (int c = 0; c < d; ++c) q = q + sx[c] * sx[c];
   }
-  const double e = mean_at(A.X, A.x2, A.alpha, A.n, A.dp, A.var, A.neg_half_inv_ls2, A.bias, sx, q, red);
+  const double e = mean_at<KIND>(A.X, A.x2, A.alpha, A.n, A.dp, A.var, A.neg_half_inv_ls2, A.bias, sx, q, red);
   // an energy that is not finite is kept with its trial: the next launch (there always is one) finds it in Ein, in every
   // workgroup alike, and ends the search with the error -- no flag is written here, where other workgroups might read it
   const bool take = g == 0 || e <= Ein[i] || !isfinite(e);
@@ -261,8 +264,10 @@ static int predict_mean_impl(elfihip_gp* gp, const double* Xs, int64_t S, double
   double* dmu = dx + (size_t)S * (dp + 1);
   hipStream_t st = ctx->stream;
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dx, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(mean_kernel, dim3((unsigned)S), dim3(256), 0, st, gp->X, gp->x2, gp->alpha, dx, dx + (size_t)S * dp,
-                     gp->n, dp, gp->var, -0.5 / (gp->ls * gp->ls), gp->bias, dmu);
+  dispatch_kernel(gp->kernel, [&](auto kind) {
+    hipLaunchKernelGGL(mean_kernel<decltype(kind)::value>, dim3((unsigned)S), dim3(256), 0, st, gp->X, gp->x2, gp->alpha, dx,
+                       dx + (size_t)S * dp, gp->n, dp, gp->var, -0.5 / (gp->ls * gp->ls), gp->bias, dmu);
+  });
   ELFIHIP_TRY(launch_status(ctx, "mean_kernel"));
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(mu, dmu, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, st));
   ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(st));
@@ -299,7 +304,10 @@ static int minimize_mean_impl(elfihip_gp* gp, const double* lower, const double*
   hipLaunchKernelGGL(de_start_kernel, dim3((unsigned)d), dim3(256), 0, st, A, pop[1]);
   ELFIHIP_TRY(launch_status(ctx, "de_start_kernel"));
   // generation g reads buffer (g + 1) & 1 and writes buffer g & 1
-  hipLaunchKernelGGL(de_generation_kernel, dim3((unsigned)NP), dim3(256), 0, st, A, 0, pop[1], E[1], pop[0], E[0]);
+  dispatch_kernel(gp->kernel, [&](auto kind) {
+    hipLaunchKernelGGL(de_generation_kernel<decltype(kind)::value>, dim3((unsigned)NP), dim3(256), 0, st, A, 0, pop[1], E[1], pop[0],
+                       E[0]);
+  });
   ELFIHIP_TRY(launch_status(ctx, "de_generation_kernel"));
   const int chunk = gp->min_chunk > 0 ? gp->min_chunk : DE_DEFAULT_CHUNK;
   int g = 0, converged = 0, gens = 0, nonfinite = 0;
@@ -307,8 +315,10 @@ static int minimize_mean_impl(elfihip_gp* gp, const double* lower, const double*
     // one more launch than generations: the stop test on generation maxiter's energies is the next launch's
     const int g_end = std::min(g + chunk, maxiter + 1);
     for (; g < g_end; ++g) {
-      hipLaunchKernelGGL(de_generation_kernel, dim3((unsigned)NP), dim3(256), 0, st, A, g + 1, pop[g & 1], E[g & 1],
-                         pop[(g + 1) & 1], E[(g + 1) & 1]);
+      dispatch_kernel(gp->kernel, [&](auto kind) {
+        hipLaunchKernelGGL(de_generation_kernel<decltype(kind)::value>, dim3((unsigned)NP), dim3(256), 0, st, A, g + 1, pop[g & 1],
+                           E[g & 1], pop[(g + 1) & 1], E[(g + 1) & 1]);
+      });
       ELFIHIP_TRY(launch_status(ctx, "de_generation_kernel"));
     }
     MailSrc M;

@@ -6,13 +6,14 @@
 // evaluates ONE point per call (three O(n^2) products with the dense K^-1 each, see
 // SURVEY.md 3.3); here S points are evaluated together in groups of 16 columns:
 //
-//   kr[s][i] = s_f exp(-|x_s - X_i|^2 / 2 l^2)                       (S x n, VALU + exp)
+//   kr[s][i] = k(|x_s - X_i|^2), e.g. s_f exp(-|x_s - X_i|^2 / 2 l^2)  (S x n, VALU + exp; CovFn of gp.hpp: rbf, matern32, matern52)
 //   mu_s     = sum_i (kr + s_b) alpha_i
 //   v        = L^-1 (kr + s_b)^T        v[i][s] = sum_{k<=i} WT[k][i] kb[s][k]   (n x 16, MFMA f64)
 //   var_s    = s_f + s_b - sum_i v[i][s]^2
 //   u        = L^-T v = K^-1 kb^T       u[i][s] = sum_{k>=i} WT[i][k] v[k][s]    (n x 16, MFMA f64)
 //   dmu_s    = sum_i alpha_i dk_si,   dvar_s = -2 sum_i u[i][s] dk_si,
-//              dk_si = -(kr[s][i] / l^2) (x_s - X_i)                  (RBF part only, as GPy)
+//              dk_si = -(w[s][i] / l^2) (x_s - X_i)                   (stationary part only, as GPy; w = kr for the RBF kernel,
+//                                                                     the weights kw of kstar_kernel for a Matern kind)
 //
 // The two triangular products stream a triangle of n^2/2 doubles once each: HBM/L3-bound for 16
 // columns, so they are split over (32-row block, 256-deep k chunk) pairs -- about a thousand
@@ -56,11 +57,14 @@ struct QueryArgs {
 };
 
 // ---- kr[s][i], partial mu ----------------------------------------------------------
+// KIND: the covariance function (CovFn, gp.hpp).  The Matern kinds also leave the gradient weights w = g / c in kw[s][i], which
+// the gradient sums then read in place of kr; for the RBF kernel w = k, kw is not touched and the sums read kr.
+template <int KIND>
 __global__ __launch_bounds__(256) void kstar_kernel(const double* X, const double* x2, const double* alpha,
                                                     const double* xs, const double* xs2, double* kr, double* kb,
                                                     double* mu_part, int64_t n, int64_t np, int dp, double var,
                                                     double neg_half_inv_ls2, double bias, double* xs_copy,
-                                                    int from_args, QueryArgs q, double* kbt) {
+                                                    int from_args, QueryArgs q, double* kbt, double* kw) {
   __shared__ double red[256];
   __shared__ double sx[256 + 1];  // this workgroup's query point and its squared norm
   const int s = blockIdx.y;
@@ -70,6 +74,7 @@ __global__ __launch_bounds__(256) void kstar_kernel(const double* X, const doubl
   kr += (int64_t)blockIdx.z * PC * np;
   if (kb) kb += (int64_t)blockIdx.z * PC * np;
   if (kbt) kbt += (int64_t)blockIdx.z * PC * np;   // [point][k]: the k-contiguous form the dense products read (gp_dense.hip)
+  if constexpr (KIND != KERNEL_RBF) kw += (int64_t)blockIdx.z * PC * np;
   mu_part += (int64_t)blockIdx.z * PC * gridDim.x;
   if (from_args) {
     // single-pass call: the point comes with the arguments (uniform index: two wide scalar loads); workgroup
@@ -99,15 +104,20 @@ __global__ __launch_bounds__(256) void kstar_kernel(const double* X, const doubl
   double contrib = 0.0;
   if (i < np) {
     double k = 0.0;
+    [[maybe_unused]] double wgt = 0.0;
     if (i < n) {
       double dot = 0.0;
       for (int c = 0; c < dp; ++c) dot += sx[c] * X[i * dp + c];
       double r2 = (sx[256] + x2[i]) + (-2.0 * dot);
       r2 = r2 < 0.0 ? 0.0 : r2;
-      k = var * exp(r2 * neg_half_inv_ls2);
+      if constexpr (KIND == KERNEL_RBF)
+        k = CovFn<KIND>(var, neg_half_inv_ls2).k(r2);
+      else
+        CovFn<KIND>(var, neg_half_inv_ls2).kw(r2, &k, &wgt);
       contrib = (k + bias) * alpha[i];
     }
     kr[(int64_t)s * np + i] = k;
+    if constexpr (KIND != KERNEL_RBF) kw[(int64_t)s * np + i] = wgt;
     const double kbv = i < n ? k + bias : 0.0;  // right-hand side of the first triangular product
     if (kb) kb[i * PC + s] = kbv;               // [k][s] for the streaming kernel
     if (kbt) kbt[(int64_t)s * np + i] = kbv;
@@ -164,14 +174,15 @@ __device__ __forceinline__ void store_wt(double* p, double v) {
 }
 
 __device__ inline double sum_partials(const double* __restrict__ part, int64_t np, int64_t e, int lo, int hi);
-template <int ROWS_PER_THREAD, int QN, bool FULL = false>
+template <int ROWS_PER_THREAD, int QN, bool FULL = false, bool KBIN = false>
 __device__ __forceinline__ void grad_rows(const double* __restrict__ X, const double* __restrict__ alpha,
                                           const double* __restrict__ xs, const double* __restrict__ kr,
                                           const double* __restrict__ part, int nkc, double* __restrict__ g_part, int chunk,
                                           int nchunks, int64_t i0, int64_t n, int64_t np, int dp, double (*red)[PC][32],
-                                          double bias = 0.0, double* __restrict__ sq_part = nullptr);
+                                          double bias = 0.0, double* __restrict__ sq_part = nullptr,
+                                          const double* __restrict__ kbin = nullptr);
 
-template <int MODE, bool FUSE>
+template <int MODE, bool FUSE, bool KBIN = false>
 __device__ __forceinline__ void tri_apply_body(const TriArgs& T, const int rb, const int kc, double* Bs, int* s_last_p) {
   // No LDS staging of the matrix: a lane's 16-byte load IS its MFMA operand.  Lane (kq = l >> 4, ip = l & 15)
   // of wave w loads W[k][i0 + 2 ip .. + 1] for k = k0 + 16 q + 4 w + kq, q = 0 .. len/16: one instruction covers
@@ -309,10 +320,11 @@ __device__ __forceinline__ void tri_apply_body(const TriArgs& T, const int rb, c
     // MODE 3: u of this block's rows is complete -- the gradient sums as above and the block's share of kb . u
     double(*red)[PC][32] = reinterpret_cast<double(*)[PC][32]>(Bs);
     for (int pass = 0; pass < T.npass; ++pass)
-      grad_rows<2, 2, true>(T.X, T.alpha, T.xs + (int64_t)pass * PC * T.dp, T.kr + (int64_t)pass * PC * T.np,
-                            T.part + (int64_t)pass * T.nkc * T.np * PC, T.nkc,
-                            T.g_part + (int64_t)pass * PC * T.nrb * 2 * T.dp, rb, T.nrb, i0, T.n, T.np, T.dp, red, T.bias,
-                            T.sq_part + (int64_t)pass * (T.np / 16) * PC);
+      grad_rows<2, 2, true, KBIN>(T.X, T.alpha, T.xs + (int64_t)pass * PC * T.dp, T.kr + (int64_t)pass * PC * T.np,
+                                  T.part + (int64_t)pass * T.nkc * T.np * PC, T.nkc,
+                                  T.g_part + (int64_t)pass * PC * T.nrb * 2 * T.dp, rb, T.nrb, i0, T.n, T.np, T.dp, red, T.bias,
+                                  T.sq_part + (int64_t)pass * (T.np / 16) * PC,
+                                  KBIN ? T.bin + (int64_t)pass * T.np * PC : nullptr);
   }
 }
 
@@ -362,16 +374,17 @@ static int tri_tiles(int mode, int nrb, int nkc) {
 // lock-step) and, round 6, without spills (the right-hand sides DMA'd straight into LDS, 112 registers): 1024 tiles in flight
 // instead of 768 lengthen every tile's life from 7.1 to 10.8 us -- the products already pull 6.5 TB/s while their tiles are
 // in flight -- and the lock-step went from 61.6 to 67.5 us (profiles/r06_lockstep_timeline.md).
-template <int MODE, bool FUSE>
+// KBIN: the K^-1 product (MODE 3) of a Matern kind, whose variance term reads k + s_b from T.bin (grad_rows)
+template <int MODE, bool FUSE, bool KBIN = false>
 __global__ __launch_bounds__(256, 3) void tri_apply_kernel(TriArgs T) {
   __shared__ __align__(16) double Bs[KC * PC];
   __shared__ int s_last;
   if (FUSE && MODE != 2) {
     int rb, kc;
     if (!tri_tile_of<MODE>((int)blockIdx.x, T.nrb, T.nkc, &rb, &kc)) return;
-    tri_apply_body<MODE, FUSE>(T, rb, kc, Bs, &s_last);
+    tri_apply_body<MODE, FUSE, KBIN>(T, rb, kc, Bs, &s_last);
   } else {
-    tri_apply_body<MODE, FUSE>(T, (int)blockIdx.x, (int)blockIdx.y, Bs, &s_last);
+    tri_apply_body<MODE, FUSE, KBIN>(T, (int)blockIdx.x, (int)blockIdx.y, Bs, &s_last);
   }
 }
 
@@ -434,12 +447,13 @@ constexpr int GR = 64;
 // `nchunks`: the body of grad_kernel (RPT = 4) and of the fused second product's last arriver (RPT = 2, gp_predict.hip above).
 // FULL (the K^-1 product): every chunk contributes to a row, and the rows' kb_i u_i are summed per 16-row block into
 // sq_part[(i0 / 16 + r)][s] -- the slot the first triangular product fills with sum v^2, so finish_kernel is unchanged.
-template <int RPT, int QN, bool FULL>   // QN: groups of four dimensions per round (4: grad_kernel; 2 keeps the fused product at 3 workgroups per CU)
+// `kr` is what weighs (x_s - X_i): the kernel rows for the RBF kernel, the weights kw of kstar_kernel for a Matern kind.
+template <int RPT, int QN, bool FULL, bool KBIN>   // QN: groups of four dimensions per round (4: grad_kernel; 2 keeps the fused product at 3 workgroups per CU)
 __device__ __forceinline__ void grad_rows(const double* __restrict__ X, const double* __restrict__ alpha,
                                           const double* __restrict__ xs, const double* __restrict__ kr,
                                           const double* __restrict__ part, int nkc, double* __restrict__ g_part, int chunk,
                                           int nchunks, int64_t i0, int64_t n, int64_t np, int dp, double (*red)[PC][32],
-                                          double bias, double* __restrict__ sq_part) {
+                                          double bias, double* __restrict__ sq_part, const double* __restrict__ kbin) {
   static_assert(!FULL || (RPT == 2 && QN == 2), "the variance slots of the K^-1 form sit behind two groups of four dimensions");
   const int t = threadIdx.x, s = t & 15, ig = t >> 4, w = t >> 6;
   double c1[RPT], c2[RPT], pv[RPT];
@@ -454,7 +468,11 @@ __device__ __forceinline__ void grad_rows(const double* __restrict__ X, const do
       const double u = sum_partials(part, np, i * PC + s, FULL ? 0 : (int)(i / KC), nkc);
       c1[r] = alpha[i] * k;
       c2[r] = u * k;
-      pv[r] = u * (k + bias);
+      // KBIN (a Matern kind): `kr` holds the gradient weights, and k + s_b comes from the product's right-hand side [i][s]
+      if constexpr (KBIN)
+        pv[r] = u * kbin[i * PC + s];
+      else
+        pv[r] = u * (k + bias);
     }
   }
   if (FULL) {
@@ -529,8 +547,8 @@ __global__ __launch_bounds__(256) void grad_kernel(const double* __restrict__ X,
   kr += (int64_t)blockIdx.y * PC * np;
   part += (int64_t)blockIdx.y * nkc * np * PC;
   g_part += (int64_t)blockIdx.y * PC * gridDim.x * 2 * dp;
-  grad_rows<4, 4, false>(X, alpha, xs, kr, part, nkc, g_part, (int)blockIdx.x, (int)gridDim.x, (int64_t)blockIdx.x * GR, n, np, dp,
-                         red, 0.0, nullptr);
+  grad_rows<4, 4, false, false>(X, alpha, xs, kr, part, nkc, g_part, (int)blockIdx.x, (int)gridDim.x, (int64_t)blockIdx.x * GR, n, np, dp,
+                         red, 0.0, nullptr, nullptr);
 }
 
 // ---- final assembly: mu, var, dmu, dvar, LCB value and gradient ---------------------------
@@ -743,8 +761,9 @@ __global__ __launch_bounds__(256) void mirror_kernel(const double* WT, double* W
 }
 
 // Prior covariance between two point sets, k(a, b) = s_f exp(-|a - b|^2 / 2 l^2) + s_b -- what GPy's kern.K(X, X2)
-// returns for ELFI's rbf + bias kernel ([GPy-upstream] Stationary._unscaled_dist: (|a|^2 + |b|^2) - 2 a.b clipped at 0,
+// returns for ELFI's rbf + bias kernel, or a Matern kind in the RBF's place (CovFn) ([GPy-upstream] Stationary._unscaled_dist: (|a|^2 + |b|^2) - 2 a.b clipped at 0,
 // exactly 0 on the diagonal when X2 is None).  One thread per entry.
+template <int KIND>
 __global__ __launch_bounds__(256) void kernel_matrix_kernel(const double* A, const double* B, int64_t na, int64_t nb, int d,
                                                             double var, double neg_half_inv_ls2, double bias, int same,
                                                             double* out) {
@@ -761,7 +780,7 @@ __global__ __launch_bounds__(256) void kernel_matrix_kernel(const double* A, con
   double r2 = (a2 + b2) + (-2.0 * dot);
   r2 = r2 < 0.0 ? 0.0 : r2;
   if (same && i == j) r2 = 0.0;
-  out[e] = var * exp(r2 * neg_half_inv_ls2) + bias;
+  out[e] = CovFn<KIND>(var, neg_half_inv_ls2).k(r2) + bias;
 }
 
 // L^-1 (row-wise) for the second triangular product: mirrored from L^-T once per factorisation, on first use
@@ -778,12 +797,20 @@ static int ensure_wl(elfihip_gp* gp) {
 int ensure_wl_public(elfihip_gp* gp) { return ensure_wl(gp); }
 
 // kstar / finish for `npass` 16-point passes in one launch each, for the dense path (gp_dense.hip)
+// kstar_kernel of the GP's covariance function (the arguments after the stream are the kernel's)
+template <typename... Args>
+static void launch_kstar(const elfihip_gp* gp, dim3 grid, const Args&... args) {
+  dispatch_kernel(gp->kernel, [&](auto kind) {
+    hipLaunchKernelGGL(kstar_kernel<decltype(kind)::value>, grid, dim3(256), 0, gp->ctx->stream, args...);
+  });
+}
+
 void launch_kstar_passes(elfihip_gp* gp, const double* xs, const double* xs2, double* kr, double* kbt, double* mu_part,
-                         int nblk_k, unsigned npass) {
+                         int nblk_k, unsigned npass, double* kw) {
   const double inv_ls2 = 1.0 / (gp->ls * gp->ls);
-  hipLaunchKernelGGL(kstar_kernel, dim3(nblk_k, PC, npass), dim3(256), 0, gp->ctx->stream, gp->X, gp->x2, gp->alpha, xs, xs2,
-                     kr, (double*)nullptr, mu_part, gp->n, gp->np, gp->dp, gp->var, -0.5 * inv_ls2, gp->bias,
-                     (double*)nullptr, 0, QueryArgs(), kbt);
+  launch_kstar(gp, dim3(nblk_k, PC, npass), gp->X, gp->x2, gp->alpha, xs, xs2,
+               kr, (double*)nullptr, mu_part, gp->n, gp->np, gp->dp, gp->var, -0.5 * inv_ls2, gp->bias,
+               (double*)nullptr, 0, QueryArgs(), kbt, kw);
 }
 
 void launch_finish_passes(elfihip_gp* gp, const double* mu_part, int nblk_k, const double* var_part, int nblk_v,
@@ -817,7 +844,7 @@ static TriArgs tri_args(const elfihip_gp* gp, const PredictWs& W, bool lower, co
   T.X = gp->X;
   T.alpha = gp->alpha;
   T.xs = xs;
-  T.kr = W.kr;
+  T.kr = W.kw;   // what weighs the gradient sums (== W.kr for the RBF kernel)
   T.g_part = W.g_part;
   T.n = gp->n;
   T.dp = gp->dp;
@@ -828,7 +855,9 @@ static void launch_tri(const elfihip_gp* gp, const PredictWs& W, bool lower, con
                        const double* xs = nullptr, bool full = false) {
   const TriArgs T = tri_args(gp, W, lower, bin, g, xs, full);
   const dim3 grid((unsigned)T.nrb, (unsigned)W.nkc);
-  if (full)
+  if (full && gp->kernel != KERNEL_RBF)
+    hipLaunchKernelGGL((tri_apply_kernel<3, true, true>), dim3((unsigned)tri_tiles(3, T.nrb, T.nkc)), dim3(256), 0, gp->ctx->stream, T);
+  else if (full)
     hipLaunchKernelGGL((tri_apply_kernel<3, true>), dim3((unsigned)tri_tiles(3, T.nrb, T.nkc)), dim3(256), 0, gp->ctx->stream, T);
   else if (fused && lower)
     hipLaunchKernelGGL((tri_apply_kernel<1, true>), dim3((unsigned)tri_tiles(1, T.nrb, T.nkc)), dim3(256), 0, gp->ctx->stream, T);
@@ -958,7 +987,8 @@ static int ensure_ws(elfihip_gp* gp, PredictWs* W, int64_t npass) {
     return o;
   };
   // passes run `group` at a time in one set of launches; the scratch below is per pass of a group
-  const size_t per_pass = (size_t)(W->nkc + 4) * np * PC * sizeof(double);
+  const bool weights = gp->kernel != KERNEL_RBF;   // a Matern kind keeps its gradient weights beside the kernel rows
+  const size_t per_pass = (size_t)(W->nkc + (weights ? 5 : 4)) * np * PC * sizeof(double);
   int64_t group = (int64_t)(((size_t)768 << 20) / per_pass);
   group = group < 1 ? 1 : (group > MAX_GROUP ? MAX_GROUP : group);
   if (group > npass) group = npass;
@@ -967,13 +997,15 @@ static int ensure_ws(elfihip_gp* gp, PredictWs* W, int64_t npass) {
   const size_t o_xs = take((size_t)npass * PC * gp->dp), o_xs2 = take((size_t)npass * PC),
                o_kr = take(g * PC * np), o_kb = take(g * PC * np), o_part = take(g * W->nkc * np * PC), o_v = take(g * np * PC),
                o_u = take(g * np * PC), o_mu = take(g * PC * W->nblk_k), o_var = take(g * (np * PC / 256) * PC + 16),
-               o_g = take(g * PC * W->ngc * 2 * gp->dp), o_out = take((size_t)npass * (3 * PC + 3 * PC * gp->dp));
+               o_g = take(g * PC * W->ngc * 2 * gp->dp), o_out = take((size_t)npass * (3 * PC + 3 * PC * gp->dp)),
+               o_kw = weights ? take(g * PC * np) : o_kr;
   ELFIHIP_CHECK_HIP(ctx, gp->ws.reserve(off * sizeof(double)));
   double* base = gp->ws.as<double>();
   W->xs = base + o_xs;
   W->xs2 = base + o_xs2;
   W->kr = base + o_kr;
   W->kb = base + o_kb;
+  W->kw = base + o_kw;
   W->part = base + o_part;
   W->v = base + o_v;
   W->u = base + o_u;
@@ -1074,10 +1106,10 @@ int predict_enqueue(elfihip_gp* gp, const PredictPlan& P, int64_t S_active, int 
     }
     const bool prof = gp->profile && P.npass <= W.group;   // phase timing of single-group calls
     if (prof) prof_mark(gp, 0);
-    hipLaunchKernelGGL(kstar_kernel, dim3(W.nblk_k, PC, g), dim3(256), 0, st, gp->X, gp->x2, gp->alpha,
-                       from_host ? P.hx : xs, from_host ? P.hx + (size_t)P.npass * PC * dp : xs2, W.kr, W.kb,
-                       W.mu_part, gp->n, np, dp, gp->var, -0.5 * inv_ls2, gp->bias,
-                       P.direct ? W.xs : (double*)nullptr, P.by_args ? 1 : 0, qa, (double*)nullptr);
+    launch_kstar(gp, dim3(W.nblk_k, PC, g), gp->X, gp->x2, gp->alpha,
+                 from_host ? P.hx : xs, from_host ? P.hx + (size_t)P.npass * PC * dp : xs2, W.kr, W.kb,
+                 W.mu_part, gp->n, np, dp, gp->var, -0.5 * inv_ls2, gp->bias,
+                 P.direct ? W.xs : (double*)nullptr, P.by_args ? 1 : 0, qa, (double*)nullptr, W.kw);
     if (prof) prof_mark(gp, 1);
     if (fused && with_kinv && mode == 1) {
       launch_tri(gp, W, true, W.kb, g, true, xs, true);   // u = K^-1 kb, the block sums of kb . u and the gradient sums
@@ -1100,7 +1132,7 @@ int predict_enqueue(elfihip_gp* gp, const PredictPlan& P, int64_t S_active, int 
       if (mode == 1) {
         launch_tri(gp, W, true, W.v, g);
         if (prof) prof_mark(gp, 3);
-        hipLaunchKernelGGL(grad_kernel, dim3(W.ngc, g), dim3(256), 0, st, gp->X, gp->alpha, xs, W.kr, W.part, W.nkc,
+        hipLaunchKernelGGL(grad_kernel, dim3(W.ngc, g), dim3(256), 0, st, gp->X, gp->alpha, xs, W.kw, W.part, W.nkc,
                            W.g_part, gp->n, np, dp);
       }
     }
@@ -1317,9 +1349,9 @@ static int extend_one(elfihip_gp* gp, const double* x, double ynew) {
     ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(W.xs, P.hx, P.n_in * sizeof(double), hipMemcpyHostToDevice, st));
   }
   ELFIHIP_TRY(ensure_wl(gp));
-  hipLaunchKernelGGL(kstar_kernel, dim3(W.nblk_k, PC), dim3(256), 0, st, gp->X, gp->x2, gp->alpha, W.xs, W.xs2, W.kr,
-                     W.kb, W.mu_part, n, np, dp, gp->var, -0.5 * inv_ls2, gp->bias, by_args ? W.xs : (double*)nullptr,
-                     by_args ? 1 : 0, qa, (double*)nullptr);
+  launch_kstar(gp, dim3(W.nblk_k, PC), gp->X, gp->x2, gp->alpha, W.xs, W.xs2, W.kr,
+               W.kb, W.mu_part, n, np, dp, gp->var, -0.5 * inv_ls2, gp->bias, by_args ? W.xs : (double*)nullptr,
+               by_args ? 1 : 0, qa, (double*)nullptr, W.kw);
   const int rblocks = (int)(np * PC / 256);
   launch_tri(gp, W, false, W.kb, 1);
   hipLaunchKernelGGL(tri_reduce_kernel, dim3(rblocks), dim3(256), 0, st, W.part, W.v, W.var_part, np, W.nkc, 0, 1);
@@ -1371,6 +1403,7 @@ __global__ __launch_bounds__(256) void scatter_v_kernel(const double* v, double*
   if (e < np * PC) VP[(e / PC) * ldvp + col0 + (int64_t)blockIdx.y * PC + (e % PC)] = v[e];
 }
 
+template <int KIND>
 __global__ __launch_bounds__(256) void cross_finish_kernel(const double* Pint, const double* xs, const double* dot,
                                                            double* cov, int64_t M, int64_t m_pad, int dp, int64_t S,
                                                            int64_t s0, double var, double neg_half_inv_ls2,
@@ -1388,7 +1421,7 @@ __global__ __launch_bounds__(256) void cross_finish_kernel(const double* Pint, c
     const double t = Pint[i * dp + c] - xs[sq * dp + c];
     r2 += t * t;
   }
-  cov[i * S + col] = (var * exp(r2 * neg_half_inv_ls2) + bias) - dot[i * PC + sq];
+  cov[i * S + col] = (CovFn<KIND>(var, neg_half_inv_ls2).k(r2) + bias) - dot[i * PC + sq];
 }
 
 // first triangular product for `g` passes whose points are already in W.xs / W.xs2: W.v, W.var_part, W.mu_part
@@ -1397,9 +1430,9 @@ static void enqueue_v(elfihip_gp* gp, const PredictWs& W, int64_t pass0, unsigne
   const int dp = gp->dp;
   const int64_t np = gp->np;
   const double inv_ls2 = 1.0 / (gp->ls * gp->ls);
-  hipLaunchKernelGGL(kstar_kernel, dim3(W.nblk_k, PC, g), dim3(256), 0, st, gp->X, gp->x2, gp->alpha,
-                     W.xs + (size_t)pass0 * PC * dp, W.xs2 + (size_t)pass0 * PC, W.kr, W.kb, W.mu_part, gp->n, np, dp,
-                     gp->var, -0.5 * inv_ls2, gp->bias, (double*)nullptr, 0, QueryArgs(), (double*)nullptr);
+  launch_kstar(gp, dim3(W.nblk_k, PC, g), gp->X, gp->x2, gp->alpha,
+               W.xs + (size_t)pass0 * PC * dp, W.xs2 + (size_t)pass0 * PC, W.kr, W.kb, W.mu_part, gp->n, np, dp,
+               gp->var, -0.5 * inv_ls2, gp->bias, (double*)nullptr, 0, QueryArgs(), (double*)nullptr, W.kw);
   launch_tri(gp, W, false, W.kb, g);
   hipLaunchKernelGGL(tri_reduce_kernel, dim3((unsigned)(np * PC / 256), g), dim3(256), 0, st, W.part, W.v, W.var_part,
                      np, W.nkc, 0, 1);
@@ -1490,9 +1523,11 @@ static int cross_cov_impl(elfihip_gp* gp, const double* Q, int64_t S, double* co
     hipLaunchKernelGGL((tri_apply_kernel<2, false>), dim3((unsigned)T.nrb, (unsigned)W.nkc), dim3(256), 0, st, T);
     hipLaunchKernelGGL(tri_reduce_kernel, dim3((unsigned)(m_pad * PC / 256), g), dim3(256), 0, st, part2, dot,
                        (double*)nullptr, m_pad, W.nkc, 2, 0);
-    hipLaunchKernelGGL(cross_finish_kernel, dim3((unsigned)((M * PC + 255) / 256), g), dim3(256), 0, st, gp->Pint,
-                       W.xs + (size_t)pass0 * PC * dp, dot, cov_dev, M, m_pad, dp, S, pass0 * PC, gp->var,
-                       -0.5 * inv_ls2, gp->bias);
+    dispatch_kernel(gp->kernel, [&](auto kind) {
+      hipLaunchKernelGGL(cross_finish_kernel<decltype(kind)::value>, dim3((unsigned)((M * PC + 255) / 256), g), dim3(256), 0, st,
+                         gp->Pint, W.xs + (size_t)pass0 * PC * dp, dot, cov_dev, M, m_pad, dp, S, pass0 * PC, gp->var,
+                         -0.5 * inv_ls2, gp->bias);
+    });
   }
   ELFIHIP_TRY(launch_status(ctx, "cross covariance"));
   std::vector<double> stage;
@@ -1668,8 +1703,10 @@ int elfihip_gp_kernel_matrix(elfihip_gp* gp, const double* A, int64_t na, const 
   hipStream_t st = ctx->stream;
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dA, A, (size_t)na * d * sizeof(double), hipMemcpyHostToDevice, st));
   if (!same) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dB, B, (size_t)nb * d * sizeof(double), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(kernel_matrix_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, dA, dB, na, nb, d, gp->var,
-                     -0.5 / (gp->ls * gp->ls), gp->bias, same ? 1 : 0, ctx->out.as<double>());
+  dispatch_kernel(gp->kernel, [&](auto kind) {
+    hipLaunchKernelGGL(kernel_matrix_kernel<decltype(kind)::value>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, dA, dB,
+                       na, nb, d, gp->var, -0.5 / (gp->ls * gp->ls), gp->bias, same ? 1 : 0, ctx->out.as<double>());
+  });
   ELFIHIP_TRY(launch_status(ctx, "kernel_matrix_kernel"));
   ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(out, ctx->out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, st));
   ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(st));

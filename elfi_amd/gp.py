@@ -28,6 +28,23 @@ from . import _lib
 logger = logging.getLogger(__name__)
 
 DE_MAX_POPULATION = 3840   # include/elfihip.h: elfihip_gp_minimize_mean
+# The stationary part of the covariance function by name: the codes of elfihip_gp_set_kernel (include/elfihip.h)
+KERNEL_KINDS = {'rbf': 0, 'matern32': 1, 'matern52': 2}
+
+
+def kernel_kind(kernel):
+    """The `kernel=` argument of HipGPRegression as one of the names in KERNEL_KINDS: None is 'rbf'; a string is matched
+    without regard to case (ValueError if unknown); any other object -- a GPy kernel -- is NotImplementedError."""
+    if kernel is None:
+        return 'rbf'
+    if not isinstance(kernel, str):
+        raise NotImplementedError('HipGPRegression takes kernel= as one of the names {} (each with a bias term and a zero '
+                                  'mean function, gpy_regression.py:260-280); custom GPy kernel objects need the '
+                                  'reference GPyRegression'.format(sorted(KERNEL_KINDS)))
+    name = kernel.lower()
+    if name not in KERNEL_KINDS:
+        raise ValueError('unknown kernel {!r}: expected one of {}'.format(kernel, sorted(KERNEL_KINDS)))
+    return name
 
 
 def check_minimize_arguments(d, bounds, popsize=15, maxiter=1000, tol=0.01):
@@ -55,7 +72,7 @@ def check_minimize_arguments(d, bounds, popsize=15, maxiter=1000, tol=0.01):
 class GPHandle:
     """Owner of one elfihip_gp (device-resident evidence, factor and alpha)."""
 
-    def __init__(self, d, capacity, ctx=None):
+    def __init__(self, d, capacity, ctx=None, kernel=None):
         self.ctx = ctx or _lib.default_context()
         self.lib = self.ctx.lib
         self.d = int(d)
@@ -67,6 +84,8 @@ class GPHandle:
         self.capacity = cap.value
         self.n = 0
         self._n_int = 0   # integration points held by the device object (set_integration_points)
+        if kernel_kind(kernel) != 'rbf':
+            self.set_kernel(kernel)
 
     def _check(self, rc):
         if rc != _lib.OK:
@@ -85,6 +104,17 @@ class GPHandle:
 
     def set_hyper(self, var, ls, bias, noise):
         self._check(self.lib.elfihip_gp_set_hyper(self.h, float(var), float(ls), float(bias), float(noise)))
+
+    def set_kernel(self, kernel):
+        """The covariance function by name (KERNEL_KINDS) or code; like set_hyper it invalidates the factorisation."""
+        kind = KERNEL_KINDS[kernel_kind(kernel)] if kernel is None or isinstance(kernel, str) else int(kernel)
+        self._check(self.lib.elfihip_gp_set_kernel(self.h, kind))
+
+    def get_kernel(self):
+        """The name of the covariance function in use."""
+        kind = C.c_int(-1)
+        self._check(self.lib.elfihip_gp_get_kernel(self.h, C.byref(kind)))
+        return {v: k for k, v in KERNEL_KINDS.items()}[kind.value]
 
     def set_data(self, X, y):
         X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, self.d)
@@ -310,7 +340,7 @@ class GPHandle:
 class DiagonalScaling:
     """One lengthscale per input dimension (ARD) over a handle that knows a single one -- the transform, written once.
 
-    An RBF kernel with lengthscales l_c is the RBF kernel with lengthscale 1 on u = x / l.  This mix-in sits in front of
+    A stationary kernel (RBF, Matern) with lengthscales l_c is the same kernel with lengthscale 1 on u = x / l.  This mix-in sits in front of
     a handle with GPHandle's methods (ScaledGPHandle: the device object; tests: a NumPy stand-in), talks to it in u with
     ls = 1 and presents ORIGINAL coordinates to every caller: points, evidence and bounds go in divided by l; locations
     come back multiplied by l; gradients w.r.t. x come back divided by l (d/dx = (1/l) d/du); the gradient of the log
@@ -419,7 +449,7 @@ class DiagonalScaling:
 
 
 class ScaledGPHandle(DiagonalScaling, GPHandle):
-    """GPHandle for an RBF kernel with one lengthscale per input dimension: the device object holds x / l under ls = 1."""
+    """GPHandle for a kernel with one lengthscale per input dimension: the device object holds x / l under ls = 1."""
 
 
 # ---- the small part of the GPy object graph that ELFI code touches ---------------------------
@@ -496,7 +526,9 @@ class _GPShim:
             # acquisition.py:754,770 (the reference's ExpIntVar) evaluates the prior kernel matrix through GPy
             return m._handle.kernel_matrix(X, X2)
 
-        return _Part(K=K, rbf=_Part(variance=_Param(m._hyper['var']), lengthscale=_Param(m._hyper['ls'])),
+        # (`rbf` is the stationary part whatever its kind -- the attribute ELFI code reads; `name` tells which)
+        return _Part(K=K, name=m.kernel,
+                     rbf=_Part(name=m.kernel, variance=_Param(m._hyper['var']), lengthscale=_Param(m._hyper['ls'])),
                      bias=_Part(variance=_Param(m._hyper['bias']),
                                 K=lambda X, X2=None: np.full((len(X), len(X if X2 is None else X2)),
                                                              m._hyper['bias'])))
@@ -525,9 +557,10 @@ class _GPShim:
     def __str__(self):
         h = self._m._hyper
         ls = '%.6g' % h['ls'] if np.ndim(h['ls']) == 0 else '(%s)' % ', '.join('%.6g' % v for v in h['ls'])
-        return ("HipGPRegression  n=%d  log-marginal=%.6g\n  rbf.variance %.6g\n  rbf.lengthscale %s\n"
+        k = self._m.kernel
+        return ("HipGPRegression  n=%d  log-marginal=%.6g\n  %s.variance %.6g\n  %s.lengthscale %s\n"
                 "  bias.variance %.6g\n  Gaussian_noise.variance %.6g" %
-                (self.num_data, self._m._log_marginal, h['var'], ls, h['bias'], h['noise']))
+                (self.num_data, self._m._log_marginal, k, h['var'], k, ls, h['bias'], h['noise']))
 
 
 _REFERENCE_SUBCLASSES = {}
@@ -567,6 +600,7 @@ class HipGPRegression:
 
     _hip_origin = None
     ard = False     # (an object pickled before the keyword existed is isotropic)
+    kernel = 'rbf'  # (... and has the RBF kernel)
 
     def __reduce__(self):
         # pickle / copy by the importable class: the two-base class is re-derived where the object is rebuilt
@@ -595,16 +629,19 @@ class HipGPRegression:
         else:
             raise ValueError("Keyword `bounds` must be a dictionary "
                              "`{'parameter_name': (lower, upper), ... }`")
-        if gp_params.get('kernel') is not None or gp_params.get('mean_function') is not None:
-            raise NotImplementedError('HipGPRegression implements the default RBF+Bias kernel with a zero '
-                                      'mean function (gpy_regression.py:260-280); custom GPy kernels / mean '
-                                      'functions need the reference GPyRegression')
+        if gp_params.get('mean_function') is not None:
+            raise NotImplementedError('HipGPRegression implements a zero mean function (gpy_regression.py:260-280); '
+                                      'custom mean functions need the reference GPyRegression')
+        # kernel='rbf' (the default), 'matern32' or 'matern52', each + Bias: the stationary part of the covariance function
+        # ([GPy-upstream] RBF / Matern32 / Matern52); the prior heuristics and the hyper-parameter search are the same
+        kernel = kernel_kind(gp_params.pop('kernel', None))
         self.parameter_names = parameter_names
         self.input_dim = input_dim
         self.bounds = bounds
         # ard=True: one lengthscale per parameter ([GPy-upstream] RBF(input_dim, ARD=True)); `_hyper['ls']` is then a tuple
         # of input_dim floats (a tuple, so that dictionaries of hyper-parameters still compare with ==), shown as an array
         self.ard = bool(gp_params.pop('ard', False))
+        self.kernel = kernel
         self.gp_params = gp_params
         self.optimizer = optimizer
         self.max_opt_iters = max_opt_iters
@@ -739,7 +776,8 @@ class HipGPRegression:
             return False
         cap = max(512, int(2 ** np.ceil(np.log2(max(n, 1)))))
         old = self._handle
-        self._handle = (ScaledGPHandle if self.ard else GPHandle)(self.input_dim, cap, ctx=_lib.default_context(self.device))
+        self._handle = (ScaledGPHandle if self.ard else GPHandle)(self.input_dim, cap, ctx=_lib.default_context(self.device),
+                                                                  kernel=self.kernel)
         if self.acq_host_threads or self.acq_trace:
             self._handle.set_acq_options(self.acq_host_threads, self.acq_trace)
         if old is not None:

@@ -1173,6 +1173,17 @@ int elfihip_gp_free(elfihip_gp* gp);
  * (gpy_regression.py:151-155). */
 int elfihip_gp_set_hyper(elfihip_gp* gp, double rbf_variance, double lengthscale, double bias_variance,
                          double noise_variance);
+/* The stationary part of the covariance function (the `kernel=` of GPyRegression, gpy_regression.py:260-280), with
+ * a = |x - x'| / lengthscale and s_f = rbf_variance of elfihip_gp_set_hyper:
+ *   0 rbf       s_f exp(-a^2 / 2)                                         (the default)
+ *   1 matern32  s_f (1 + sqrt(3) a) exp(-sqrt(3) a)                       ([GPy-upstream] Matern32)
+ *   2 matern52  s_f (1 + sqrt(5) a + 5 a^2 / 3) exp(-sqrt(5) a)           ([GPy-upstream] Matern52)
+ * The bias and noise terms are unchanged.  Every entry point below follows the kind: fit, extend, prediction with gradients,
+ * the acquisition surfaces, the hyper-parameter gradients (isotropic and per dimension) and the search for the mean's
+ * minimiser.  Like elfihip_gp_set_hyper the call invalidates the factorisation (and K^-1): set the kind before the data,
+ * or factorise again.  Any other value of `kind` is ELFIHIP_ERR_ARG and changes nothing. */
+int elfihip_gp_set_kernel(elfihip_gp* gp, int kind);
+int elfihip_gp_get_kernel(const elfihip_gp* gp, int* kind);
 /* Replace / extend the evidence (GPyRegression.update, gpy_regression.py:286-315: np.r_[X_old, x]). */
 int elfihip_gp_set_data(elfihip_gp* gp, const double* X, const double* y, int64_t n);
 int elfihip_gp_append(elfihip_gp* gp, const double* X_new, const double* y_new, int64_t k);
