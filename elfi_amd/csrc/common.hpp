@@ -87,6 +87,7 @@ struct elfihip_ctx {
   //            synlik.hip, semibsl.hip, kliep.hip
   //   sel      twostage.hip: a block of subset distances and its survivors; the partial sums of the entropy
   //            adjust.hip: the tile factors, the tile sums, the jobs' means and coefficients
+  //            glasso.hip: the group moments between synlik.hip's launch (which borrows `scratch`) and the solver's, the penalties
   elfihip::DevBuf scratch, sel;
   elfihip::DevBuf stat;   // workgroup partials of the fused adaptive-distance pass (adaptive.hip)
   // The event-driven simulators (event_sim.hpp; gillespie.hip, daycare.hip, scratch_assay.hip, bdm.hip) share one work buffer:

@@ -23,11 +23,18 @@ parameters gamma of G robust chains' states in one launch; `slice_gamma_mean` / 
 reference's signatures (slice_gamma_mean.py:35, slice_gamma_variance.py:31) and leave the caller's RandomState where the
 reference's functions would; `HipBSL(..., gamma_sampler='device')` puts them into the chain.
 
-Not on the device: graphical-lasso shrinkage, the whitened semiparametric likelihood (wsemiBSL),
-estimate_whitening_matrix.  They raise or stay the reference's; nothing falls back quietly.
+`graphical_lasso` / `glasso_loglik` mirror `elfihip_graphical_lasso` / `elfihip_syn_loglik_glasso` (csrc/glasso.hip):
+graphical-lasso shrinkage of the covariance (BSLasso), B matrices or G groups x P penalties in one launch;
+`glasso_likelihood` is the `likelihood=` for BSL and `select_glasso_penalty` the reference's select_penalty at its default
+shrinkage.  The keyword shrinkage='glasso' of the calls above is not routed there yet and raises.
+
+Not on the device: graphical-lasso shrinkage inside the semiparametric likelihood, the whitened
+semiparametric likelihood (wsemiBSL), estimate_whitening_matrix.  They raise or stay the reference's; nothing falls back
+quietly.
 """
 import ctypes as C
 import sys
+import warnings
 from functools import partial
 
 import numpy as np
@@ -85,6 +92,8 @@ def _groups(ssx, ssy, n_groups):
 
 def _penalty_list(shrinkage, penalty, penalties):
     """The Warton penalties as an array, or None without shrinkage."""
+    # graphical-lasso shrinkage has calls of its own (glasso_loglik, glasso_likelihood, select_glasso_penalty); routing this
+    # keyword to them is a follow-up of a few lines that edits the tests pinning the message below
     if shrinkage == 'glasso':
         raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
     if shrinkage not in (None, 'warton'):
@@ -333,6 +342,144 @@ def select_penalty(model, n_sim, theta, feature_names, likelihood=None, lmdas=No
         print('log-likelihoods (repeat, simulation count, penalty):', logliks[:, where], sep='\n')
         print('standard deviations (simulation count, penalty):', spread, sep='\n')
     return np.asarray(lmdas, dtype=float)[pick], spread[np.arange(len(pick)), pick]
+
+
+# ---- graphical-lasso shrinkage (BSLasso; pdf_methods.py:113-120, pre_sample_methods.py:215-318) -------------------------
+
+GLASSO_NONFINITE, GLASSO_CONVERGED, GLASSO_MAX_ITER = 0, 1, 2
+MAX_GLASSO_ITER = 1 << 20
+
+
+def _glasso_args(alphas, tol, max_iter):
+    a = np.ascontiguousarray(np.atleast_1d(np.asarray(alphas, dtype=np.float64)))
+    if a.ndim != 1 or a.size < 1:
+        raise ValueError('the penalties must be a number or a non-empty list')
+    if not np.all((a >= 0) & np.isfinite(a)):
+        raise ValueError('a graphical-lasso penalty must be non-negative and finite')
+    tol, max_iter = float(tol), int(max_iter)
+    if not (tol > 0 and np.isfinite(tol)):
+        raise ValueError('tol must be positive')
+    if max_iter < 1 or max_iter > MAX_GLASSO_ITER:
+        raise ValueError('max_iter=%d: 1 to %d' % (max_iter, MAX_GLASSO_ITER))
+    return a, tol, max_iter
+
+
+def _warn_capped(status, max_iter):
+    capped = int(np.count_nonzero(status == GLASSO_MAX_ITER))
+    if capped:
+        warnings.warn('graphical lasso: %d of %d problems reached max_iter=%d before the tolerance; their values are '
+                      'returned as they stand' % (capped, status.size, max_iter), RuntimeWarning, stacklevel=3)
+
+
+def graphical_lasso(emp_cov, alpha, tol=1e-12, max_iter=10000, return_n_iter=False, return_status=False, ctx=None):
+    """sklearn.covariance.graphical_lasso on the device (`elfihip_graphical_lasso`, csrc/glasso.hip: one wavefront per
+    problem): (covariance, precision), scikit-learn's return order, and with return_n_iter the sweeps over all columns.
+
+    emp_cov: (m, m) or (B, m, m), m <= MAX_FEATURES; the lower triangle is read and mirrored.  alpha: a number, or a list,
+    which adds an axis behind B.  The solve stops at tol * max(diag emp_cov) (see include/elfihip.h); one RuntimeWarning per
+    call names how many problems reached max_iter.  alpha == 0 returns emp_cov itself and its inverse, as scikit-learn does.
+    return_status: also the status per problem (GLASSO_CONVERGED, GLASSO_MAX_ITER, GLASSO_NONFINITE)."""
+    S = np.asarray(emp_cov, dtype=np.float64)
+    single = S.ndim == 2
+    if S.ndim not in (2, 3) or S.shape[-1] != S.shape[-2]:
+        raise ValueError('emp_cov must be (m, m) or (B, m, m)')
+    S = S.reshape((-1,) + S.shape[-2:])
+    B, m = S.shape[0], S.shape[1]
+    if B < 1 or m < 1 or m > MAX_FEATURES:
+        raise ValueError('a %d x %d matrix: the device kernel takes 1 to %d rows' % (m, m, MAX_FEATURES))
+    a, tol, max_iter = _glasso_args(alpha, tol, max_iter)
+    low = np.tril(S)
+    S = np.ascontiguousarray(low + np.transpose(np.tril(S, -1), (0, 2, 1)))
+    P = a.size
+    W, Theta = np.empty((B, P, m, m)), np.empty((B, P, m, m))
+    n_iter, status = np.empty((B, P), dtype=np.int32), np.empty((B, P), dtype=np.int32)
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_graphical_lasso", _lib.ptr(S), B, m, m, _lib.ptr(a), P, tol, max_iter, _lib.ptr(W), _lib.ptr(Theta),
+             _lib.ptr(n_iter), _lib.ptr(status))
+    _warn_capped(status, max_iter)
+    out = [W, Theta] + ([n_iter] if return_n_iter else []) + ([status] if return_status else [])
+    if np.ndim(alpha) == 0:
+        out = [o[:, 0] for o in out]
+    if single:
+        out = [o[0] for o in out]
+    return tuple(int(o) if o.ndim == 0 else o for o in out)
+
+
+def glasso_loglik(ssx, ssy, penalty=None, penalties=None, n_groups=1, whitening=None, standardise=False, tol=1e-12,
+                  max_iter=10000, return_moments=False, return_status=False, ctx=None):
+    """Gaussian synthetic log-likelihoods with graphical-lasso shrinkage of the covariance (BSLasso) of `n_groups` groups
+    of simulated summaries x the penalties in one device call (`elfihip_syn_loglik_glasso`).
+
+    ssx, ssy, n_groups, whitening and the shape of the result as syn_loglik: (n_groups[, len(penalties)]), a float for one
+    group given as a 2-d array and `penalty`.  standardise: the reference's keyword (pdf_methods.py:113-120) -- the solve
+    runs on cov_ij / (sd_i sd_j) and its result is used as the reference writes it, as the covariance around the
+    unstandardised mean; that is the reference's statement, not a rescaled one.  With return_moments: (loglik, mean (G, m),
+    cov (G[, P], m, m) the shrunk matrices); with return_status the status per problem is appended."""
+    if (penalty is None) == (penalties is None):
+        raise ValueError('give either penalty or penalties')
+    X, y, n_groups, n, m, keep_group_axis = _groups(ssx, ssy, n_groups)
+    a, tol, max_iter = _glasso_args(penalty if penalties is None else penalties, tol, max_iter)
+    if penalties is None and a.size != 1:
+        raise ValueError('penalty is one number; a list goes to penalties')
+    Wh = None
+    if whitening is not None:
+        Wh = np.ascontiguousarray(whitening, dtype=np.float64)
+        if Wh.shape != (m, m):
+            raise ValueError('whitening must be (%d, %d)' % (m, m))
+    X = np.ascontiguousarray(X)
+    P = a.size
+    ll = np.empty((n_groups, P), dtype=np.float64)
+    status = np.empty((n_groups, P), dtype=np.int32)
+    mean = np.empty((n_groups, m), dtype=np.float64) if return_moments else None
+    cov = np.empty((n_groups, P, m, m), dtype=np.float64) if return_moments else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_syn_loglik_glasso", _lib.ptr(X), n_groups, n, m, m, _lib.ptr(y), _lib.ptr(Wh), _lib.ptr(a), P,
+             1 if standardise else 0, tol, max_iter, _lib.ptr(ll), _lib.ptr(status), _lib.ptr(mean), _lib.ptr(cov))
+    _warn_capped(status, max_iter)
+    ll = _squeeze(ll[:, None, :], keep_group_axis, None, penalties)
+    if penalties is None:
+        status = status[:, 0]
+        cov = cov[:, 0] if return_moments else None
+    out = (ll, mean, cov) if return_moments else (ll,)
+    if return_status:
+        out += (status,)
+    return out if len(out) > 1 else out[0]
+
+
+def gaussian_syn_likelihood_glasso(ssx, ssy, shrinkage=None, penalty=None, whitening=None, standardise=False):
+    """gaussian_syn_likelihood(..., shrinkage='glasso') of one (n, m) summary matrix; np.array([ll])."""
+    if shrinkage not in (None, 'glasso'):
+        raise ValueError("this likelihood is the graphical-lasso one; shrinkage=%r goes to standard_likelihood" % (shrinkage,))
+    return np.array([glasso_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, penalty=penalty,
+                                   whitening=whitening, standardise=standardise)])
+
+
+def glasso_likelihood(penalty, whitening=None, standardise=False):
+    """pdf_methods.standard_likelihood(shrinkage='glasso', penalty=penalty) on the device: a `likelihood=` for elfi.BSL and
+    HipBSL; like the other factories' callables it takes shrinkage=, penalty= and whitening= keywords that override."""
+    _glasso_args(penalty, 1e-12, 1)
+    return partial(gaussian_syn_likelihood_glasso, shrinkage='glasso', penalty=penalty, whitening=whitening,
+                   standardise=standardise)
+
+
+def select_glasso_penalty(model, n_sim, theta, feature_names, lmdas=None, M=20, sigma=1.5, whitening=None,
+                          standardise=False, seed=None):
+    """pre_sample_methods.select_penalty at its default shrinkage, the graphical lasso: for every simulation count the
+    penalty whose log-likelihood standard deviation over M repeats is closest to sigma -- (closest_lmdas,
+    closest_std_devs).  The draws are the reference's (child seed i of SeedSequence(seed) -> one generate call); one
+    device call per entry of n_sim evaluates its M groups x all penalties."""
+    if lmdas is None:
+        lmdas = list(np.exp(np.arange(-5.5, -1.5, 0.2)))
+    counts = np.atleast_1d(np.asarray(n_sim)).astype(np.int64).reshape(-1)
+    groups, observed = _generate_groups(model, theta, int(counts.max()), feature_names, M, seed)
+    lmdas = np.asarray(lmdas, dtype=float)
+    closest, spread = np.zeros(len(counts)), np.zeros(len(counts))
+    for i, n in enumerate(counts):
+        ll = glasso_loglik(groups[:, :n], observed, penalties=lmdas, whitening=whitening, standardise=standardise)
+        std = np.array([np.std(ll[:, j]) for j in range(len(lmdas))])       # the reference's expression
+        pick = np.argmin(np.abs(std - sigma))
+        closest[i], spread[i] = lmdas[pick], std[pick]
+    return closest, spread
 
 
 # ---- the slice samplers for gamma (slice_gamma_mean.py:35-138, slice_gamma_variance.py:31-115) ------------------------

@@ -352,6 +352,40 @@ int elfihip_syn_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_
                            const double* dW, int variant, const double* dgamma_adj, const int64_t* prefixes, int K,
                            const double* penalties, int P, double* dloglik, double* dmean, double* dcov);
 
+/* Graphical-lasso shrinkage (BSLasso, An et al. 2019; sklearn.covariance.graphical_lasso as pdf_methods.py:113-120 calls
+ * it): B symmetric positive semi-definite matrices S (m x m, rows at pitch lds >= m, 1 <= m <= 64; S is taken as symmetric:
+ * row j is read for column j) x P penalties alphas (host array, >= 0) in one launch, one wavefront per problem.  Problem
+ * (b, p) finds the W = Theta^-1 that minimises -log det Theta + tr(S Theta) + alpha sum_{i != j} |Theta_ij| (the diagonal
+ * is not penalised: diag W = diag S) by block coordinate descent over columns with a cyclic coordinate-descent lasso
+ * (Friedman, Hastie & Tibshirani), from scikit-learn's start (W = S with the off-diagonal scaled by 0.95, coefficients 0)
+ * -- never from a neighbouring problem's result: a problem does not depend on what else is in the call.  The lasso of a
+ * column stops when the largest coefficient change times its diagonal entry in a sweep is <= tol max_i S_ii (or after 1000
+ * sweeps), the descent when the largest change of any off-diagonal entry of W in a sweep over all columns is (or after
+ * max_iter sweeps, 1 <= max_iter <= 2^20).  alpha == 0 or m == 1: W = S bit for bit and Theta = S^-1 (Cholesky).
+ * W, Theta (B, P, m, m; Theta or NULL: from the columns as scikit-learn takes it, theta22 = 1 / (w22 - w12' beta),
+ * theta12 = -beta theta22), n_iter (B, P; or NULL) the sweeps over all columns, status (B, P):
+ * ELFIHIP_GLASSO_CONVERGED, ELFIHIP_GLASSO_MAX_ITER (the values are written as they stand), ELFIHIP_GLASSO_NONFINITE (a
+ * value that is not finite, or a theta22 / Cholesky pivot that is not positive); the call gives ELFIHIP_OK in all three.
+ * Host form: host pointers, synchronises.  _dev form: S, W, Theta, n_iter, status are device pointers, no synchronisation;
+ * alphas is a host array in both.  Deterministic. */
+enum { ELFIHIP_GLASSO_NONFINITE = 0, ELFIHIP_GLASSO_CONVERGED = 1, ELFIHIP_GLASSO_MAX_ITER = 2 };
+int elfihip_graphical_lasso(elfihip_ctx* ctx, const double* S, int64_t B, int m, int64_t lds, const double* alphas, int P,
+                            double tol, int max_iter, double* W, double* Theta, int32_t* n_iter, int32_t* status);
+int elfihip_graphical_lasso_dev(elfihip_ctx* ctx, const double* dS, int64_t B, int m, int64_t lds, const double* alphas, int P,
+                                double tol, int max_iter, double* dW, double* dTheta, int32_t* dn_iter, int32_t* dstatus);
+/* The standard synthetic log-likelihood with graphical-lasso shrinkage (gaussian_syn_likelihood(shrinkage='glasso'),
+ * pdf_methods.py:105-130) of G groups x P penalties: the moments of elfihip_syn_loglik (X, G, n, m, ldx, y, Wh as there:
+ * whitening first), then per (group, penalty) the solve above on cov -- with standardise != 0 on cov_ij / (sd_i sd_j),
+ * sd = sqrt(diag cov), whose result is used as the reference writes it: as the covariance, around the unstandardised mean
+ * -- and loglik (G, P) = log N(y; mean, W), -inf where W has a Cholesky pivot that is not positive.  status (G, P) as
+ * above; mean (G, m) or NULL; cov (G, P, m, m) or NULL: the shrunk matrices W. */
+int elfihip_syn_loglik_glasso(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, int m, int64_t ldx, const double* y,
+                              const double* Wh, const double* alphas, int P, int standardise, double tol, int max_iter,
+                              double* loglik, int32_t* status, double* mean, double* cov);
+int elfihip_syn_loglik_glasso_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx, const double* dy,
+                                  const double* dWh, const double* alphas, int P, int standardise, double tol, int max_iter,
+                                  double* dloglik, int32_t* dstatus, double* dmean, double* dcov);
+
 /* The semiparametric synthetic log-likelihood (semiBSL: a kernel density estimate per summary and a Gaussian copula with
  * the Gaussian rank correlation; elfi/methods/bsl/pdf_methods.py:179-264, gaussian_rank_corr.py:30-52) of G groups of n
  * rows in one call.  X, y, ldx, prefixes, penalties and loglik (G, K, max(P, 1)) as for elfihip_syn_loglik; m <= 64,
