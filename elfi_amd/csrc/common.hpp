@@ -84,7 +84,7 @@ struct elfihip_ctx {
   // (SelWork::err in `scratch`, topk_resident_err_dev), which the selection's caller reads in stream order before any other
   // user of `scratch` is enqueued.
   //   scratch  topk.hip (SelWork / SelState: histograms, the barrier counter, the flag), welford.hip, wstats.hip, gmix.hip,
-  //            synlik.hip, semibsl.hip, kliep.hip
+  //            synlik.hip, semibsl.hip, wsemibsl.hip, kliep.hip
   //   sel      twostage.hip: a block of subset distances and its survivors; the partial sums of the entropy
   //            adjust.hip: the tile factors, the tile sums, the jobs' means and coefficients
   //            glasso.hip: the group moments between synlik.hip's launch (which borrows `scratch`) and the solver's, the penalties

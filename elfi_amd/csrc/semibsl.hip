@@ -27,9 +27,7 @@
 // column without spread (h = 0; a decided divergence: the reference raises LinAlgError from gaussian_kde there); two rows
 // and more than one column (every column of scores is +-(a, b): rho has rank one; the reference returns about -1e16 from
 // the noise of its LU).
-#include "common.hpp"
-#include "special.hpp"
-#include "syn_gram.hpp"
+#include "semi_rank.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -37,50 +35,6 @@
 #pragma clang fp contract(off)
 
 namespace elfihip {
-
-constexpr int SEMI_MAX_N = 16384;   // one column (128 KB) + the reduction buffer in the 160 KB of LDS
-constexpr int SEMI_RED = 256;
-constexpr int SEMI_STATS = 2 * SL_MAX_M + 8;   // per (group, prefix): eta (64), logpdf (64), the denominator
-
-struct SemiArgs {
-  const double* X;          // (G n, m), pitch ldx
-  int64_t n, ldx;
-  int m, K, P, MP;
-  const double* y;          // (m)
-  const int64_t* prefixes;  // (K) ascending, last == n
-  const double* penalties;  // (P) or NULL
-  double* Q;                // scratch (G K, n, MP): normal scores of the first prefixes[k] rows
-  double* stats;            // scratch (G K, SEMI_STATS)
-  double* loglik;           // (G, K, max(P, 1))
-  double* u;                // (G, m) or NULL
-  double* rho;              // (G, m, m) or NULL
-  double* scores;           // (G, n, m) or NULL
-};
-
-// The sum / the maximum over the workgroup of one value per thread, in a fixed tree; every thread gets it.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int s = SEMI_RED / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-__device__ __forceinline__ double block_max(double v, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int s = SEMI_RED / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-    __syncthreads();
-  }
-  return red[0];
-}
 
 __global__ __launch_bounds__(256) void semibsl_column_kernel(SemiArgs A) {
   extern __shared__ __align__(16) double lds[];
@@ -143,15 +97,7 @@ __global__ __launch_bounds__(256) void semibsl_column_kernel(SemiArgs A) {
   double* Qg = A.Q + gk * A.n * A.MP + j;
   const double2* col2 = reinterpret_cast<const double2*>(col);
   for (int i = tid; i < p; i += 256) {
-    const double xi = col[i];
-    int lt = 0, eq = 0;
-    for (int t = 0; t < pp / 2; t += 2) {
-      const double2 a = col2[t], b = col2[t + 1];
-      lt += (a.x < xi) + (a.y < xi) + (b.x < xi) + (b.y < xi);
-      eq += (a.x == xi) + (a.y == xi) + (b.x == xi) + (b.y == xi);
-    }
-    const double r = (double)lt + 0.5 * (double)(eq + 1);
-    const double q = norm_ppf(r / np1);
+    const double q = rank_score(col2, pp, col[i], np1);
     Qg[(int64_t)i * A.MP] = q;
     if (A.scores && full) A.scores[(g * A.n + i) * m + j] = q;
   }
@@ -282,6 +228,13 @@ static int semibsl_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, 
   return ELFIHIP_OK;
 }
 
+int semibsl_launch_column(elfihip_ctx* ctx, const SemiArgs& A, int64_t GK) {
+  const size_t bytes = (size_t)(SEMI_RED + ((A.n + 3) & ~(int64_t)3)) * sizeof(double);
+  ELFIHIP_TRY(set_lds(ctx, semibsl_column_kernel, bytes, 48 * 1024));
+  hipLaunchKernelGGL(semibsl_column_kernel, dim3((unsigned)(GK * A.m)), dim3(256), bytes, ctx->stream, A);
+  return launch_status(ctx, "semiparametric likelihood column kernel");
+}
+
 // Device rows, y and outputs; host prefixes and penalties (checked above).
 static int semibsl_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx, const double* dy,
                             const int64_t* prefixes, int K, const double* penalties, int P, double* dll, double* du,
@@ -315,10 +268,7 @@ static int semibsl_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64
   A.u = du;
   A.rho = drho;
   A.scores = dscores;
-  const size_t bytes = (size_t)(SEMI_RED + ((n + 3) & ~(int64_t)3)) * sizeof(double);
-  ELFIHIP_TRY(set_lds(ctx, semibsl_column_kernel, bytes, 48 * 1024));
-  hipLaunchKernelGGL(semibsl_column_kernel, dim3((unsigned)(GK * m)), dim3(256), bytes, st, A);
-  ELFIHIP_TRY(launch_status(ctx, "semiparametric likelihood column kernel"));
+  ELFIHIP_TRY(semibsl_launch_column(ctx, A, GK));
   return launch_by_tiles(
       ctx, m, (unsigned)GK, "semiparametric likelihood finish kernel",
       [](auto T) { return semibsl_finish_kernel<decltype(T)::value>; },

@@ -28,9 +28,14 @@ graphical-lasso shrinkage of the covariance (BSLasso), B matrices or G groups x 
 `glasso_likelihood` is the `likelihood=` for BSL and `select_glasso_penalty` the reference's select_penalty at its default
 shrinkage.  The keyword shrinkage='glasso' of the calls above is not routed there yet and raises.
 
-Not on the device: graphical-lasso shrinkage inside the semiparametric likelihood, the whitened
-semiparametric likelihood (wsemiBSL), estimate_whitening_matrix.  They raise or stay the reference's; nothing falls back
-quietly.
+`wsemi_loglik` mirrors `elfihip_wsemi_loglik` (csrc/wsemibsl.hip): the whitened semiparametric likelihood (wsemiBSL,
+Priddle et al. 2021; the whitening branch of pdf_methods.py:213-264) with the same (G, K, P) call shape;
+`whitened_semiparametric_likelihood(W)` is the `likelihood=` for BSL, select_penalty and log_SL_stdev.  The keyword
+whitening= of the semiparametric calls above is not routed there and raises.
+
+Not on the device: graphical-lasso shrinkage inside the semiparametric likelihoods, estimate_whitening_matrix
+(the reference's runs once before sampling, on the device models too; its W goes straight into the calls here).  They
+raise or stay the reference's; nothing falls back quietly.
 """
 import ctypes as C
 import sys
@@ -204,6 +209,46 @@ def semi_loglik(ssx, ssy, n_groups=1, shrinkage=None, penalty=None, prefixes=Non
     return (ll, u, rho, scores) if return_parts else ll
 
 
+def wsemi_loglik(ssx, ssy, whitening, n_groups=1, shrinkage=None, penalty=None, prefixes=None, penalties=None,
+                 return_parts=False, ctx=None):
+    """Whitened semiparametric synthetic log-likelihoods (wsemiBSL: the normal scores of the rows are multiplied by
+    whitening^T, every transformed column is ranked and scored again, and the rank correlation of those scores is scaled by
+    d = sqrt(diag(whitening cov(scores) whitening^T))) of `n_groups` groups of simulated summaries in one device call.
+
+    whitening: (m, m), finite.  Everything else, and the shape of the result, as semi_loglik; shrinkage 'warton' acts on
+    the rank correlation before the scaling.  -inf as semi_loglik, and where a d is not positive and finite.  With
+    return_parts: (loglik, u (G, m), rho (G, m, m), scale (G, m), scores (G, n, m)) of the full groups -- the integrals of
+    the density estimates up to ssy, the rank correlation of the transformed scores before shrinkage, d, the re-ranked
+    scores.  whitening = I is not semi_loglik: d is then the standard deviation of the scores, not 1.
+    """
+    X, y, n_groups, n, m, keep_group_axis = _groups(ssx, ssy, n_groups)
+    if n > MAX_SEMI_ROWS:
+        raise ValueError('%d rows per group: the semiparametric kernel takes 2 to %d' % (n, MAX_SEMI_ROWS))
+    if whitening is None:
+        raise ValueError('the whitened semiparametric likelihood needs a whitening matrix')
+    W = np.ascontiguousarray(whitening, dtype=np.float64)
+    if W.shape != (m, m):
+        raise ValueError('whitening must be (%d, %d)' % (m, m))
+    if not np.all(np.isfinite(W)):
+        raise ValueError('whitening has a non-finite entry')
+    pen = _penalty_list(shrinkage, penalty, penalties)
+    pre = _prefix_list(prefixes, n)
+    X = np.ascontiguousarray(X)
+    K = 1 if pre is None else pre.size
+    P = 0 if pen is None else pen.size
+    ll = np.empty((n_groups, K, max(P, 1)), dtype=np.float64)
+    u = np.empty((n_groups, m), dtype=np.float64) if return_parts else None
+    rho = np.empty((n_groups, m, m), dtype=np.float64) if return_parts else None
+    scale = np.empty((n_groups, m), dtype=np.float64) if return_parts else None
+    scores = np.empty((n_groups, n, m), dtype=np.float64) if return_parts else None
+    ctx = ctx or _lib.default_context()
+    ctx.call("elfihip_wsemi_loglik", _lib.ptr(X), n_groups, n, m, m, _lib.ptr(y), _lib.ptr(W), _lib.ptr(pre),
+             0 if pre is None else K, _lib.ptr(pen), P, _lib.ptr(ll), _lib.ptr(u), _lib.ptr(rho), _lib.ptr(scale),
+             _lib.ptr(scores))
+    ll = _squeeze(ll, keep_group_axis, prefixes, penalties)
+    return (ll, u, rho, scale, scores) if return_parts else ll
+
+
 # ---- the reference's likelihood callables (pdf_methods.py:77-135, 138-176, 267-316) ----------------------------------
 
 def gaussian_syn_likelihood(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
@@ -231,6 +276,15 @@ def semi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitening
                                  penalty=penalty)])
 
 
+def wsemi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
+    """Whitened semiparametric synthetic log-likelihood (semi_param_kernel_estimate with whitening=, pdf_methods.py:
+    232-244) of one (n, m) summary matrix; np.array([ll])."""
+    if whitening is None:
+        raise ValueError('the whitened semiparametric likelihood needs whitening=')
+    return np.array([wsemi_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, whitening,
+                                  shrinkage=shrinkage, penalty=penalty)])
+
+
 def standard_likelihood(shrinkage=None, penalty=None, whitening=None):
     """pdf_methods.standard_likelihood on the device (Warton shrinkage or none)."""
     if shrinkage == 'glasso':
@@ -251,6 +305,18 @@ def semiparametric_likelihood(shrinkage=None, penalty=None, whitening=None):
     return partial(semi_param_kernel_estimate, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
 
 
+def whitened_semiparametric_likelihood(whitening, shrinkage=None, penalty=None):
+    """pdf_methods.semiparametric_likelihood(whitening=W) on the device (wsemiBSL; Warton shrinkage or none): a
+    `likelihood=` for elfi.BSL, HipBSL, select_penalty and log_SL_stdev."""
+    if shrinkage == 'glasso':
+        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
+    if shrinkage not in (None, 'warton'):
+        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    if whitening is None:
+        raise ValueError('the whitened semiparametric likelihood needs a whitening matrix')
+    return partial(wsemi_param_kernel_estimate, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
+
+
 def unbiased_likelihood():
     """pdf_methods.unbiased_likelihood on the device."""
     return gaussian_syn_likelihood_ghurye_olkin
@@ -264,7 +330,8 @@ def robust_likelihood(adjustment):
 
 
 def _likelihood_setup(likelihood, **override):
-    """syn_loglik keywords of one of the callables above (None: the standard one); with semi=True: semi_loglik's."""
+    """syn_loglik keywords of one of the callables above (None: the standard one); with semi=True: semi_loglik's; with
+    wsemi=True: wsemi_loglik's."""
     kw = {}
     fn = likelihood
     if isinstance(likelihood, partial):
@@ -277,10 +344,23 @@ def _likelihood_setup(likelihood, **override):
         if kw.get('whitening') is not None:
             raise NotImplementedError('the whitened semiparametric likelihood (wsemiBSL) is not on the device')
         return dict(semi=True, shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'))
+    if fn is wsemi_param_kernel_estimate:
+        kw.update({k: v for k, v in override.items() if not (k == 'whitening' and v is None)})
+        if kw.get('whitening') is None:
+            raise ValueError('the whitened semiparametric likelihood needs whitening=')
+        return dict(wsemi=True, shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw['whitening'])
     if fn is gaussian_syn_likelihood_ghurye_olkin and not override:
         return dict(variant='unbiased')
     raise TypeError('the batched evaluation takes the device likelihoods of elfi_amd (standard_likelihood(...), '
-                    'semiparametric_likelihood(...), unbiased_likelihood()); got %r' % (likelihood,))
+                    'semiparametric_likelihood(...), whitened_semiparametric_likelihood(...), unbiased_likelihood()); '
+                    'got %r' % (likelihood,))
+
+
+def _batched_call(setup):
+    """The batched call a setup of _likelihood_setup goes to (the marker is taken out of the setup)."""
+    if setup.pop('wsemi', False):
+        return lambda groups, observed, **kw: wsemi_loglik(groups, observed, kw.pop('whitening'), **kw)
+    return semi_loglik if setup.pop('semi', False) else syn_loglik
 
 
 def _generate_groups(model, theta, max_sim, feature_names, M, seed):
@@ -315,7 +395,7 @@ def log_SL_stdev(model, theta, n_sim, feature_names, likelihood=None, M=20, seed
     setup = _likelihood_setup(likelihood)
     counts, uniq, where = _prefix_axis(n_sim)
     groups, observed = _generate_groups(model, theta, int(uniq[-1]), feature_names, M, seed)
-    batched = semi_loglik if setup.pop('semi', False) else syn_loglik
+    batched = _batched_call(setup)
     ll = batched(groups, observed, prefixes=uniq, **setup)          # (M, len(uniq))
     return np.std(np.ascontiguousarray(ll[:, where].T), axis=1)     # (len(n_sim), M), the reference's layout
 
@@ -334,7 +414,7 @@ def select_penalty(model, n_sim, theta, feature_names, likelihood=None, lmdas=No
     counts, uniq, where = _prefix_axis(n_sim)
     groups, observed = _generate_groups(model, theta, int(uniq[-1]), feature_names, M, seed)
     setup.pop('penalty', None)
-    batched = semi_loglik if setup.pop('semi', False) else syn_loglik
+    batched = _batched_call(setup)
     logliks = batched(groups, observed, prefixes=uniq, penalties=lmdas, **setup)        # (M, len(uniq), len(lmdas))
     spread = logliks.std(axis=0)[where]                    # over the repeats: (len(n_sim), len(lmdas))
     pick = np.abs(spread - sigma).argmin(axis=1)           # ties go to the smaller penalty index, as argmin does

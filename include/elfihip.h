@@ -410,6 +410,29 @@ int elfihip_semi_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64
                             const int64_t* prefixes, int K, const double* penalties, int P, double* dloglik, double* du,
                             double* drho, double* dscores);
 
+/* The whitened semiparametric synthetic log-likelihood (wsemiBSL, Priddle et al. 2021; the whitening branch of
+ * elfi/methods/bsl/pdf_methods.py:213-264 and gaussian_copula_density.py:33-60) of G groups of n rows in one call.  The
+ * arguments of elfihip_semi_loglik and W, the whitening matrix (m x m, row-major, pitch m).  Per column of the first p
+ * rows logpdf_j, u_j, eta_j and the scores Q as above; then T = Q W^T; every column of T is ranked again (ties at the
+ * average rank) and scored, q'_ij = Phi^-1(rank'_ij / (p + 1)); rho_ab = sum_i q'_ia q'_ib / sum_i Phi^-1(i / (p + 1))^2,
+ * rho_aa = 1; C = cov(Q) (ddof 1, about the column means); d_a = sqrt((W C W^T)_aa); penalty l: rho <- (1 - l) rho + l I
+ * (before the scaling); M = diag(d) rho diag(d), eta_w = W eta,
+ * loglik = -(log|M| + eta_w^T M^-1 eta_w - eta_w^T eta_w) / 2 + sum_j logpdf_j.  (W = I is not elfihip_semi_loglik: d is
+ * the standard deviation of the scores, not 1.)
+ * -inf with the status left at ELFIHIP_OK: a u_j of 0 or 1, a column without spread, a d_a that is not positive and
+ * finite, a non-positive Cholesky pivot, a non-finite value, two rows and m > 1.
+ * u (G, m), rho (G, m, m), scale (G, m), scores (G, n, m) or NULL: of the full groups, the integrals u_j, the rank
+ * correlation of the transformed scores before shrinkage, d, and the scores q' of the transformed columns.
+ * Host form: host pointers, synchronises; a non-finite entry of W is ELFIHIP_ERR_ARG.  _dev form: X, y, W, loglik, u, rho,
+ * scale, scores are device pointers, no synchronisation; prefixes and penalties are host arrays in both forms.
+ * Deterministic; a group's result does not depend on G, and prefix p has the bits of a group of p rows. */
+int elfihip_wsemi_loglik(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, int m, int64_t ldx, const double* y,
+                         const double* W, const int64_t* prefixes, int K, const double* penalties, int P, double* loglik,
+                         double* u, double* rho, double* scale, double* scores);
+int elfihip_wsemi_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx, const double* dy,
+                             const double* dW, const int64_t* prefixes, int K, const double* penalties, int P,
+                             double* dloglik, double* du, double* drho, double* dscale, double* dscores);
+
 /* KLIEP density-ratio estimation (elfi/methods/density_ratio_estimation.py: fit, _KLIEP :183-202, _KLIEP_lcv :157-181) of
  * numerator rows x (Nx, d), pitch ldx, against denominator rows y (Ny, d), pitch ldy, for S basis scales in one call; with
  * F > 0 folds also the S x F leave-fold-out fits of the likelihood cross-validation.
