@@ -386,10 +386,8 @@ static int adjust_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64_
   const int64_t sumT = adj_tile_offsets(prefixes, Ke, n, TR, toff);
   // parameter block: [prefixes Ke][tile offsets Ke]
   const GroupParams B = group_params(prefixes, K, n, toff.data(), nullptr, 0);
-  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve(B.words.size() * sizeof(double)));
-  double* dpar = ctx->par.as<double>();
-  // pageable host memory: the copy is done with it when hipMemcpyAsync returns (common.hpp: pageable uploads)
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, B.words.data(), B.words.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  double* dpar;
+  ELFIHIP_TRY(upload_group_params(ctx, B, 0, &dpar));
   const size_t J = (size_t)G * Ke, tiles = (size_t)G * (size_t)sumT, rec_len = (size_t)W + 2 * m + 1;
   // scratch: [tri tiles W W][rec tiles rec_len][mean J W][beta J q m][jflag J][jstatus J]
   const size_t doubles = tiles * W * W + tiles * rec_len + J * W + J * q * m;

@@ -264,6 +264,16 @@ static inline int launch_by_tiles(elfihip_ctx* ctx, int m, unsigned grid, const 
 // point wait for the stream.  tests/test_stream_order_gpu.py overwrites every host array argument the moment its call
 // returns, on a busy stream, and compares bit for bit.
 
+// The parameter block of group_args.hpp into the context's `par` buffer, with room for extra_doubles behind it for the
+// caller, on the context's stream; *dpar receives the buffer.  B is pageable: done with when this returns (above).
+inline int upload_group_params(elfihip_ctx* ctx, const GroupParams& B, size_t extra_doubles, double** dpar) {
+  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve((B.words.size() + extra_doubles) * sizeof(double)));
+  *dpar = ctx->par.as<double>();
+  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(*dpar, B.words.data(), B.words.size() * sizeof(double), hipMemcpyHostToDevice,
+                                        ctx->stream));
+  return ELFIHIP_OK;
+}
+
 // rows x m doubles from host memory at pitch ld (in doubles) to contiguous device memory, on the context's stream
 inline int upload_rows(elfihip_ctx* ctx, double* dst, const double* src, size_t rows, int m, int64_t ld) {
   const size_t md = (size_t)m * sizeof(double);

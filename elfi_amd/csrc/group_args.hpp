@@ -1,6 +1,7 @@
-// What the group-statistic entry points (synlik.hip, semibsl.hip, logratio.hip: one workgroup per group of summary rows,
-// m <= 64 columns in tiles of 16) settle on the host: the check of the prefix and penalty lists, the parameter block the
-// kernels read them from, the tile count.  No HIP, no context: tests/test_group_args.py checks them without a GPU.
+// What the entry points over groups of summary rows with prefix and penalty lists (synlik.hip, semibsl.hip, wsemibsl.hip,
+// adjust.hip) settle on the host: the check of the lists, the parameter block the kernels read them from, the number of
+// results, and the count of 16-column tiles that hold m <= 64 columns (launch_by_tiles picks the kernel instance by it, for
+// logratio.hip too).  No HIP, no context: tests/test_group_args.py checks them without a GPU.
 #pragma once
 
 #include <cstdint>
@@ -13,6 +14,11 @@ namespace elfihip {
 
 // 16-column tiles that hold m columns
 inline int group_tiles(int m) { return (m + 15) / 16; }
+
+// Results of a call over G groups: one per group, prefix and penalty; a list that is not given counts as one entry.
+inline size_t group_results(int64_t G, const int64_t* prefixes, int K, int P) {
+  return (size_t)G * (size_t)(prefixes ? K : 1) * (size_t)(P > 0 ? P : 1);
+}
 
 // The lists of a call over n rows per group: K prefixes (or none: the whole group) and P penalties (or none).  Returns what
 // is wrong with them, in the words the caller reports, or an empty string.  (A NaN penalty fails both comparisons.)

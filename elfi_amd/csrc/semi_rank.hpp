@@ -1,5 +1,6 @@
 // What the two semiparametric likelihoods share (semibsl.hip: semiBSL; wsemibsl.hip: the whitened form): the arguments
-// and the launch of the column kernel, the workgroup reductions, and the rank of a value within a column held in LDS.
+// and the launch of the column kernel, the entry points' first checks and the set-up before the launches, the workgroup
+// reductions, and the rank of a value within a column held in LDS.
 #pragma once
 
 #include "common.hpp"
@@ -31,6 +32,50 @@ struct SemiArgs {
 
 // The column kernel of semibsl.hip over GK * m workgroups on the context's stream: Q, stats and, if asked for, u and scores.
 int semibsl_launch_column(elfihip_ctx* ctx, const SemiArgs& A, int64_t GK);
+
+// The checks both likelihoods' entry points begin with; `what` names the likelihood in the texts.  Each goes on with its own
+// bound on the number of workgroups and the check of the lists.
+inline int semi_check(elfihip_ctx* ctx, const char* what, const void* X, int64_t G, int64_t n, int m, int64_t ldx,
+                      const void* y, const void* loglik) {
+  ELFIHIP_REQUIRE(ctx, m >= 1 && m <= SL_MAX_M, "%s: %d summaries; 1 to %d are supported", what, m, SL_MAX_M);
+  ELFIHIP_REQUIRE(ctx, n >= 2 && n <= SEMI_MAX_N, "%s: %lld rows per group; 2 to %d are supported", what, (long long)n,
+                  SEMI_MAX_N);
+  ELFIHIP_REQUIRE(ctx, G >= 1 && ldx >= m, "bad shape G=%lld n=%lld m=%d ldx=%lld", (long long)G, (long long)n, m,
+                  (long long)ldx);
+  ELFIHIP_REQUIRE(ctx, X && y && loglik, "NULL data pointer");
+  return ELFIHIP_OK;
+}
+
+// What both likelihoods do before their launches, on device rows, y and outputs and host lists (checked): the parameter
+// block [prefixes Ke][penalties P] goes to the device, the scratch is reserved as [Q][extra_doubles, the caller's][stats],
+// and A is filled in.
+inline int semi_setup(elfihip_ctx* ctx, SemiArgs& A, const double* dX, int64_t G, int64_t n, int m, int64_t ldx,
+                      const double* dy, const int64_t* prefixes, int K, const double* penalties, int P,
+                      size_t extra_doubles, double* dll, double* du, double* drho, double* dscores) {
+  const GroupParams B = group_params(prefixes, K, n, nullptr, penalties, P);
+  double* dpar;
+  ELFIHIP_TRY(upload_group_params(ctx, B, 0, &dpar));
+  const int MP = 16 * group_tiles(m);
+  const size_t GK = (size_t)G * B.Ke, qd = GK * (size_t)n * MP;
+  ELFIHIP_CHECK_HIP(ctx, ctx->scratch.reserve((qd + extra_doubles + GK * SEMI_STATS) * sizeof(double)));
+  A.X = dX;
+  A.n = n;
+  A.ldx = ldx;
+  A.m = m;
+  A.K = B.Ke;
+  A.P = P;
+  A.MP = MP;
+  A.y = dy;
+  A.prefixes = reinterpret_cast<const int64_t*>(dpar);
+  A.penalties = P > 0 ? dpar + B.pen : nullptr;
+  A.Q = ctx->scratch.as<double>();
+  A.stats = A.Q + qd + extra_doubles;
+  A.loglik = dll;
+  A.u = du;
+  A.rho = drho;
+  A.scores = dscores;
+  return ELFIHIP_OK;
+}
 
 #if defined(__HIPCC__)
 // The sum / the maximum over the workgroup of one value per thread, in a fixed tree; every thread gets it.

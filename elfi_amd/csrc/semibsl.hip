@@ -214,13 +214,7 @@ __global__ __launch_bounds__(256) void semibsl_finish_kernel(SemiArgs A) {
 
 static int semibsl_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, int m, int64_t ldx, const void* y,
                          const int64_t* prefixes, int K, const double* penalties, int P, const void* loglik) {
-  ELFIHIP_REQUIRE(ctx, m >= 1 && m <= SL_MAX_M, "semiparametric likelihood: %d summaries; 1 to %d are supported", m,
-                  SL_MAX_M);
-  ELFIHIP_REQUIRE(ctx, n >= 2 && n <= SEMI_MAX_N, "semiparametric likelihood: %lld rows per group; 2 to %d are supported",
-                  (long long)n, SEMI_MAX_N);
-  ELFIHIP_REQUIRE(ctx, G >= 1 && ldx >= m, "bad shape G=%lld n=%lld m=%d ldx=%lld", (long long)G, (long long)n, m,
-                  (long long)ldx);
-  ELFIHIP_REQUIRE(ctx, X && y && loglik, "NULL data pointer");
+  ELFIHIP_TRY(semi_check(ctx, "semiparametric likelihood", X, G, n, m, ldx, y, loglik));
   ELFIHIP_REQUIRE(ctx, G * (int64_t)(prefixes ? K : 1) * m <= 0x7fffffff, "G K m = %lld x %d x %d workgroups are too many",
                   (long long)G, prefixes ? K : 1, m);
   const std::string bad = group_lists_error(prefixes, K, penalties, P, n);
@@ -239,35 +233,9 @@ int semibsl_launch_column(elfihip_ctx* ctx, const SemiArgs& A, int64_t GK) {
 static int semibsl_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx, const double* dy,
                             const int64_t* prefixes, int K, const double* penalties, int P, double* dll, double* du,
                             double* drho, double* dscores) {
-  hipStream_t st = ctx->stream;
-  // parameter block: [prefixes Ke][penalties P]
-  const GroupParams B = group_params(prefixes, K, n, nullptr, penalties, P);
-  const int Ke = B.Ke;
-  const int64_t GK = G * Ke;
-  const int MP = 16 * group_tiles(m);
-  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve(B.words.size() * sizeof(double)));
-  double* dpar = ctx->par.as<double>();
-  // pageable host memory: the copy is done with it when hipMemcpyAsync returns (common.hpp: pageable uploads)
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, B.words.data(), B.words.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  const size_t qd = (size_t)GK * (size_t)n * MP;
-  ELFIHIP_CHECK_HIP(ctx, ctx->scratch.reserve((qd + (size_t)GK * SEMI_STATS) * sizeof(double)));
   SemiArgs A;
-  A.X = dX;
-  A.n = n;
-  A.ldx = ldx;
-  A.m = m;
-  A.K = Ke;
-  A.P = P;
-  A.MP = MP;
-  A.y = dy;
-  A.prefixes = reinterpret_cast<const int64_t*>(dpar);
-  A.penalties = P > 0 ? dpar + B.pen : nullptr;
-  A.Q = ctx->scratch.as<double>();
-  A.stats = A.Q + qd;
-  A.loglik = dll;
-  A.u = du;
-  A.rho = drho;
-  A.scores = dscores;
+  ELFIHIP_TRY(semi_setup(ctx, A, dX, G, n, m, ldx, dy, prefixes, K, penalties, P, 0, dll, du, drho, dscores));
+  const int64_t GK = G * A.K;
   ELFIHIP_TRY(semibsl_launch_column(ctx, A, GK));
   return launch_by_tiles(
       ctx, m, (unsigned)GK, "semiparametric likelihood finish kernel",
@@ -298,7 +266,7 @@ int elfihip_semi_loglik(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n,
   DeviceGuard g(ctx->device);
   hipStream_t st = ctx->stream;
   const size_t rows = (size_t)G * (size_t)n, md = (size_t)m * sizeof(double);
-  const size_t nll = (size_t)G * (prefixes ? K : 1) * (P > 0 ? P : 1);
+  const size_t nll = group_results(G, prefixes, K, P);
   // in: [X rows m][y m]; out: [loglik][u G m][rho G m m][scores G n m]
   ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((rows * m + (size_t)m) * sizeof(double)));
   ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((nll + (size_t)G * m + (size_t)G * m * m + (scores ? rows * m : 0)) * sizeof(double)));

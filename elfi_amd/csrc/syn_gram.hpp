@@ -6,7 +6,10 @@
 // here (zero chk, the gram_step loop, tot += chk) the loop changed all four instruction streams of semibsl_finish_kernel
 // and its VGPR counts (T = 3: 64 -> 124 or 118, T = 4: 96 -> 132 or 156, by the helper's spelling), and a shared
 // tile-to-LDS store changed all four as well (811 -> 812, 837 -> 825, 928 reordered, 1064 -> 1062 instructions); what that
-// costs is not measured.  The host side these files share is in group_args.hpp and common.hpp.
+// costs is not measured.  Thread 0's scalar tail of semibsl_finish_kernel and wsemi_finish_kernel (sums, log-likelihood,
+// store) as one __forceinline__ function in semi_rank.hpp changed all eight instruction streams (same lengths but T = 4 of
+// wsemi: 1590 -> 1595, SGPRs 62 -> 61), so it stays written out in both.  The host side these files share is in
+// group_args.hpp, common.hpp and semi_rank.hpp.
 #pragma once
 
 #include "mfma_f64.hpp"

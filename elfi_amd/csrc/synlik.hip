@@ -275,10 +275,8 @@ static int synlik_dev_impl(elfihip_ctx* ctx, const double* dX, int G, int64_t n,
   for (int k = 0; k < Ke; ++k) konst[k] = variant == 1 ? unbiased_const(m, prefixes ? prefixes[k] : n) : 0.0;
   // parameter block: [prefixes Ke][konst Ke][penalties P], and behind it on the device [yw m]
   const GroupParams B = group_params(prefixes, K, n, konst.data(), penalties, P);
-  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve((B.words.size() + m) * sizeof(double)));
-  double* dpar = ctx->par.as<double>();
-  // pageable host memory: the copy is done with it when hipMemcpyAsync returns (common.hpp: pageable uploads)
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, B.words.data(), B.words.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  double* dpar;
+  ELFIHIP_TRY(upload_group_params(ctx, B, m, &dpar));
   SynArgs A;
   A.X = dX;
   A.n = n;
@@ -337,7 +335,7 @@ int elfihip_syn_loglik(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, 
   DeviceGuard g(ctx->device);
   hipStream_t st = ctx->stream;
   const size_t rows = (size_t)G * (size_t)n, md = (size_t)m * sizeof(double);
-  const size_t nll = (size_t)G * (prefixes ? K : 1) * (P > 0 ? P : 1);
+  const size_t nll = group_results(G, prefixes, K, P);
   // in: [X rows m][y m][gamma m][W m m]; out: [loglik][mean G m][cov G m m]
   ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((rows * m + 2 * (size_t)m + (size_t)m * m) * sizeof(double)));
   ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((nll + (size_t)G * m + (size_t)G * m * m) * sizeof(double)));

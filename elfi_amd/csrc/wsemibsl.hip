@@ -304,13 +304,7 @@ __global__ __launch_bounds__(256) void wsemi_finish_kernel(WsemiArgs A) {
 
 static int wsemi_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, int m, int64_t ldx, const void* y,
                        const void* W, const int64_t* prefixes, int K, const double* penalties, int P, const void* loglik) {
-  ELFIHIP_REQUIRE(ctx, m >= 1 && m <= SL_MAX_M, "whitened semiparametric likelihood: %d summaries; 1 to %d are supported",
-                  m, SL_MAX_M);
-  ELFIHIP_REQUIRE(ctx, n >= 2 && n <= SEMI_MAX_N,
-                  "whitened semiparametric likelihood: %lld rows per group; 2 to %d are supported", (long long)n, SEMI_MAX_N);
-  ELFIHIP_REQUIRE(ctx, G >= 1 && ldx >= m, "bad shape G=%lld n=%lld m=%d ldx=%lld", (long long)G, (long long)n, m,
-                  (long long)ldx);
-  ELFIHIP_REQUIRE(ctx, X && y && loglik, "NULL data pointer");
+  ELFIHIP_TRY(semi_check(ctx, "whitened semiparametric likelihood", X, G, n, m, ldx, y, loglik));
   ELFIHIP_REQUIRE(ctx, W, "the whitening matrix is NULL");
   const int64_t Ke = prefixes ? K : 1, chunks = (n + WS_ROWS - 1) / WS_ROWS;
   ELFIHIP_REQUIRE(ctx, G * Ke * std::max<int64_t>(m, chunks) <= 0x7fffffff, "G K = %lld x %d: the workgroups are too many",
@@ -325,37 +319,13 @@ static int wsemi_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t
                           const double* dW, const int64_t* prefixes, int K, const double* penalties, int P, double* dll,
                           double* du, double* drho, double* dscale, double* dscores) {
   hipStream_t st = ctx->stream;
-  // parameter block: [prefixes Ke][penalties P]
-  const GroupParams B = group_params(prefixes, K, n, nullptr, penalties, P);
-  const int Ke = B.Ke;
-  const int64_t GK = G * Ke;
-  const int MP = 16 * group_tiles(m);
-  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve(B.words.size() * sizeof(double)));
-  double* dpar = ctx->par.as<double>();
-  // pageable host memory: the copy is done with it when hipMemcpyAsync returns (common.hpp: pageable uploads)
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, B.words.data(), B.words.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  // scratch: [Q][Q'][T][stats]
-  const size_t qd = (size_t)GK * (size_t)n * MP, td = (size_t)GK * (size_t)n * m;
-  ELFIHIP_CHECK_HIP(ctx, ctx->scratch.reserve((2 * qd + td + (size_t)GK * SEMI_STATS) * sizeof(double)));
+  const int64_t GK = G * (prefixes ? K : 1);
+  // scratch: [Q][Q'][T][stats], Q' and T between semi_setup's two
+  const size_t qd = (size_t)GK * (size_t)n * (16 * group_tiles(m)), td = (size_t)GK * (size_t)n * m;
   WsemiArgs A;
-  A.S.X = dX;
-  A.S.n = n;
-  A.S.ldx = ldx;
-  A.S.m = m;
-  A.S.K = Ke;
-  A.S.P = P;
-  A.S.MP = MP;
-  A.S.y = dy;
-  A.S.prefixes = reinterpret_cast<const int64_t*>(dpar);
-  A.S.penalties = P > 0 ? dpar + B.pen : nullptr;
-  A.S.Q = ctx->scratch.as<double>();
+  ELFIHIP_TRY(semi_setup(ctx, A.S, dX, G, n, m, ldx, dy, prefixes, K, penalties, P, qd + td, dll, du, nullptr, nullptr));
   A.Q2 = A.S.Q + qd;
   A.T = A.Q2 + qd;
-  A.S.stats = A.T + td;
-  A.S.loglik = dll;
-  A.S.u = du;
-  A.S.rho = nullptr;
-  A.S.scores = nullptr;
   A.W = dW;
   A.chunks = (int)((n + WS_ROWS - 1) / WS_ROWS);
   A.rho = drho;
@@ -401,7 +371,7 @@ int elfihip_wsemi_loglik(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n
   DeviceGuard g(ctx->device);
   hipStream_t st = ctx->stream;
   const size_t rows = (size_t)G * (size_t)n, md = (size_t)m * sizeof(double);
-  const size_t nll = (size_t)G * (prefixes ? K : 1) * (P > 0 ? P : 1);
+  const size_t nll = group_results(G, prefixes, K, P);
   // in: [X rows m][y m][W m m]; out: [loglik][u G m][rho G m m][scale G m][scores G n m]
   ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((rows * m + (size_t)m + (size_t)m * m) * sizeof(double)));
   ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((nll + 2 * (size_t)G * m + (size_t)G * m * m + (scores ? rows * m : 0)) * sizeof(double)));

@@ -67,8 +67,32 @@ def _variant_code(variant, adjustment):
     return _VARIANTS[variant]
 
 
-def _groups(ssx, ssy, n_groups):
-    """(X (n_groups n, m), y (m), n_groups, n, m, keep_group_axis) of the two layouts ssx may have."""
+def _check_shrinkage(shrinkage, known=(None, 'warton')):
+    # graphical-lasso shrinkage has calls of its own (glasso_loglik, glasso_likelihood, select_glasso_penalty); routing this
+    # keyword to them is a follow-up of a few lines that edits the tests pinning the message below
+    if shrinkage == 'glasso':
+        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
+    if shrinkage not in known:
+        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+
+
+def _whitening_matrix(whitening, m, finite=False):
+    W = np.ascontiguousarray(whitening, dtype=np.float64)
+    if W.shape != (m, m):
+        raise ValueError('whitening must be (%d, %d)' % (m, m))
+    if finite and not np.all(np.isfinite(W)):
+        raise ValueError('whitening has a non-finite entry')
+    return W
+
+
+def _one_group(ssx):
+    """The (n, m) matrix of one group, as the reference's callables receive it."""
+    return np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1)
+
+
+def _groups(ssx, ssy, n_groups, max_rows=None):
+    """(X (n_groups n, m), y (m), n_groups, n, m, keep_group_axis) of the two layouts ssx may have; max_rows: the rows per
+    group the semiparametric kernels take."""
     X = np.asarray(ssx, dtype=np.float64)
     keep_group_axis = X.ndim == 3 or n_groups != 1
     if X.ndim == 3:
@@ -92,17 +116,14 @@ def _groups(ssx, ssy, n_groups):
     y = np.ascontiguousarray(np.asarray(ssy, dtype=np.float64).reshape(-1))
     if y.shape != (m,):
         raise ValueError('ssy has %d entries, ssx has %d columns' % (y.size, m))
+    if max_rows is not None and n > max_rows:
+        raise ValueError('%d rows per group: the semiparametric kernel takes 2 to %d' % (n, max_rows))
     return X, y, n_groups, n, m, keep_group_axis
 
 
 def _penalty_list(shrinkage, penalty, penalties):
     """The Warton penalties as an array, or None without shrinkage."""
-    # graphical-lasso shrinkage has calls of its own (glasso_loglik, glasso_likelihood, select_glasso_penalty); routing this
-    # keyword to them is a follow-up of a few lines that edits the tests pinning the message below
-    if shrinkage == 'glasso':
-        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
-    if shrinkage not in (None, 'warton'):
-        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    _check_shrinkage(shrinkage)
     if shrinkage is None:
         if penalties is not None:
             raise ValueError("penalties need shrinkage='warton'")
@@ -139,6 +160,26 @@ def _squeeze(ll, keep_group_axis, prefixes, penalties):
     return ll
 
 
+def _group_call(name, groups, shrinkage, penalty, penalties, prefixes, middle, extra_shapes, want_extras, ctx):
+    """The (G, K, P) call of the batched likelihoods: entry point `name` over the `groups` of _groups, the checked penalty
+    and prefix lists, and `middle`, what the entry point takes between y and the lists (numbers, or pointers to arrays the
+    caller holds).  The entry point's optional outputs are doubles of `extra_shapes`: allocated if want_extras, NULL
+    otherwise.  Returns the log-likelihoods with the axes the caller asked for, and with want_extras (loglik, *extras)."""
+    X, y, n_groups, n, m, keep_group_axis = groups
+    pen = _penalty_list(shrinkage, penalty, penalties)
+    pre = _prefix_list(prefixes, n)
+    X = np.ascontiguousarray(X)
+    K = 1 if pre is None else pre.size
+    P = 0 if pen is None else pen.size
+    ll = np.empty((n_groups, K, max(P, 1)), dtype=np.float64)
+    extras = [np.empty(shape, dtype=np.float64) if want_extras else None for shape in extra_shapes]
+    ctx = ctx or _lib.default_context()
+    ctx.call(name, _lib.ptr(X), n_groups, n, m, m, _lib.ptr(y), *middle, _lib.ptr(pre), 0 if pre is None else K,
+             _lib.ptr(pen), P, _lib.ptr(ll), *[_lib.ptr(e) for e in extras])
+    ll = _squeeze(ll, keep_group_axis, prefixes, penalties)
+    return (ll, *extras) if want_extras else ll
+
+
 def syn_loglik(ssx, ssy, n_groups=1, variant='standard', shrinkage=None, penalty=None, whitening=None, gamma=None,
                adjustment=None, prefixes=None, penalties=None, return_moments=False, ctx=None):
     """Gaussian synthetic log-likelihoods of `n_groups` groups of simulated summaries in one device call.
@@ -150,33 +191,20 @@ def syn_loglik(ssx, ssy, n_groups=1, variant='standard', shrinkage=None, penalty
     Returns an array (n_groups[, len(prefixes)][, len(penalties)]); a float for one group given as a 2-d array and
     neither list.  With return_moments: (loglik, mean (G, m), cov (G, m, m)) of the full groups after whitening.
     """
-    X, y, n_groups, n, m, keep_group_axis = _groups(ssx, ssy, n_groups)
+    groups = _groups(ssx, ssy, n_groups)
+    G, m = groups[2], groups[4]
     code = _variant_code(variant, adjustment)
     g = None
     if code >= 2:
         if gamma is None:
             raise ValueError('the robust likelihood needs gamma')
         g = np.ascontiguousarray(np.broadcast_to(np.asarray(gamma, dtype=np.float64).reshape(-1), (m,)))
-    pen = _penalty_list(shrinkage, penalty, penalties)
+    _check_shrinkage(shrinkage)
     if shrinkage is not None and code != 0:
         raise ValueError('shrinkage goes with the standard likelihood only (the unbiased and robust ones have none)')
-    pre = _prefix_list(prefixes, n)
-    W = None
-    if whitening is not None:
-        W = np.ascontiguousarray(whitening, dtype=np.float64)
-        if W.shape != (m, m):
-            raise ValueError('whitening must be (%d, %d)' % (m, m))
-    X = np.ascontiguousarray(X)
-    K = 1 if pre is None else pre.size
-    P = 0 if pen is None else pen.size
-    ll = np.empty((n_groups, K, max(P, 1)), dtype=np.float64)
-    mean = np.empty((n_groups, m), dtype=np.float64) if return_moments else None
-    cov = np.empty((n_groups, m, m), dtype=np.float64) if return_moments else None
-    ctx = ctx or _lib.default_context()
-    ctx.call("elfihip_syn_loglik", _lib.ptr(X), n_groups, n, m, m, _lib.ptr(y), _lib.ptr(W), code, _lib.ptr(g),
-             _lib.ptr(pre), 0 if pre is None else K, _lib.ptr(pen), P, _lib.ptr(ll), _lib.ptr(mean), _lib.ptr(cov))
-    ll = _squeeze(ll, keep_group_axis, prefixes, penalties)
-    return (ll, mean, cov) if return_moments else ll
+    W = None if whitening is None else _whitening_matrix(whitening, m)
+    return _group_call("elfihip_syn_loglik", groups, shrinkage, penalty, penalties, prefixes,
+                       (_lib.ptr(W), code, _lib.ptr(g)), [(G, m), (G, m, m)], return_moments, ctx)
 
 
 def semi_loglik(ssx, ssy, n_groups=1, shrinkage=None, penalty=None, prefixes=None, penalties=None, return_parts=False,
@@ -190,23 +218,10 @@ def semi_loglik(ssx, ssy, n_groups=1, shrinkage=None, penalty=None, prefixes=Non
     Cholesky factor.  With return_parts: (loglik, u (G, m), rho (G, m, m), scores (G, n, m)) of the full groups -- the
     integrals of the density estimates up to ssy, the rank correlation before shrinkage, the normal scores of the rows.
     """
-    X, y, n_groups, n, m, keep_group_axis = _groups(ssx, ssy, n_groups)
-    if n > MAX_SEMI_ROWS:
-        raise ValueError('%d rows per group: the semiparametric kernel takes 2 to %d' % (n, MAX_SEMI_ROWS))
-    pen = _penalty_list(shrinkage, penalty, penalties)
-    pre = _prefix_list(prefixes, n)
-    X = np.ascontiguousarray(X)
-    K = 1 if pre is None else pre.size
-    P = 0 if pen is None else pen.size
-    ll = np.empty((n_groups, K, max(P, 1)), dtype=np.float64)
-    u = np.empty((n_groups, m), dtype=np.float64) if return_parts else None
-    rho = np.empty((n_groups, m, m), dtype=np.float64) if return_parts else None
-    scores = np.empty((n_groups, n, m), dtype=np.float64) if return_parts else None
-    ctx = ctx or _lib.default_context()
-    ctx.call("elfihip_semi_loglik", _lib.ptr(X), n_groups, n, m, m, _lib.ptr(y), _lib.ptr(pre), 0 if pre is None else K,
-             _lib.ptr(pen), P, _lib.ptr(ll), _lib.ptr(u), _lib.ptr(rho), _lib.ptr(scores))
-    ll = _squeeze(ll, keep_group_axis, prefixes, penalties)
-    return (ll, u, rho, scores) if return_parts else ll
+    groups = _groups(ssx, ssy, n_groups, MAX_SEMI_ROWS)
+    G, n, m = groups[2:5]
+    return _group_call("elfihip_semi_loglik", groups, shrinkage, penalty, penalties, prefixes, (),
+                       [(G, m), (G, m, m), (G, n, m)], return_parts, ctx)
 
 
 def wsemi_loglik(ssx, ssy, whitening, n_groups=1, shrinkage=None, penalty=None, prefixes=None, penalties=None,
@@ -221,50 +236,30 @@ def wsemi_loglik(ssx, ssy, whitening, n_groups=1, shrinkage=None, penalty=None, 
     the density estimates up to ssy, the rank correlation of the transformed scores before shrinkage, d, the re-ranked
     scores.  whitening = I is not semi_loglik: d is then the standard deviation of the scores, not 1.
     """
-    X, y, n_groups, n, m, keep_group_axis = _groups(ssx, ssy, n_groups)
-    if n > MAX_SEMI_ROWS:
-        raise ValueError('%d rows per group: the semiparametric kernel takes 2 to %d' % (n, MAX_SEMI_ROWS))
+    groups = _groups(ssx, ssy, n_groups, MAX_SEMI_ROWS)
+    G, n, m = groups[2:5]
     if whitening is None:
         raise ValueError('the whitened semiparametric likelihood needs a whitening matrix')
-    W = np.ascontiguousarray(whitening, dtype=np.float64)
-    if W.shape != (m, m):
-        raise ValueError('whitening must be (%d, %d)' % (m, m))
-    if not np.all(np.isfinite(W)):
-        raise ValueError('whitening has a non-finite entry')
-    pen = _penalty_list(shrinkage, penalty, penalties)
-    pre = _prefix_list(prefixes, n)
-    X = np.ascontiguousarray(X)
-    K = 1 if pre is None else pre.size
-    P = 0 if pen is None else pen.size
-    ll = np.empty((n_groups, K, max(P, 1)), dtype=np.float64)
-    u = np.empty((n_groups, m), dtype=np.float64) if return_parts else None
-    rho = np.empty((n_groups, m, m), dtype=np.float64) if return_parts else None
-    scale = np.empty((n_groups, m), dtype=np.float64) if return_parts else None
-    scores = np.empty((n_groups, n, m), dtype=np.float64) if return_parts else None
-    ctx = ctx or _lib.default_context()
-    ctx.call("elfihip_wsemi_loglik", _lib.ptr(X), n_groups, n, m, m, _lib.ptr(y), _lib.ptr(W), _lib.ptr(pre),
-             0 if pre is None else K, _lib.ptr(pen), P, _lib.ptr(ll), _lib.ptr(u), _lib.ptr(rho), _lib.ptr(scale),
-             _lib.ptr(scores))
-    ll = _squeeze(ll, keep_group_axis, prefixes, penalties)
-    return (ll, u, rho, scale, scores) if return_parts else ll
+    W = _whitening_matrix(whitening, m, finite=True)
+    return _group_call("elfihip_wsemi_loglik", groups, shrinkage, penalty, penalties, prefixes, (_lib.ptr(W),),
+                       [(G, m), (G, m, m), (G, m), (G, n, m)], return_parts, ctx)
 
 
 # ---- the reference's likelihood callables (pdf_methods.py:77-135, 138-176, 267-316) ----------------------------------
 
 def gaussian_syn_likelihood(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
     """Standard synthetic log-likelihood of one (n, m) summary matrix; np.array([ll]) as the reference returns."""
-    return np.array([syn_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, shrinkage=shrinkage,
-                                penalty=penalty, whitening=whitening)])
+    return np.array([syn_loglik(_one_group(ssx), ssy, shrinkage=shrinkage, penalty=penalty, whitening=whitening)])
 
 
 def gaussian_syn_likelihood_ghurye_olkin(ssx, ssy):
     """The unbiased estimator of the synthetic likelihood (Ghurye & Olkin); np.array([ll])."""
-    return np.array([syn_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, variant='unbiased')])
+    return np.array([syn_loglik(_one_group(ssx), ssy, variant='unbiased')])
 
 
 def syn_likelihood_misspec(ssx, ssy, gamma, adjustment):
     """Mean- or variance-adjusted synthetic log-likelihood (Frazier & Drovandi); a scalar."""
-    return syn_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, gamma=gamma, adjustment=adjustment)
+    return syn_loglik(_one_group(ssx), ssy, gamma=gamma, adjustment=adjustment)
 
 
 def semi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
@@ -272,8 +267,7 @@ def semi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitening
     device callables (the reference's own return is a (1, 1, 1) array that BSL only adds to a scalar)."""
     if whitening is not None:
         raise NotImplementedError('the whitened semiparametric likelihood (wsemiBSL) is not on the device')
-    return np.array([semi_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, shrinkage=shrinkage,
-                                 penalty=penalty)])
+    return np.array([semi_loglik(_one_group(ssx), ssy, shrinkage=shrinkage, penalty=penalty)])
 
 
 def wsemi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
@@ -281,25 +275,18 @@ def wsemi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitenin
     232-244) of one (n, m) summary matrix; np.array([ll])."""
     if whitening is None:
         raise ValueError('the whitened semiparametric likelihood needs whitening=')
-    return np.array([wsemi_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, whitening,
-                                  shrinkage=shrinkage, penalty=penalty)])
+    return np.array([wsemi_loglik(_one_group(ssx), ssy, whitening, shrinkage=shrinkage, penalty=penalty)])
 
 
 def standard_likelihood(shrinkage=None, penalty=None, whitening=None):
     """pdf_methods.standard_likelihood on the device (Warton shrinkage or none)."""
-    if shrinkage == 'glasso':
-        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
-    if shrinkage not in (None, 'warton'):
-        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    _check_shrinkage(shrinkage)
     return partial(gaussian_syn_likelihood, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
 
 
 def semiparametric_likelihood(shrinkage=None, penalty=None, whitening=None):
     """pdf_methods.semiparametric_likelihood on the device (Warton shrinkage of the correlation matrix or none)."""
-    if shrinkage == 'glasso':
-        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
-    if shrinkage not in (None, 'warton'):
-        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    _check_shrinkage(shrinkage)
     if whitening is not None:
         raise NotImplementedError('the whitened semiparametric likelihood (wsemiBSL) is not on the device')
     return partial(semi_param_kernel_estimate, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
@@ -308,10 +295,7 @@ def semiparametric_likelihood(shrinkage=None, penalty=None, whitening=None):
 def whitened_semiparametric_likelihood(whitening, shrinkage=None, penalty=None):
     """pdf_methods.semiparametric_likelihood(whitening=W) on the device (wsemiBSL; Warton shrinkage or none): a
     `likelihood=` for elfi.BSL, HipBSL, select_penalty and log_SL_stdev."""
-    if shrinkage == 'glasso':
-        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
-    if shrinkage not in (None, 'warton'):
-        raise ValueError('unknown shrinkage %r' % (shrinkage,))
+    _check_shrinkage(shrinkage)
     if whitening is None:
         raise ValueError('the whitened semiparametric likelihood needs a whitening matrix')
     return partial(wsemi_param_kernel_estimate, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
@@ -330,37 +314,30 @@ def robust_likelihood(adjustment):
 
 
 def _likelihood_setup(likelihood, **override):
-    """syn_loglik keywords of one of the callables above (None: the standard one); with semi=True: semi_loglik's; with
-    wsemi=True: wsemi_loglik's."""
+    """(batched call, its keywords) of one of the callables above (None: the standard one): syn_loglik, semi_loglik or
+    wsemi_loglik, which is called as batched(groups, observed, **keywords)."""
     kw = {}
     fn = likelihood
     if isinstance(likelihood, partial):
         fn, kw = likelihood.func, dict(likelihood.keywords)
     if fn is None or fn is gaussian_syn_likelihood:
-        kw.update({k: v for k, v in override.items()})
-        return dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw.get('whitening'))
+        kw.update(override)
+        return syn_loglik, dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw.get('whitening'))
     if fn is semi_param_kernel_estimate:
-        kw.update({k: v for k, v in override.items()})
+        kw.update(override)
         if kw.get('whitening') is not None:
             raise NotImplementedError('the whitened semiparametric likelihood (wsemiBSL) is not on the device')
-        return dict(semi=True, shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'))
+        return semi_loglik, dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'))
     if fn is wsemi_param_kernel_estimate:
         kw.update({k: v for k, v in override.items() if not (k == 'whitening' and v is None)})
         if kw.get('whitening') is None:
             raise ValueError('the whitened semiparametric likelihood needs whitening=')
-        return dict(wsemi=True, shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw['whitening'])
+        return wsemi_loglik, dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw['whitening'])
     if fn is gaussian_syn_likelihood_ghurye_olkin and not override:
-        return dict(variant='unbiased')
+        return syn_loglik, dict(variant='unbiased')
     raise TypeError('the batched evaluation takes the device likelihoods of elfi_amd (standard_likelihood(...), '
                     'semiparametric_likelihood(...), whitened_semiparametric_likelihood(...), unbiased_likelihood()); '
                     'got %r' % (likelihood,))
-
-
-def _batched_call(setup):
-    """The batched call a setup of _likelihood_setup goes to (the marker is taken out of the setup)."""
-    if setup.pop('wsemi', False):
-        return lambda groups, observed, **kw: wsemi_loglik(groups, observed, kw.pop('whitening'), **kw)
-    return semi_loglik if setup.pop('semi', False) else syn_loglik
 
 
 def _generate_groups(model, theta, max_sim, feature_names, M, seed):
@@ -392,10 +369,9 @@ def _prefix_axis(n_sim):
 def log_SL_stdev(model, theta, n_sim, feature_names, likelihood=None, M=20, seed=None):
     """pre_sample_methods.log_SL_stdev: the standard deviation of the log synthetic likelihood for every simulation
     count of n_sim, from M repeats -- the M x len(n_sim) likelihoods in one device call."""
-    setup = _likelihood_setup(likelihood)
+    batched, setup = _likelihood_setup(likelihood)
     counts, uniq, where = _prefix_axis(n_sim)
     groups, observed = _generate_groups(model, theta, int(uniq[-1]), feature_names, M, seed)
-    batched = _batched_call(setup)
     ll = batched(groups, observed, prefixes=uniq, **setup)          # (M, len(uniq))
     return np.std(np.ascontiguousarray(ll[:, where].T), axis=1)     # (len(n_sim), M), the reference's layout
 
@@ -404,17 +380,13 @@ def select_penalty(model, n_sim, theta, feature_names, likelihood=None, lmdas=No
                    shrinkage='warton', whitening=None, seed=None, verbose=False):
     """pre_sample_methods.select_penalty with Warton shrinkage: for every simulation count the penalty whose log-likelihood
     standard deviation over M repeats is closest to sigma -- the M x len(n_sim) x len(lmdas) likelihoods in one call."""
-    if shrinkage == 'glasso':
-        raise NotImplementedError("graphical-lasso shrinkage is not on the device; shrinkage='warton' is")
-    if shrinkage != 'warton':
-        raise ValueError('unknown shrinkage %r' % (shrinkage,))
-    setup = _likelihood_setup(likelihood, shrinkage=shrinkage, whitening=whitening)
+    _check_shrinkage(shrinkage, known=('warton',))
+    batched, setup = _likelihood_setup(likelihood, shrinkage=shrinkage, whitening=whitening)
     if lmdas is None:
         lmdas = list(np.arange(0.2, 0.8, 0.02))
     counts, uniq, where = _prefix_axis(n_sim)
     groups, observed = _generate_groups(model, theta, int(uniq[-1]), feature_names, M, seed)
     setup.pop('penalty', None)
-    batched = _batched_call(setup)
     logliks = batched(groups, observed, prefixes=uniq, penalties=lmdas, **setup)        # (M, len(uniq), len(lmdas))
     spread = logliks.std(axis=0)[where]                    # over the repeats: (len(n_sim), len(lmdas))
     pick = np.abs(spread - sigma).argmin(axis=1)           # ties go to the smaller penalty index, as argmin does
@@ -501,11 +473,7 @@ def glasso_loglik(ssx, ssy, penalty=None, penalties=None, n_groups=1, whitening=
     a, tol, max_iter = _glasso_args(penalty if penalties is None else penalties, tol, max_iter)
     if penalties is None and a.size != 1:
         raise ValueError('penalty is one number; a list goes to penalties')
-    Wh = None
-    if whitening is not None:
-        Wh = np.ascontiguousarray(whitening, dtype=np.float64)
-        if Wh.shape != (m, m):
-            raise ValueError('whitening must be (%d, %d)' % (m, m))
+    Wh = None if whitening is None else _whitening_matrix(whitening, m)
     X = np.ascontiguousarray(X)
     P = a.size
     ll = np.empty((n_groups, P), dtype=np.float64)
@@ -530,8 +498,7 @@ def gaussian_syn_likelihood_glasso(ssx, ssy, shrinkage=None, penalty=None, white
     """gaussian_syn_likelihood(..., shrinkage='glasso') of one (n, m) summary matrix; np.array([ll])."""
     if shrinkage not in (None, 'glasso'):
         raise ValueError("this likelihood is the graphical-lasso one; shrinkage=%r goes to standard_likelihood" % (shrinkage,))
-    return np.array([glasso_loglik(np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1), ssy, penalty=penalty,
-                                   whitening=whitening, standardise=standardise)])
+    return np.array([glasso_loglik(_one_group(ssx), ssy, penalty=penalty, whitening=whitening, standardise=standardise)])
 
 
 def glasso_likelihood(penalty, whitening=None, standardise=False):

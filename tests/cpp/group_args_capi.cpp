@@ -9,6 +9,10 @@ extern "C" {
 
 int ga_tiles(int m) { return group_tiles(m); }
 
+long long ga_results(long long G, const long long* prefixes, int K, int P) {
+  return (long long)group_results(G, reinterpret_cast<const int64_t*>(prefixes), K, P);
+}
+
 // The error text goes to buf (empty: the lists are good); returns its length.
 int ga_lists_error(const long long* prefixes, int K, const double* penalties, int P, long long n, char* buf, int cap) {
   const std::string e = group_lists_error(reinterpret_cast<const int64_t*>(prefixes), K, penalties, P, n);

@@ -9,6 +9,7 @@ The header is plain C++ (no HIP), so it is compiled here with g++ behind a tiny 
   block    [Ke prefixes as int64 bit patterns][Ke constants, only if given][P penalties]; Ke = K, or 1 without prefixes
            (the one prefix is n)
   tiles    ceil(m / 16)
+  results  G x (K, or 1 without prefixes) x (P, or 1 without penalties)
 """
 import ctypes as C
 import os
@@ -30,6 +31,8 @@ def ga(tmp_path_factory):
     lib = C.CDLL(out)
     lib.ga_tiles.restype = C.c_int
     lib.ga_tiles.argtypes = [C.c_int]
+    lib.ga_results.restype = LL
+    lib.ga_results.argtypes = [LL, C.POINTER(LL), C.c_int, C.c_int]
     lib.ga_lists_error.restype = C.c_int
     lib.ga_lists_error.argtypes = [C.POINTER(LL), C.c_int, C.POINTER(C.c_double), C.c_int, LL, C.c_char_p, C.c_int]
     lib.ga_params.restype = C.c_int
@@ -150,6 +153,15 @@ def test_block_without_lists_is_the_one_prefix_n(ga):
     Ke, konst, pen, words = params(ga, None, 1, 7, [2.5], None, 0)
     assert (Ke, konst, pen) == (1, 1, 2)
     assert as_int64(words[0]) == 7 and as_double(words[1]) == 2.5 and len(words) == 2
+
+
+def test_results_count_an_absent_list_as_one_entry(ga):
+    G = 5
+    assert ga.ga_results(G, None, 0, 0) == G                    # no prefixes and no penalties
+    assert ga.ga_results(G, _ll([2, 5, N]), 3, 0) == G * 3      # prefixes only
+    assert ga.ga_results(G, None, 0, 4) == G * 4                # penalties only
+    assert ga.ga_results(G, _ll([2, 5, N]), 3, 4) == G * 3 * 4
+    assert ga.ga_results(G, None, 1, 0) == G                    # K = 1 without a list is the whole group
 
 
 def test_tiles(ga):

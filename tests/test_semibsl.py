@@ -129,9 +129,10 @@ def test_factories_have_the_reference_shapes():
     assert elfi_amd.semiparametric_likelihood().keywords == dict(shrinkage=None, penalty=None, whitening=None)
     assert 'adjustment' not in lik.keywords                                             # BSL must not take it for robust
     # the batched tools recognise the partial and send it to semi_loglik; the Gaussian default is untouched
-    assert synlik._likelihood_setup(elfi_amd.semiparametric_likelihood()) == dict(semi=True, shrinkage=None, penalty=None)
+    semi = synlik.semi_loglik
+    assert synlik._likelihood_setup(elfi_amd.semiparametric_likelihood()) == (semi, dict(shrinkage=None, penalty=None))
     setup = synlik._likelihood_setup(lik, shrinkage='warton', whitening=None)
-    assert setup == dict(semi=True, shrinkage='warton', penalty=0.3)
-    assert synlik._likelihood_setup(None) == dict(shrinkage=None, penalty=None, whitening=None)
-    assert synlik._likelihood_setup(synlik.semi_param_kernel_estimate) == dict(semi=True, shrinkage=None, penalty=None)
+    assert setup == (semi, dict(shrinkage='warton', penalty=0.3))
+    assert synlik._likelihood_setup(None) == (synlik.syn_loglik, dict(shrinkage=None, penalty=None, whitening=None))
+    assert synlik._likelihood_setup(synlik.semi_param_kernel_estimate) == (semi, dict(shrinkage=None, penalty=None))
     assert elfi_amd.semi_loglik is synlik.semi_loglik

@@ -108,8 +108,9 @@ def test_factories_have_the_reference_shapes():
     rob = elfi_amd.robust_likelihood('variance')
     assert isinstance(rob, partial) and rob.keywords == {'adjustment': 'variance'}      # what BSL.__init__ looks for
     assert elfi_amd.unbiased_likelihood() is synlik.gaussian_syn_likelihood_ghurye_olkin
-    assert synlik._likelihood_setup(None) == dict(shrinkage=None, penalty=None, whitening=None)
-    assert synlik._likelihood_setup(lik, shrinkage='warton', whitening=None)['penalty'] == 0.3
-    assert synlik._likelihood_setup(elfi_amd.unbiased_likelihood()) == dict(variant='unbiased')
+    assert synlik._likelihood_setup(None) == (synlik.syn_loglik, dict(shrinkage=None, penalty=None, whitening=None))
+    batched, setup = synlik._likelihood_setup(lik, shrinkage='warton', whitening=None)
+    assert batched is synlik.syn_loglik and setup['penalty'] == 0.3
+    assert synlik._likelihood_setup(elfi_amd.unbiased_likelihood()) == (synlik.syn_loglik, dict(variant='unbiased'))
     counts, uniq, where = synlik._prefix_axis([200, 50, 100, 50])
     assert list(uniq) == [50, 100, 200] and list(uniq[where]) == [200, 50, 100, 50]

@@ -90,9 +90,11 @@ def test_factory_and_routing():
     lik = elfi_amd.whitened_semiparametric_likelihood(W, shrinkage='warton', penalty=0.3)
     assert isinstance(lik, partial) and lik.func is synlik.wsemi_param_kernel_estimate
     assert set(lik.keywords) == {'shrinkage', 'penalty', 'whitening'} and lik.keywords['whitening'] is W
-    assert synlik._likelihood_setup(lik) == dict(wsemi=True, shrinkage='warton', penalty=0.3, whitening=W)
+    assert synlik._likelihood_setup(lik) == (synlik.wsemi_loglik, dict(shrinkage='warton', penalty=0.3, whitening=W))
     # select_penalty's call: its own whitening=None must not erase the partial's
-    assert synlik._likelihood_setup(lik, shrinkage='warton', whitening=None)['whitening'] is W
+    batched, setup = synlik._likelihood_setup(lik, shrinkage='warton', whitening=None)
+    assert batched is synlik.wsemi_loglik and setup['whitening'] is W
     with pytest.raises(ValueError):
         synlik._likelihood_setup(synlik.wsemi_param_kernel_estimate)                    # the function alone has no W
-    assert synlik._likelihood_setup(synlik.wsemi_param_kernel_estimate, whitening=W)['whitening'] is W
+    batched, setup = synlik._likelihood_setup(synlik.wsemi_param_kernel_estimate, whitening=W)
+    assert batched is synlik.wsemi_loglik and setup['whitening'] is W
