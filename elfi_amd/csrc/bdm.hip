@@ -36,6 +36,7 @@
 
 #include "dist_metrics.hpp"
 #include "event_sim.hpp"
+#include "host_stage.hpp"
 #include "np_sum.hpp"
 #include "philox.hpp"
 
@@ -501,32 +502,24 @@ int elfihip_bdm_clusters(elfihip_ctx* ctx, const double* U, uint64_t seed, uint6
   if (!ctx) return fail(nullptr, ELFIHIP_ERR_ARG, "ctx is NULL");
   ELFIHIP_TRY(bd_model_check(ctx, first, n, N, mode, max_events, alpha, delta, tau, obs, D));
   DeviceGuard g(ctx->device);
-  const size_t nn = (size_t)n, nu = U ? nn * 2 * (size_t)max_events : 0, pb = nn * sizeof(double);
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((nu + 3 * nn) * sizeof(double)));
-  const size_t o_d = align256(2 * pb), o_e = o_d + align256(pb), o_c = o_e + align256(nn * sizeof(int64_t));
-  const size_t o_s = o_c + align256(nn * (size_t)N * sizeof(int32_t));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(o_s + nn * sizeof(int32_t)));
-  char* out = ctx->out.as<char>();
-  double *dU = ctx->in.as<double>(), *dpar = dU + nu;
-  double* dT = ctx->out.as<double>();
-  double* dD = reinterpret_cast<double*>(out + o_d);
-  int64_t* dev = reinterpret_cast<int64_t*>(out + o_e);
-  int32_t* dCl = reinterpret_cast<int32_t*>(out + o_c);
-  int32_t* dst = reinterpret_cast<int32_t*>(out + o_s);
-  if (U) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dU, U, nu * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, alpha, pb, hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar + nn, delta, pb, hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar + 2 * nn, tau, pb, hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(bd_dev_impl(ctx, U ? dU : nullptr, 2 * max_events, seed, stream, first, n, N, mode, max_events, dpar, dpar + nn,
-                          dpar + 2 * nn, t2_n, obs, Cl ? dCl : nullptr, N, status ? dst : nullptr, events ? dev : nullptr,
-                          T ? dT : nullptr, 2, D ? dD : nullptr));
-  if (Cl) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Cl, dCl, nn * (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (status) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(status, dst, nn * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (events) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(events, dev, nn * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (T) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(T, dT, 2 * pb, hipMemcpyDeviceToHost, ctx->stream));
-  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, pb, hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const size_t nn = (size_t)n;
+  double *dU, *dalpha, *ddelta, *dtau, *dT, *dD;
+  int32_t *dCl, *dst;
+  int64_t* dev;
+  HostStage st(ctx);
+  st.in(&dU, U, nn * 2 * (size_t)max_events);
+  st.in(&dalpha, alpha, nn);
+  st.in(&ddelta, delta, nn);
+  st.in(&dtau, tau, nn);
+  st.out(&dCl, Cl, nn * (size_t)N);
+  st.out(&dst, status, nn);
+  st.out(&dev, events, nn);
+  st.out(&dT, T, 2 * nn);
+  st.out(&dD, D, nn);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(bd_dev_impl(ctx, dU, 2 * max_events, seed, stream, first, n, N, mode, max_events, dalpha, ddelta, dtau, t2_n, obs, dCl,
+                          N, dst, dev, dT, 2, dD));
+  return st.download();
 }
 
 int elfihip_bdm_draws_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int64_t n_events,
@@ -541,12 +534,12 @@ int elfihip_bdm_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t 
   ELFIHIP_TRY(bd_shape_check(ctx, first, n, n_events));
   ELFIHIP_REQUIRE(ctx, U, "NULL pointer");
   DeviceGuard g(ctx->device);
-  const size_t nu = (size_t)n * 2 * (size_t)n_events;
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(nu * sizeof(double)));
-  ELFIHIP_TRY(bd_draws_impl(ctx, seed, stream, first, n, n_events, ctx->out.as<double>(), 2 * n_events));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(U, ctx->out.p, nu * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  double* dU;
+  HostStage st(ctx);
+  st.out(&dU, U, (size_t)n * 2 * (size_t)n_events);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(bd_draws_impl(ctx, seed, stream, first, n, n_events, dU, 2 * n_events));
+  return st.download();
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@
 #include <cmath>
 
 #include "event_sim.hpp"
+#include "host_stage.hpp"
 #include "lane_sort.hpp"
 #include "np_sum.hpp"
 #include "philox.hpp"
@@ -432,38 +433,27 @@ int elfihip_daycare_summaries(elfihip_ctx* ctx, const double* E, const double* U
   ELFIHIP_REQUIRE(ctx, (E == nullptr) == (U == nullptr), "E and U are given together or not at all");
   ELFIHIP_REQUIRE(ctx, t1 && t2 && t3, "NULL parameter pointer");
   DeviceGuard g(ctx->device);
-  const size_t nn = (size_t)n, pairs = nn * (size_t)n_dcc, ne = E ? pairs * (size_t)max_events : 0;
-  const size_t nm = M ? pairs * (size_t)n_obs : 0, ns = S ? nn * DC_SUMMARIES * (size_t)n_dcc : 0;
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((2 * ne + 3 * nn) * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((nm + ns + nn + 2 * pairs) * sizeof(double) + pairs * sizeof(int32_t)));
-  double* dE = ctx->in.as<double>();
-  double* dU = dE + ne;
-  double* dpar = dU + ne;
-  uint64_t* dM = ctx->out.as<uint64_t>();
-  double* dS = reinterpret_cast<double*>(dM + nm);
-  double* dD = dS + ns;
-  double* dT = dD + nn;
-  int64_t* dev = reinterpret_cast<int64_t*>(dT + pairs);
-  int32_t* dst = reinterpret_cast<int32_t*>(dev + pairs);
-  if (E) {
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dE, E, ne * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dU, U, ne * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  }
-  const double* par[3] = {t1, t2, t3};
-  for (int j = 0; j < 3; ++j)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar + j * nn, par[j], nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(dc_dev_impl(ctx, E ? dE : nullptr, max_events, E ? dU : nullptr, max_events, seed, stream, first, n, n_dcc, n_ind,
-                          n_strains, n_obs, time_end, max_events, dpar, dpar + nn, dpar + 2 * nn, freq, obs, M ? dM : nullptr, n_obs,
-                          T ? dT : nullptr, status ? dst : nullptr, events ? dev : nullptr, S ? dS : nullptr,
-                          (int64_t)DC_SUMMARIES * n_dcc, D ? dD : nullptr));
-  if (M) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(M, dM, nm * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (S) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(S, dS, ns * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (T) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(T, dT, pairs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (events) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(events, dev, pairs * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (status) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(status, dst, pairs * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const size_t nn = (size_t)n, pairs = nn * (size_t)n_dcc, ne = pairs * (size_t)max_events;
+  double *dE, *dU, *dt1, *dt2, *dt3, *dS, *dD, *dT;
+  uint64_t* dM;
+  int64_t* dev;
+  int32_t* dst;
+  HostStage st(ctx);
+  st.in(&dE, E, ne);
+  st.in(&dU, U, ne);
+  st.in(&dt1, t1, nn);
+  st.in(&dt2, t2, nn);
+  st.in(&dt3, t3, nn);
+  st.out(&dM, M, pairs * (size_t)n_obs);
+  st.out(&dS, S, pairs * DC_SUMMARIES);
+  st.out(&dD, D, nn);
+  st.out(&dT, T, pairs);
+  st.out(&dev, events, pairs);
+  st.out(&dst, status, pairs);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(dc_dev_impl(ctx, dE, max_events, dU, max_events, seed, stream, first, n, n_dcc, n_ind, n_strains, n_obs, time_end,
+                          max_events, dt1, dt2, dt3, freq, obs, dM, n_obs, dT, dst, dev, dS, (int64_t)DC_SUMMARIES * n_dcc, dD));
+  return st.download();
 }
 
 int elfihip_daycare_draws_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int n_dcc,
@@ -480,14 +470,13 @@ int elfihip_daycare_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int6
   ELFIHIP_REQUIRE(ctx, E && U, "NULL pointer");
   DeviceGuard g(ctx->device);
   const size_t ne = (size_t)n * (size_t)n_dcc * (size_t)n_events;
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(2 * ne * sizeof(double)));
-  double* dE = ctx->out.as<double>();
-  double* dU = dE + ne;
+  double *dE, *dU;
+  HostStage st(ctx);
+  st.out(&dE, E, ne);
+  st.out(&dU, U, ne);
+  ELFIHIP_TRY(st.upload());
   ELFIHIP_TRY(dc_draws_impl(ctx, seed, stream, first, n, n_dcc, n_events, dE, n_events, dU, n_events));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(E, dE, ne * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(U, dU, ne * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  return st.download();
 }
 
 int elfihip_daycare_distance_dev(elfihip_ctx* ctx, const double* dX, int64_t ldx, int64_t n, int k, int m, const double* obs,
@@ -502,14 +491,13 @@ int elfihip_daycare_distance(elfihip_ctx* ctx, const double* X, int64_t n, int k
   ELFIHIP_TRY(dc_distance_check(ctx, n, k, m, obs));
   ELFIHIP_REQUIRE(ctx, X && D, "NULL pointer");
   DeviceGuard g(ctx->device);
-  const size_t nx = (size_t)n * k * m;
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(nx * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((size_t)n * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(ctx->in.p, X, nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(dc_distance_dev_impl(ctx, ctx->in.as<double>(), (int64_t)k * m, n, k, m, obs, ctx->out.as<double>()));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, ctx->out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  double *dX, *dD;
+  HostStage st(ctx);
+  st.in(&dX, X, (size_t)n * k * m);
+  st.out(&dD, D, (size_t)n);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(dc_distance_dev_impl(ctx, dX, (int64_t)k * m, n, k, m, obs, dD));
+  return st.download();
 }
 
 }  // extern "C"

@@ -33,6 +33,7 @@
 
 #include "dist_metrics.hpp"
 #include "event_sim.hpp"
+#include "host_stage.hpp"
 #include "np_sum.hpp"
 #include "philox.hpp"
 
@@ -382,42 +383,27 @@ int elfihip_lv_summaries(elfihip_ctx* ctx, const double* E, const double* U, con
   ELFIHIP_REQUIRE(ctx, r1 && r2 && r3 && prey && pred, "NULL parameter pointer");
   ELFIHIP_REQUIRE(ctx, !D || obs, "a distance needs the observed summaries");
   DeviceGuard g(ctx->device);
-  const size_t nn = (size_t)n, ne = E ? nn * (size_t)max_events : 0, nz = Z ? nn * 2 * (size_t)(n_obs - 1) : 0;
-  const size_t ny = Y ? nn * 2 * (size_t)n_obs : 0;
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((2 * ne + nz + 6 * nn) * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((ny + (LV_SUMMARIES + 3) * nn) * sizeof(double) + nn * sizeof(int32_t)));
-  double* dE = ctx->in.as<double>();
-  double* dU = dE + ne;
-  double* dZ = dU + ne;
-  double* dpar = dZ + nz;
-  double* dY = ctx->out.as<double>();
-  double* dS = dY + ny;
-  double* dD = dS + LV_SUMMARIES * nn;
-  double* dT = dD + nn;
-  int64_t* dev = reinterpret_cast<int64_t*>(dT + nn);
-  int32_t* dst = reinterpret_cast<int32_t*>(dev + nn);
-  const size_t pb = nn * sizeof(double);
-  if (E) {
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dE, E, ne * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dU, U, ne * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (Z) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dZ, Z, nz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  const double* par[6] = {r1, r2, r3, prey, pred, sigma};
-  for (int j = 0; j < 6; ++j)
-    if (par[j]) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar + j * nn, par[j], pb, hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(lv_dev_impl(ctx, E ? dE : nullptr, max_events, E ? dU : nullptr, max_events, Z ? dZ : nullptr, 2 * (int64_t)(n_obs - 1),
-                          seed, stream, first, n, n_obs, time_end, max_events, dpar, dpar + nn, dpar + 2 * nn, dpar + 3 * nn,
-                          dpar + 4 * nn, sigma ? dpar + 5 * nn : nullptr, obs, Y ? dY : nullptr, 2 * (int64_t)n_obs,
-                          T ? dT : nullptr, status ? dst : nullptr, events ? dev : nullptr, S ? dS : nullptr, LV_SUMMARIES,
-                          D ? dD : nullptr));
-  if (Y) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Y, dY, ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (S) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(S, dS, LV_SUMMARIES * pb, hipMemcpyDeviceToHost, ctx->stream));
-  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, pb, hipMemcpyDeviceToHost, ctx->stream));
-  if (T) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(T, dT, pb, hipMemcpyDeviceToHost, ctx->stream));
-  if (events) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(events, dev, nn * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (status) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(status, dst, nn * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const size_t nn = (size_t)n, ne = nn * (size_t)max_events;
+  const double* hpar[6] = {r1, r2, r3, prey, pred, sigma};   // sigma may be NULL: no observation noise
+  double *dE, *dU, *dZ, *dpar[6], *dY, *dS, *dD, *dT;
+  int64_t* dev;
+  int32_t* dst;
+  HostStage st(ctx);
+  st.in(&dE, E, ne);
+  st.in(&dU, U, ne);
+  st.in(&dZ, Z, nn * 2 * (size_t)(n_obs - 1));
+  for (int j = 0; j < 6; ++j) st.in(&dpar[j], hpar[j], nn);
+  st.out(&dY, Y, nn * 2 * (size_t)n_obs);
+  st.out(&dS, S, nn * LV_SUMMARIES);
+  st.out(&dD, D, nn);
+  st.out(&dT, T, nn);
+  st.out(&dev, events, nn);
+  st.out(&dst, status, nn);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(lv_dev_impl(ctx, dE, max_events, dU, max_events, dZ, 2 * (int64_t)(n_obs - 1), seed, stream, first, n, n_obs, time_end,
+                          max_events, dpar[0], dpar[1], dpar[2], dpar[3], dpar[4], dpar[5], obs, dY, 2 * (int64_t)n_obs, dT, dst, dev,
+                          dS, LV_SUMMARIES, dD));
+  return st.download();
 }
 
 int elfihip_lv_draws_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int64_t n_events,
@@ -433,14 +419,13 @@ int elfihip_lv_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t f
   ELFIHIP_REQUIRE(ctx, n >= 1 && n_events >= 1 && n_events <= ELFIHIP_LV_MAX_EVENTS && E && U, "bad arguments");
   DeviceGuard g(ctx->device);
   const size_t ne = (size_t)n * (size_t)n_events;
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(2 * ne * sizeof(double)));
-  double* dE = ctx->out.as<double>();
-  double* dU = dE + ne;
+  double *dE, *dU;
+  HostStage st(ctx);
+  st.out(&dE, E, ne);
+  st.out(&dU, U, ne);
+  ELFIHIP_TRY(st.upload());
   ELFIHIP_TRY(lv_draws_impl(ctx, seed, stream, first, n, n_events, dE, n_events, dU, n_events));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(E, dE, ne * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(U, dU, ne * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  return st.download();
 }
 
 }  // extern "C"

@@ -32,6 +32,7 @@
 
 #include "dist_launch.hpp"
 #include "dist_metrics.hpp"
+#include "host_stage.hpp"
 #include "lane_sort.hpp"
 #include "philox.hpp"
 
@@ -329,31 +330,22 @@ int elfihip_gnk_summaries(elfihip_ctx* ctx, const double* Z, uint64_t seed, uint
   if (n == 0) return ELFIHIP_OK;
   DeviceGuard g(ctx->device);
   const int np = dim == 1 ? 4 : 9, mo = GNK_NOCT * dim, mr = 4 * dim;
-  const size_t nn = (size_t)n * n_obs * dim, nz = Z ? nn : 0;
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((nz + (size_t)n * np) * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(((Y ? nn : 0) + (Zo ? nn : 0) + (Ys ? nn : 0) + (size_t)n * (mo + mr + 1)) * sizeof(double)));
-  double* dZ = ctx->in.as<double>();
-  double* dP = dZ + nz;
-  double* dO = ctx->out.as<double>();
-  double* dR = dO + (size_t)n * mo;
-  double* dD = dR + (size_t)n * mr;
-  double* dY = dD + n;
-  double* dZo = dY + (Y ? nn : 0);
-  double* dYs = dZo + (Zo ? nn : 0);
-  if (Z) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dZ, Z, nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dP, P, (size_t)n * np * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(gnk_dev_impl(ctx, Z ? dZ : nullptr, (int64_t)n_obs * dim, seed, stream, n, n_obs, dim, dP, np, c, lo, hi, t, obs,
-                           which, Y ? dY : nullptr, (int64_t)n_obs * dim, Zo ? dZo : nullptr, (int64_t)n_obs * dim,
-                           Ys ? dYs : nullptr, (int64_t)n_obs * dim, O ? dO : nullptr, mo, R ? dR : nullptr, mr,
-                           D ? dD : nullptr));
-  if (O) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(O, dO, (size_t)n * mo * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (R) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(R, dR, (size_t)n * mr * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (Y) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Y, dY, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (Zo) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Zo, dZo, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (Ys) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Ys, dYs, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const int64_t L = (int64_t)n_obs * dim;
+  const size_t nn = (size_t)n, ns = nn * (size_t)L;
+  double *dZ, *dP, *dO, *dR, *dD, *dY, *dZo, *dYs;
+  HostStage st(ctx);
+  st.in(&dZ, Z, ns);
+  st.in(&dP, P, nn * np);
+  st.out(&dO, O, nn * mo);
+  st.out(&dR, R, nn * mr);
+  st.out(&dD, D, nn);
+  st.out(&dY, Y, ns);
+  st.out(&dZo, Zo, ns);
+  st.out(&dYs, Ys, ns);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(gnk_dev_impl(ctx, dZ, L, seed, stream, n, n_obs, dim, dP, np, c, lo, hi, t, obs, which, dY, L, dZo, L, dYs, L, dO, mo,
+                           dR, mr, dD));
+  return st.download();
 }
 
 }  // extern "C"

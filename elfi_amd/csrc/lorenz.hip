@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "dist_metrics.hpp"
+#include "host_stage.hpp"
 #include "philox.hpp"
 
 #pragma clang fp contract(off)
@@ -394,29 +395,20 @@ int elfihip_lorenz_summaries(elfihip_ctx* ctx, const double* E, uint64_t seed, u
   if (n == 0) return ELFIHIP_OK;
   DeviceGuard g(ctx->device);
   const size_t series = (size_t)n_timestep * n_obs, draws = series - n_obs;
-  const size_t ne = E ? (size_t)n * draws : 0, ny0 = y0_per_simulation ? (size_t)n * n_obs : (size_t)n_obs;
-  const size_t ns = (size_t)n * 6, ny = Y ? (size_t)n * series : 0;
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((ne + 2 * (size_t)n + ny0) * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((ns + (size_t)n + ny) * sizeof(double)));
-  double* dE = ctx->in.as<double>();
-  double* dt1 = dE + ne;
-  double* dt2 = dt1 + n;
-  double* dy0 = dt2 + n;
-  double* dS = ctx->out.as<double>();
-  double* dD = dS + ns;
-  double* dY = dD + n;
-  if (E) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dE, E, ne * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt1, t1, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt2, t2, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dy0, y0, ny0 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(lorenz_dev_impl(ctx, E ? dE : nullptr, (int64_t)draws, seed, stream, n, n_obs, n_timestep, dt1, dt2, f, c, phi, h,
-                              dy0, y0_per_simulation ? n_obs : 0, obs, dS, 6, Y ? dY : nullptr, (int64_t)series,
-                              D ? dD : nullptr));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(S, dS, ns * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (Y) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Y, dY, ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const size_t nn = (size_t)n;
+  double *dE, *dt1, *dt2, *dy0, *dS, *dD, *dY;
+  HostStage st(ctx);
+  st.in(&dE, E, nn * draws);
+  st.in(&dt1, t1, nn);
+  st.in(&dt2, t2, nn);
+  st.in(&dy0, y0, y0_per_simulation ? nn * n_obs : (size_t)n_obs);
+  st.out(&dS, S, nn * 6);
+  st.out(&dD, D, nn);
+  st.out(&dY, Y, nn * series);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(lorenz_dev_impl(ctx, dE, (int64_t)draws, seed, stream, n, n_obs, n_timestep, dt1, dt2, f, c, phi, h, dy0,
+                              y0_per_simulation ? n_obs : 0, obs, dS, 6, dY, (int64_t)series, dD));
+  return st.download();
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 
+#include "host_stage.hpp"
 #include "poisson.hpp"
 
 #pragma clang fp contract(off)
@@ -39,16 +40,13 @@ int elfihip_poisson(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t n,
   ELFIHIP_REQUIRE(ctx, n >= 0 && (n == 0 || (lam && out)), "bad arguments");
   if (n == 0) return ELFIHIP_OK;
   DeviceGuard g(ctx->device);
-  const size_t bytes = (size_t)n * sizeof(double);
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(bytes));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(bytes));
-  double* dlam = ctx->in.as<double>();
-  double* dout = ctx->out.as<double>();
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dlam, lam, bytes, hipMemcpyHostToDevice, ctx->stream));
+  double *dlam, *dout;
+  HostStage st(ctx);
+  st.in(&dlam, lam, (size_t)n);
+  st.out(&dout, out, (size_t)n);
+  ELFIHIP_TRY(st.upload());
   ELFIHIP_TRY(elfihip_poisson_dev(ctx, seed, stream, n, dlam, dout));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  return st.download();
 }
 
 }  // extern "C"

@@ -40,6 +40,7 @@
 #include <cmath>
 
 #include "event_sim.hpp"
+#include "host_stage.hpp"
 #include "philox.hpp"
 
 #pragma clang fp contract(off)
@@ -319,37 +320,26 @@ int elfihip_assay_summaries(elfihip_ctx* ctx, const int32_t* C, const double* P,
   if (!ctx) return fail(nullptr, ELFIHIP_ERR_ARG, "ctx is NULL");
   ELFIHIP_TRY(sa_model_check(ctx, first, n, nrows, ncols, n_iter, obs_every, init, C, P, M, pm, pp, S));
   DeviceGuard g(ctx->device);
-  const size_t nn = (size_t)n, nd = C ? nn * (size_t)n_iter * 2 * (size_t)(nrows * ncols) : 0, ns = nn * (size_t)(n_iter / obs_every + 1);
-  const size_t nf = frames ? ns * SA_WORDS : 0;
-  const size_t i_c = align256((nd + 2 * nn) * sizeof(double)), i_m = i_c + align256(nd * sizeof(int32_t));
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(i_m + nd));
-  const size_t o_e = align256(ns * sizeof(double)), o_f = o_e + align256(2 * nn * sizeof(int64_t));
-  const size_t o_s = o_f + align256(nf * sizeof(uint32_t));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(o_s + nn * sizeof(int32_t)));
-  char *in = ctx->in.as<char>(), *out = ctx->out.as<char>();
-  double *dP = ctx->in.as<double>(), *dpar = dP + nd;
-  int32_t* dC = reinterpret_cast<int32_t*>(in + i_c);
-  uint8_t* dM = reinterpret_cast<uint8_t*>(in + i_m);
-  double* dS = ctx->out.as<double>();
-  int64_t* dev = reinterpret_cast<int64_t*>(out + o_e);
-  uint32_t* dfr = reinterpret_cast<uint32_t*>(out + o_f);
-  int32_t* dst = reinterpret_cast<int32_t*>(out + o_s);
-  if (C) {
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dP, P, nd * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dC, C, nd * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dM, M, nd, hipMemcpyHostToDevice, ctx->stream));
-  }
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar, pm, nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar + nn, pp, nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(sa_dev_impl(ctx, C ? dC : nullptr, C ? dP : nullptr, C ? dM : nullptr, seed, stream, first, n, nrows, ncols, n_iter,
-                          obs_every, init, dpar, dpar + nn, dS, n_iter / obs_every + 1, status ? dst : nullptr,
-                          events ? dev : nullptr, frames ? dfr : nullptr));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(S, dS, ns * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (status) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(status, dst, nn * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (events) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(events, dev, 2 * nn * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (frames) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(frames, dfr, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const size_t nn = (size_t)n, nd = nn * (size_t)n_iter * 2 * (size_t)(nrows * ncols), ns = nn * (size_t)(n_iter / obs_every + 1);
+  double *dP, *dpm, *dpp, *dS;
+  int32_t *dC, *dst;
+  uint8_t* dM;
+  int64_t* dev;
+  uint32_t* dfr;
+  HostStage st(ctx);
+  st.in(&dP, P, nd);
+  st.in(&dC, C, nd);
+  st.in(&dM, M, nd);
+  st.in(&dpm, pm, nn);
+  st.in(&dpp, pp, nn);
+  st.out(&dS, S, ns);
+  st.out(&dst, status, nn);
+  st.out(&dev, events, 2 * nn);
+  st.out(&dfr, frames, ns * SA_WORDS);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(sa_dev_impl(ctx, dC, dP, dM, seed, stream, first, n, nrows, ncols, n_iter, obs_every, init, dpm, dpp, dS,
+                          n_iter / obs_every + 1, dst, dev, dfr));
+  return st.download();
 }
 
 int elfihip_assay_draws_dev(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t first, int64_t n, int n_iter, int cells,
@@ -368,20 +358,17 @@ int elfihip_assay_draws(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_
   for (size_t r = 0; r < rows; ++r)
     ELFIHIP_REQUIRE(ctx, num_cells[r] >= 0 && num_cells[r] <= cells, "num_cells[%lld] = %d: 0 to %d", (long long)r, num_cells[r], cells);
   DeviceGuard g(ctx->device);
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(rows * sizeof(int32_t)));
-  const size_t o_c = align256(nd * sizeof(double)), o_m = o_c + align256(nd * sizeof(int32_t));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(o_m + nd));
-  char* out = ctx->out.as<char>();
-  double* dP = ctx->out.as<double>();
-  int32_t* dC = reinterpret_cast<int32_t*>(out + o_c);
-  uint8_t* dM = reinterpret_cast<uint8_t*>(out + o_m);
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(ctx->in.p, num_cells, rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(sa_draws_impl(ctx, seed, stream, first, n, n_iter, cells, ctx->in.as<int32_t>(), dC, dP, dM));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(C, dC, nd * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(P, dP, nd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(M, dM, nd, hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  double* dP;
+  int32_t *dnum, *dC;
+  uint8_t* dM;
+  HostStage st(ctx);
+  st.in(&dnum, num_cells, rows);
+  st.out(&dC, C, nd);
+  st.out(&dP, P, nd);
+  st.out(&dM, M, nd);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(sa_draws_impl(ctx, seed, stream, first, n, n_iter, cells, dnum, dC, dP, dM));
+  return st.download();
 }
 
 }  // extern "C"

@@ -42,6 +42,7 @@
 
 #include "dist_launch.hpp"
 #include "dist_metrics.hpp"
+#include "host_stage.hpp"
 #include "lane_sort.hpp"
 #include "np_sum.hpp"
 #include "philox.hpp"
@@ -724,25 +725,18 @@ int elfihip_arch_summaries(elfihip_ctx* ctx, const double* W, uint64_t seed, uin
   if (n == 0) return ELFIHIP_OK;
   DeviceGuard g(ctx->device);
   const int L = n_obs + 2, m = 2 + n_lags + n_lags * (n_lags - 1) / 2;
-  const size_t nw = W ? (size_t)n * L : 0, ny = Y ? (size_t)n * n_obs : 0, ns = (size_t)n * m;
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((nw + 2 * (size_t)n) * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((ns + (size_t)n + ny) * sizeof(double)));
-  double* dW = ctx->in.as<double>();
-  double* dt1 = dW + nw;
-  double* dt2 = dt1 + n;
-  double* dS = ctx->out.as<double>();
-  double* dD = dS + ns;
-  double* dY = dD + n;
-  if (W) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dW, W, nw * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt1, t1, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt2, t2, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(arch_dev_impl(ctx, W ? dW : nullptr, L, seed, stream, n, n_obs, n_lags, dt1, dt2, obs, dS, m, Y ? dY : nullptr,
-                            n_obs, D ? dD : nullptr));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(S, dS, ns * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (Y) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Y, dY, ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const size_t nn = (size_t)n;
+  double *dW, *dt1, *dt2, *dS, *dD, *dY;
+  HostStage st(ctx);
+  st.in(&dW, W, nn * L);
+  st.in(&dt1, t1, nn);
+  st.in(&dt2, t2, nn);
+  st.out(&dS, S, nn * m);
+  st.out(&dD, D, nn);
+  st.out(&dY, Y, nn * n_obs);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(arch_dev_impl(ctx, dW, L, seed, stream, n, n_obs, n_lags, dt1, dt2, obs, dS, m, dY, n_obs, dD));
+  return st.download();
 }
 
 int elfihip_ar1_series_dev(elfihip_ctx* ctx, const double* dW, int64_t ldw, uint64_t seed, uint64_t stream, int64_t n,
@@ -761,20 +755,16 @@ int elfihip_ar1_series(elfihip_ctx* ctx, const double* W, uint64_t seed, uint64_
   if (n == 0) return ELFIHIP_OK;
   DeviceGuard g(ctx->device);
   const int L = n_obs + 1;
-  const size_t nw = W ? (size_t)n * L : 0, nx = X ? (size_t)n * n_obs : 0;
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((nw + (size_t)n) * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(((size_t)n + nx) * sizeof(double)));
-  double* dW = ctx->in.as<double>();
-  double* dphi = dW + nw;
-  double* dD = ctx->out.as<double>();
-  double* dX = dD + n;
-  if (W) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dW, W, nw * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dphi, phi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(ar1_dev_impl(ctx, W ? dW : nullptr, L, seed, stream, n, n_obs, dphi, obs, X ? dX : nullptr, n_obs, D ? dD : nullptr));
-  if (X) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(X, dX, nx * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const size_t nn = (size_t)n;
+  double *dW, *dphi, *dX, *dD;
+  HostStage st(ctx);
+  st.in(&dW, W, nn * L);
+  st.in(&dphi, phi, nn);
+  st.out(&dX, X, nn * n_obs);
+  st.out(&dD, D, nn);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(ar1_dev_impl(ctx, dW, L, seed, stream, n, n_obs, dphi, obs, dX, n_obs, dD));
+  return st.download();
 }
 
 int elfihip_mg1_summaries_dev(elfihip_ctx* ctx, const double* dE, int64_t lde, const double* dV, int64_t ldv, uint64_t seed,
@@ -800,38 +790,24 @@ int elfihip_mg1_summaries(elfihip_ctx* ctx, const double* E, const double* V, ui
   ELFIHIP_REQUIRE(ctx, !D || obs, "a distance needs the observed quantiles");
   if (n == 0) return ELFIHIP_OK;
   DeviceGuard g(ctx->device);
-  const size_t nn = (size_t)n * n_obs, nd = E ? nn : 0, nqn = (size_t)n * nq;
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((2 * nd + 3 * (size_t)n) * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((nn + nqn + (size_t)n + (Y ? nn : 0) + (Eo ? nn : 0) + (Vo ? nn : 0)) * sizeof(double)));
-  double* dE = ctx->in.as<double>();
-  double* dV = dE + nd;
-  double* dt1 = dV + nd;
-  double* dt2 = dt1 + n;
-  double* dt3 = dt2 + n;
-  double* dL = ctx->out.as<double>();
-  double* dQ = dL + nn;
-  double* dD = dQ + nqn;
-  double* dY = dD + n;
-  double* dEo = dY + (Y ? nn : 0);
-  double* dVo = dEo + (Eo ? nn : 0);
-  if (E) {
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dE, E, nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dV, V, nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  }
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt1, t1, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt2, t2, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt3, t3, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(mg1_dev_impl(ctx, E ? dE : nullptr, n_obs, E ? dV : nullptr, n_obs, seed, stream, n, n_obs, dt1, dt2, dt3, nq, lo,
-                           hi, t, obs, w, dL, n_obs, dQ, nq, Y ? dY : nullptr, n_obs, Eo ? dEo : nullptr, n_obs,
-                           Vo ? dVo : nullptr, n_obs, D ? dD : nullptr));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(logY, dL, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Q, dQ, nqn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (Y) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Y, dY, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (Eo) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Eo, dEo, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (Vo) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Vo, dVo, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const size_t nn = (size_t)n, ns = nn * n_obs;
+  double *dE, *dV, *dt1, *dt2, *dt3, *dL, *dQ, *dD, *dY, *dEo, *dVo;
+  HostStage st(ctx);
+  st.in(&dE, E, ns);
+  st.in(&dV, V, ns);
+  st.in(&dt1, t1, nn);
+  st.in(&dt2, t2, nn);
+  st.in(&dt3, t3, nn);
+  st.out(&dL, logY, ns);
+  st.out(&dQ, Q, nn * nq);
+  st.out(&dD, D, nn);
+  st.out(&dY, Y, ns);
+  st.out(&dEo, Eo, ns);
+  st.out(&dVo, Vo, ns);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(mg1_dev_impl(ctx, dE, n_obs, dV, n_obs, seed, stream, n, n_obs, dt1, dt2, dt3, nq, lo, hi, t, obs, w, dL, n_obs, dQ, nq,
+                           dY, n_obs, dEo, n_obs, dVo, n_obs, dD));
+  return st.download();
 }
 
 int elfihip_ricker_summaries_dev(elfihip_ctx* ctx, const double* dZ, int64_t ldz, uint64_t seed, uint64_t stream, int64_t n,
@@ -854,35 +830,22 @@ int elfihip_ricker_summaries(elfihip_ctx* ctx, const double* Z, uint64_t seed, u
   ELFIHIP_REQUIRE(ctx, log_rate && S, "NULL data pointer");
   ELFIHIP_REQUIRE(ctx, !D || obs, "a distance needs the observed summaries");
   DeviceGuard g(ctx->device);
-  const size_t nn = (size_t)n * n_obs, nz = Z ? nn : 0, np_ = sd ? 3 * (size_t)n : (size_t)n;
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve((nz + np_) * sizeof(double)));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve((4 * (size_t)n + (Y ? nn : 0) + (St ? nn : 0) + (Zo ? nn : 0)) * sizeof(double)));
-  double* dZ = ctx->in.as<double>();
-  double* dt1 = dZ + nz;
-  double* dt2 = dt1 + n;
-  double* dt3 = dt2 + n;
-  double* dS = ctx->out.as<double>();
-  double* dD = dS + 3 * (size_t)n;
-  double* dY = dD + n;
-  double* dSt = dY + (Y ? nn : 0);
-  double* dZo = dSt + (St ? nn : 0);
-  const size_t pb = (size_t)n * sizeof(double);
-  if (Z) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dZ, Z, nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt1, log_rate, pb, hipMemcpyHostToDevice, ctx->stream));
-  if (sd) {
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt2, sd, pb, hipMemcpyHostToDevice, ctx->stream));
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dt3, scale, pb, hipMemcpyHostToDevice, ctx->stream));
-  }
-  ELFIHIP_TRY(ricker_dev_impl(ctx, Z ? dZ : nullptr, n_obs, seed, stream, n, n_obs, dt1, sd ? dt2 : nullptr, sd ? dt3 : nullptr,
-                              stock_init, obs, which, dS, 3, Y ? dY : nullptr, n_obs, St ? dSt : nullptr, n_obs,
-                              Zo ? dZo : nullptr, n_obs, D ? dD : nullptr));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(S, dS, 3 * pb, hipMemcpyDeviceToHost, ctx->stream));
-  if (D) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(D, dD, pb, hipMemcpyDeviceToHost, ctx->stream));
-  if (Y) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Y, dY, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (St) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(St, dSt, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (Zo) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Zo, dZo, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const size_t nn = (size_t)n, ns = nn * n_obs;
+  double *dZ, *dt1, *dt2, *dt3, *dS, *dD, *dY, *dSt, *dZo;
+  HostStage st(ctx);
+  st.in(&dZ, Z, ns);
+  st.in(&dt1, log_rate, nn);
+  st.in(&dt2, sd, nn);
+  st.in(&dt3, scale, nn);
+  st.out(&dS, S, 3 * nn);
+  st.out(&dD, D, nn);
+  st.out(&dY, Y, ns);
+  st.out(&dSt, St, ns);
+  st.out(&dZo, Zo, ns);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(ricker_dev_impl(ctx, dZ, n_obs, seed, stream, n, n_obs, dt1, dt2, dt3, stock_init, obs, which, dS, 3, dY, n_obs, dSt,
+                              n_obs, dZo, n_obs, dD));
+  return st.download();
 }
 
 }  // extern "C"

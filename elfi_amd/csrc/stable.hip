@@ -4,6 +4,7 @@
 
 #include <algorithm>
 
+#include "host_stage.hpp"
 #include "stable.hpp"
 
 #pragma clang fp contract(off)
@@ -43,19 +44,14 @@ int elfihip_stable(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int64_t n, 
   ELFIHIP_REQUIRE(ctx, (angle == nullptr) == (expo == nullptr), "angles and exponentials are given together or not at all");
   if (n == 0) return ELFIHIP_OK;
   DeviceGuard g(ctx->device);
-  const size_t bytes = (size_t)n * sizeof(double);
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(4 * bytes));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(bytes));
-  double* din = ctx->in.as<double>();
-  double* dout = ctx->out.as<double>();
-  const double* src[4] = {alpha, scale, angle, expo};
-  for (int k = 0; k < (angle ? 4 : 2); ++k)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(din + (size_t)k * n, src[k], bytes, hipMemcpyHostToDevice, ctx->stream));
-  ELFIHIP_TRY(elfihip_stable_dev(ctx, seed, stream, n, din, din + n, angle ? din + 2 * (size_t)n : nullptr,
-                                 angle ? din + 3 * (size_t)n : nullptr, dout));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const double* src[4] = {alpha, scale, angle, expo};   // angle and expo may be NULL: drawn in the kernel
+  double *din[4], *dout;
+  HostStage st(ctx);
+  for (int k = 0; k < 4; ++k) st.in(&din[k], src[k], (size_t)n);
+  st.out(&dout, out, (size_t)n);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(elfihip_stable_dev(ctx, seed, stream, n, din[0], din[1], din[2], din[3], dout));
+  return st.download();
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 
+#include "host_stage.hpp"
 #include "stable.hpp"
 
 #pragma clang fp contract(off)
@@ -63,20 +64,14 @@ int elfihip_stable_general(elfihip_ctx* ctx, uint64_t seed, uint64_t stream, int
   ELFIHIP_TRY(stable_general_check(ctx, n, s0, alpha, beta, loc, scale, angle, expo, out));
   if (n == 0) return ELFIHIP_OK;
   DeviceGuard g(ctx->device);
-  const size_t bytes = (size_t)n * sizeof(double);
-  ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(6 * bytes));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(bytes));
-  double* din = ctx->in.as<double>();
-  double* dout = ctx->out.as<double>();
-  const double* src[6] = {alpha, beta, loc, scale, angle, expo};
-  for (int k = 0; k < (angle ? 6 : 4); ++k)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(din + (size_t)k * n, src[k], bytes, hipMemcpyHostToDevice, ctx->stream));
-  const size_t N = (size_t)n;
-  ELFIHIP_TRY(elfihip_stable_general_dev(ctx, seed, stream, n, s0, din, din + N, din + 2 * N, din + 3 * N,
-                                         angle ? din + 4 * N : nullptr, angle ? din + 5 * N : nullptr, dout));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const double* src[6] = {alpha, beta, loc, scale, angle, expo};   // angle and expo may be NULL: drawn in the kernel
+  double *din[6], *dout;
+  HostStage st(ctx);
+  for (int k = 0; k < 6; ++k) st.in(&din[k], src[k], (size_t)n);
+  st.out(&dout, out, (size_t)n);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(elfihip_stable_general_dev(ctx, seed, stream, n, s0, din[0], din[1], din[2], din[3], din[4], din[5], dout));
+  return st.download();
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@
 
 #include <algorithm>
 
+#include "host_stage.hpp"
 #include "stable.hpp"
 #include "wg_sort.hpp"
 
@@ -258,40 +259,22 @@ int elfihip_sv_summaries(elfihip_ctx* ctx, const double* Z, const double* TH, co
   ELFIHIP_REQUIRE(ctx, !echo || (Zo && THo && Wo), "the three draw outputs are asked for together");
   ELFIHIP_REQUIRE(ctx, alpha && beta && kappa && eta && mu && phi && sigma && S, "parameters and summaries are needed");
   DeviceGuard g(ctx->device);
-  const size_t N = (size_t)n, cells = (size_t)n_obs, d8 = sizeof(double);
-  // staging: parameters | given draws | outputs
-  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve(8 * N * d8));
-  double* dpar = ctx->par.as<double>();
-  const double* hp[8] = {alpha, beta, kappa, eta, mu, phi, sigma, x0};
-  for (int k = 0; k < (x0 ? 8 : 7); ++k)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar + k * N, hp[k], N * d8, hipMemcpyHostToDevice, ctx->stream));
-  double* dd[3] = {nullptr, nullptr, nullptr};
-  if (given) {
-    ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(3 * N * cells * d8));
-    const double* hd[3] = {Z, TH, W};
-    for (int k = 0; k < 3; ++k) {
-      dd[k] = ctx->in.as<double>() + k * N * cells;
-      ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dd[k], hd[k], N * cells * d8, hipMemcpyHostToDevice, ctx->stream));
-    }
-  }
-  double* ho[7] = {S, Y, X, V, Zo, THo, Wo};
-  double* dop[7];
-  size_t width[7] = {2, cells, cells, cells, cells, cells, cells}, total = 0;
-  for (int k = 0; k < 7; ++k) total += ho[k] ? N * width[k] : 0;
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(total * d8));
-  double* o = ctx->out.as<double>();
-  for (int k = 0; k < 7; ++k) {
-    dop[k] = ho[k] ? o : nullptr;
-    o += ho[k] ? N * width[k] : 0;
-  }
-  ELFIHIP_TRY(elfihip_sv_summaries_dev(ctx, dd[0], dd[1], dd[2], (int64_t)cells, seed, stream, first_index, n, n_obs, q, dpar,
-                                       dpar + N, dpar + 2 * N, dpar + 3 * N, dpar + 4 * N, dpar + 5 * N, dpar + 6 * N,
-                                       x0 ? dpar + 7 * N : nullptr, dop[0], 2, dop[1], (int64_t)cells, dop[2], (int64_t)cells,
-                                       dop[3], (int64_t)cells, dop[4], dop[5], dop[6], (int64_t)cells));
-  for (int k = 0; k < 7; ++k)
-    if (ho[k]) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(ho[k], dop[k], N * width[k] * d8, hipMemcpyDeviceToHost, ctx->stream));
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+  const size_t N = (size_t)n, cells = (size_t)n_obs;
+  const double* hpar[8] = {alpha, beta, kappa, eta, mu, phi, sigma, x0};   // x0 may be NULL: the stationary start
+  const double* hdraw[3] = {Z, TH, W};
+  double* hout[6] = {Y, X, V, Zo, THo, Wo};
+  double *dpar[8], *ddraw[3], *dS, *dout[6];
+  HostStage st(ctx);
+  for (int k = 0; k < 8; ++k) st.in(&dpar[k], hpar[k], N);
+  for (int k = 0; k < 3; ++k) st.in(&ddraw[k], hdraw[k], N * cells);
+  st.out(&dS, S, N * 2);
+  for (int k = 0; k < 6; ++k) st.out(&dout[k], hout[k], N * cells);
+  ELFIHIP_TRY(st.upload());
+  ELFIHIP_TRY(elfihip_sv_summaries_dev(ctx, ddraw[0], ddraw[1], ddraw[2], (int64_t)cells, seed, stream, first_index, n, n_obs, q,
+                                       dpar[0], dpar[1], dpar[2], dpar[3], dpar[4], dpar[5], dpar[6], dpar[7], dS, 2, dout[0],
+                                       (int64_t)cells, dout[1], (int64_t)cells, dout[2], (int64_t)cells, dout[3], dout[4], dout[5],
+                                       (int64_t)cells));
+  return st.download();
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 
 #include <algorithm>
 
+#include "host_stage.hpp"
 #include "stable.hpp"
 #include "wg_sort.hpp"
 
@@ -303,55 +304,29 @@ int elfihip_toad_summaries(elfihip_ctx* ctx, const double* U, const double* TH, 
   ELFIHIP_REQUIRE(ctx, alpha && gamma && p0 && S, "parameters and summaries are needed");
   DeviceGuard g(ctx->device);
   const size_t cells = (size_t)(n_days - 1) * n_toads, grid_cells = (size_t)n_days * n_toads, ns = (size_t)(nq + 1) * n_lags;
-  const size_t N = (size_t)n, d8 = sizeof(double);
-  // staging: parameters | given draws (three double arrays and the int32 one) | outputs
-  ELFIHIP_CHECK_HIP(ctx, ctx->par.reserve(3 * N * d8));
-  double* dpar = ctx->par.as<double>();
-  const double* hp[3] = {alpha, gamma, p0};
-  for (int k = 0; k < 3; ++k)
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dpar + k * N, hp[k], N * d8, hipMemcpyHostToDevice, ctx->stream));
-  double *dU = nullptr, *dTH = nullptr, *dW = nullptr;
-  int32_t* dR = nullptr;
-  if (given) {
-    ELFIHIP_CHECK_HIP(ctx, ctx->in.reserve(N * cells * (3 * d8 + sizeof(int32_t))));
-    dU = ctx->in.as<double>(), dTH = dU + N * cells, dW = dTH + N * cells;
-    dR = reinterpret_cast<int32_t*>(dW + N * cells);
-    const double* hd[3] = {U, TH, W};
-    double* dd[3] = {dU, dTH, dW};
-    for (int k = 0; k < 3; ++k)
-      ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dd[k], hd[k], N * cells * d8, hipMemcpyHostToDevice, ctx->stream));
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(dR, R, N * cells * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  }
-  const size_t out_doubles = N * (ns + (X ? grid_cells : 0) + (Dx ? cells : 0) + (echo ? 3 * cells : 0));
-  ELFIHIP_CHECK_HIP(ctx, ctx->out.reserve(out_doubles * d8 + (echo ? N * cells * sizeof(int32_t) : 0)));
-  double* o = ctx->out.as<double>();
-  double* dS = o;
-  o += N * ns;
-  double* dX = X ? o : nullptr;
-  o += X ? N * grid_cells : 0;
-  double* dDx = Dx ? o : nullptr;
-  o += Dx ? N * cells : 0;
-  double *dUo = nullptr, *dTHo = nullptr, *dWo = nullptr;
-  int32_t* dRo = nullptr;
-  if (echo) {
-    dUo = o, dTHo = o + N * cells, dWo = o + 2 * N * cells;
-    dRo = reinterpret_cast<int32_t*>(o + 3 * N * cells);
-  }
+  const size_t N = (size_t)n;
+  double *dalpha, *dgamma, *dp0, *dU, *dTH, *dW, *dS, *dX, *dDx, *dUo, *dTHo, *dWo;
+  int32_t *dR, *dRo;
+  HostStage st(ctx);
+  st.in(&dalpha, alpha, N);
+  st.in(&dgamma, gamma, N);
+  st.in(&dp0, p0, N);
+  st.in(&dU, U, N * cells);
+  st.in(&dTH, TH, N * cells);
+  st.in(&dW, W, N * cells);
+  st.in(&dR, R, N * cells);
+  st.out(&dS, S, N * ns);
+  st.out(&dX, X, N * grid_cells);
+  st.out(&dDx, Dx, N * cells);
+  st.out(&dUo, Uo, N * cells);
+  st.out(&dTHo, THo, N * cells);
+  st.out(&dWo, Wo, N * cells);
+  st.out(&dRo, Ro, N * cells);
+  ELFIHIP_TRY(st.upload());
   ELFIHIP_TRY(elfihip_toad_summaries_dev(ctx, dU, dTH, dW, dR, (int64_t)cells, seed, stream, first_index, n, n_toads, n_days,
-                                         n_lags, lags, nq, p, thd, dpar, dpar + N, dpar + 2 * N, dS, (int64_t)ns, dX,
-                                         (int64_t)grid_cells, dDx, (int64_t)cells, dUo, dTHo, dWo, dRo, (int64_t)cells));
-  ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(S, dS, N * ns * d8, hipMemcpyDeviceToHost, ctx->stream));
-  if (X) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(X, dX, N * grid_cells * d8, hipMemcpyDeviceToHost, ctx->stream));
-  if (Dx) ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Dx, dDx, N * cells * d8, hipMemcpyDeviceToHost, ctx->stream));
-  if (echo) {
-    double* ho[3] = {Uo, THo, Wo};
-    double* dd[3] = {dUo, dTHo, dWo};
-    for (int k = 0; k < 3; ++k)
-      ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(ho[k], dd[k], N * cells * d8, hipMemcpyDeviceToHost, ctx->stream));
-    ELFIHIP_CHECK_HIP(ctx, hipMemcpyAsync(Ro, dRo, N * cells * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  ELFIHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ELFIHIP_OK;
+                                         n_lags, lags, nq, p, thd, dalpha, dgamma, dp0, dS, (int64_t)ns, dX, (int64_t)grid_cells,
+                                         dDx, (int64_t)cells, dUo, dTHo, dWo, dRo, (int64_t)cells));
+  return st.download();
 }
 
 }  // extern "C"
