@@ -84,7 +84,8 @@ struct elfihip_ctx {
   // (SelWork::err in `scratch`, topk_resident_err_dev), which the selection's caller reads in stream order before any other
   // user of `scratch` is enqueued.
   //   scratch  topk.hip (SelWork / SelState: histograms, the barrier counter, the flag), welford.hip, wstats.hip, gmix.hip,
-  //            synlik.hip, semibsl.hip, wsemibsl.hip, kliep.hip
+  //            synlik.hip, semibsl.hip, wsemibsl.hip, kliep.hip, synlik_wide.hip (whitened rows, moment snapshots,
+  //            factor slabs: at most its cap per call)
   //   sel      twostage.hip: a block of subset distances and its survivors; the partial sums of the entropy
   //            adjust.hip: the tile factors, the tile sums, the jobs' means and coefficients
   //            glasso.hip: the group moments between synlik.hip's launch (which borrows `scratch`) and the solver's, the penalties
@@ -110,6 +111,7 @@ struct elfihip_ctx {
   uint64_t rows_epoch = 0;
   int64_t rows_n = 0;
   int rows_m = 0;
+  size_t wide_cap = 0;   // bytes of `scratch` a wide synthetic-likelihood call may hold; 0: its default (elfihip_syn_wide_set_cap)
 };
 
 namespace elfihip {

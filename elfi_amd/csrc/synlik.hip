@@ -20,12 +20,13 @@
 //   finish     at every boundary, in LDS: covariance, then per penalty the shrunk / adjusted matrix, its Cholesky factor
 //              with the residual y - mean as an extra row (the forward solve rides along), the log-determinant and the
 //              quadratic form.  A non-positive pivot or a non-finite value gives -inf.
-// Whitening (rows -> rows W^T, y -> W y) is a launch of its own in front.
+// Whitening (rows -> rows W^T, y -> W y) is a launch of its own in front (syn_gauss.hpp).
 // Determinism: no atomics, fixed order everywhere; a group's result does not depend on G.
 // The shape of the LDS buffers, the MFMA step and the factorisation are shared with semibsl.hip and logratio.hip
 // (syn_gram.hpp); the check of the lists and their parameter block with semibsl.hip (group_args.hpp).
 #include "common.hpp"
 #include "syn_gram.hpp"
+#include "syn_gauss.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -57,27 +58,6 @@ struct SynShape : GramShape<T> {
   static constexpr int DOUBLES = SL_RC * SP + MP * LP + (MP + 1) * LP + 6 * MP;
   static_assert(DOUBLES * sizeof(double) <= 160 * 1024);
 };
-
-// rows -> rows W^T (sequential k), one output element per thread and step
-__global__ __launch_bounds__(256) void synlik_whiten_kernel(const double* X, int64_t rows, int m, int64_t ldx,
-                                                            const double* W, const double* y, double* Xw, double* yw) {
-  const int64_t total = rows * m;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = e / m;
-    const int j = (int)(e - r * m);
-    const double* x = X + r * ldx;
-    const double* w = W + (int64_t)j * m;
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s += x[k] * w[k];
-    Xw[e] = s;
-  }
-  if (blockIdx.x == 0 && (int)threadIdx.x < m) {
-    const double* w = W + (int64_t)threadIdx.x * m;
-    double s = 0.0;
-    for (int k = 0; k < m; ++k) s += w[k] * y[k];
-    yw[threadIdx.x] = s;
-  }
-}
 
 // The log-likelihoods of prefix kb (np rows) for every penalty; S holds S2, s1 holds S1 of the shifted rows.  All 256
 // threads; ends with a barrier.
@@ -236,17 +216,6 @@ __global__ __launch_bounds__(256) void synlik_kernel(SynArgs A) {
     for (int i = 0; i < NT; ++i) tot[i] += chk[i];
     s1tot += s1chk;
   }
-}
-
-// log c(d, n - 2) - log c(d, n - 1) - d/2 log(1 - 1/n) - d/2 log(2 pi) of Ghurye & Olkin's unbiased estimator
-// (pdf_methods.py:168-171, wcon :319-341); NaN where a gamma function's argument is not positive (n <= d + 1)
-static double unbiased_const(int d, int64_t n) {
-  if (n <= (int64_t)d + 1) return NAN;
-  long double a = 0.5L * d * logl(2.0L);
-  for (int x = 0; x < d; ++x) a -= lgammal(0.5L * (long double)(n - 2 - x)) - lgammal(0.5L * (long double)(n - 1 - x));
-  a -= 0.5L * d * logl(1.0L - 1.0L / (long double)n);
-  a -= 0.5L * d * logl(2.0L * 3.14159265358979323846264338327950288L);
-  return (double)a;
 }
 
 static int synlik_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, int m, int64_t ldx, const void* y,

@@ -33,6 +33,12 @@ Priddle et al. 2021; the whitening branch of pdf_methods.py:213-264) with the sa
 `whitened_semiparametric_likelihood(W)` is the `likelihood=` for BSL, select_penalty and log_SL_stdev.  The keyword
 whitening= of the semiparametric calls above is not routed there and raises.
 
+`wide_syn_loglik` mirrors `elfihip_syn_loglik_wide` (csrc/synlik_wide.hip): the Gaussian synthetic likelihood of
+MIN_WIDE_FEATURES = 65 to MAX_WIDE_FEATURES = 256 summaries (the scratch-assay example has 145), standard (Warton
+shrinkage or none, whitening) and unbiased, with the (G, K, P) call shape of `syn_loglik`;
+`wide_standard_likelihood(...)` / `wide_unbiased_likelihood()` are the `likelihood=` for BSL, select_penalty and
+log_SL_stdev.  Every other call here, the robust variants and slice_gamma included, takes at most MAX_FEATURES = 64.
+
 Not on the device: graphical-lasso shrinkage inside the semiparametric likelihoods, estimate_whitening_matrix
 (the reference's runs once before sampling, on the device models too; its W goes straight into the calls here).  They
 raise or stay the reference's; nothing falls back quietly.
@@ -48,6 +54,7 @@ from . import _lib
 from .priors import SLICE_GAMMA_STREAM_BASE
 
 MAX_FEATURES = 64
+MIN_WIDE_FEATURES, MAX_WIDE_FEATURES = 65, 256      # the wide Gaussian likelihood (csrc/synlik_wide.hip)
 MAX_SEMI_ROWS = 16384       # rows per group of the semiparametric likelihood: one column is held in LDS
 _VARIANTS = {'standard': 0, 'unbiased': 1, 'mean': 2, 'variance': 3}
 _CLASSES = {}
@@ -90,9 +97,9 @@ def _one_group(ssx):
     return np.asarray(ssx, dtype=np.float64).reshape(len(ssx), -1)
 
 
-def _groups(ssx, ssy, n_groups, max_rows=None):
+def _groups(ssx, ssy, n_groups, max_rows=None, width=(1, MAX_FEATURES), kernel='device'):
     """(X (n_groups n, m), y (m), n_groups, n, m, keep_group_axis) of the two layouts ssx may have; max_rows: the rows per
-    group the semiparametric kernels take."""
+    group the semiparametric kernels take; width: the summaries the `kernel` kernel takes."""
     X = np.asarray(ssx, dtype=np.float64)
     keep_group_axis = X.ndim == 3 or n_groups != 1
     if X.ndim == 3:
@@ -111,8 +118,8 @@ def _groups(ssx, ssy, n_groups, max_rows=None):
     n = rows // n_groups
     if n < 2:
         raise ValueError('a group needs at least 2 rows (n=%d)' % n)
-    if m < 1 or m > MAX_FEATURES:
-        raise ValueError('%d summaries: the device kernel takes 1 to %d' % (m, MAX_FEATURES))
+    if m < width[0] or m > width[1]:
+        raise ValueError('%d summaries: the %s kernel takes %d to %d' % (m, kernel, width[0], width[1]))
     y = np.ascontiguousarray(np.asarray(ssy, dtype=np.float64).reshape(-1))
     if y.shape != (m,):
         raise ValueError('ssy has %d entries, ssx has %d columns' % (y.size, m))
@@ -207,6 +214,23 @@ def syn_loglik(ssx, ssy, n_groups=1, variant='standard', shrinkage=None, penalty
                        (_lib.ptr(W), code, _lib.ptr(g)), [(G, m), (G, m, m)], return_moments, ctx)
 
 
+def wide_syn_loglik(ssx, ssy, n_groups=1, variant='standard', shrinkage=None, penalty=None, whitening=None, prefixes=None,
+                    penalties=None, return_moments=False, ctx=None):
+    """syn_loglik for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries (`elfihip_syn_loglik_wide`): variant 'standard'
+    (shrinkage None | 'warton', whitening) or 'unbiased'; the robust variants stop at MAX_FEATURES.  Layouts, lists, the
+    shape of the result and return_moments as syn_loglik; narrower input belongs to syn_loglik."""
+    groups = _groups(ssx, ssy, n_groups, width=(MIN_WIDE_FEATURES, MAX_WIDE_FEATURES), kernel='wide device')
+    G, m = groups[2], groups[4]
+    if variant not in ('standard', 'unbiased'):
+        raise ValueError("variant %r: above %d summaries the device has 'standard' and 'unbiased'" % (variant, MAX_FEATURES))
+    _check_shrinkage(shrinkage)
+    if shrinkage is not None and variant != 'standard':
+        raise ValueError('shrinkage goes with the standard likelihood only (the unbiased one has none)')
+    W = None if whitening is None else _whitening_matrix(whitening, m)
+    return _group_call("elfihip_syn_loglik_wide", groups, shrinkage, penalty, penalties, prefixes,
+                       (_lib.ptr(W), _VARIANTS[variant]), [(G, m), (G, m, m)], return_moments, ctx)
+
+
 def semi_loglik(ssx, ssy, n_groups=1, shrinkage=None, penalty=None, prefixes=None, penalties=None, return_parts=False,
                 ctx=None):
     """Semiparametric synthetic log-likelihoods (semiBSL: a kernel density estimate per summary, a Gaussian copula with
@@ -257,6 +281,16 @@ def gaussian_syn_likelihood_ghurye_olkin(ssx, ssy):
     return np.array([syn_loglik(_one_group(ssx), ssy, variant='unbiased')])
 
 
+def wide_gaussian_syn_likelihood(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
+    """gaussian_syn_likelihood for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries; np.array([ll])."""
+    return np.array([wide_syn_loglik(_one_group(ssx), ssy, shrinkage=shrinkage, penalty=penalty, whitening=whitening)])
+
+
+def wide_gaussian_syn_likelihood_ghurye_olkin(ssx, ssy):
+    """gaussian_syn_likelihood_ghurye_olkin for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries; np.array([ll])."""
+    return np.array([wide_syn_loglik(_one_group(ssx), ssy, variant='unbiased')])
+
+
 def syn_likelihood_misspec(ssx, ssy, gamma, adjustment):
     """Mean- or variance-adjusted synthetic log-likelihood (Frazier & Drovandi); a scalar."""
     return syn_loglik(_one_group(ssx), ssy, gamma=gamma, adjustment=adjustment)
@@ -282,6 +316,18 @@ def standard_likelihood(shrinkage=None, penalty=None, whitening=None):
     """pdf_methods.standard_likelihood on the device (Warton shrinkage or none)."""
     _check_shrinkage(shrinkage)
     return partial(gaussian_syn_likelihood, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
+
+
+def wide_standard_likelihood(shrinkage=None, penalty=None, whitening=None):
+    """standard_likelihood for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries: a `likelihood=` for elfi.BSL, HipBSL,
+    select_penalty and log_SL_stdev."""
+    _check_shrinkage(shrinkage)
+    return partial(wide_gaussian_syn_likelihood, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
+
+
+def wide_unbiased_likelihood():
+    """unbiased_likelihood for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries."""
+    return wide_gaussian_syn_likelihood_ghurye_olkin
 
 
 def semiparametric_likelihood(shrinkage=None, penalty=None, whitening=None):
@@ -314,15 +360,15 @@ def robust_likelihood(adjustment):
 
 
 def _likelihood_setup(likelihood, **override):
-    """(batched call, its keywords) of one of the callables above (None: the standard one): syn_loglik, semi_loglik or
-    wsemi_loglik, which is called as batched(groups, observed, **keywords)."""
+    """(batched call, its keywords) of one of the callables above (None: the standard one): syn_loglik, wide_syn_loglik,
+    semi_loglik or wsemi_loglik, which is called as batched(groups, observed, **keywords)."""
     kw = {}
     fn = likelihood
     if isinstance(likelihood, partial):
         fn, kw = likelihood.func, dict(likelihood.keywords)
-    if fn is None or fn is gaussian_syn_likelihood:
+    if fn is None or fn is gaussian_syn_likelihood or fn is wide_gaussian_syn_likelihood:
         kw.update(override)
-        return syn_loglik, dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw.get('whitening'))
+        return wide_syn_loglik if fn is wide_gaussian_syn_likelihood else syn_loglik, dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw.get('whitening'))
     if fn is semi_param_kernel_estimate:
         kw.update(override)
         if kw.get('whitening') is not None:
@@ -335,6 +381,8 @@ def _likelihood_setup(likelihood, **override):
         return wsemi_loglik, dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw['whitening'])
     if fn is gaussian_syn_likelihood_ghurye_olkin and not override:
         return syn_loglik, dict(variant='unbiased')
+    if fn is wide_gaussian_syn_likelihood_ghurye_olkin and not override:
+        return wide_syn_loglik, dict(variant='unbiased')
     raise TypeError('the batched evaluation takes the device likelihoods of elfi_amd (standard_likelihood(...), '
                     'semiparametric_likelihood(...), whitened_semiparametric_likelihood(...), unbiased_likelihood()); '
                     'got %r' % (likelihood,))

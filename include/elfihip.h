@@ -352,6 +352,21 @@ int elfihip_syn_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_
                            const double* dW, int variant, const double* dgamma_adj, const int64_t* prefixes, int K,
                            const double* penalties, int P, double* dloglik, double* dmean, double* dcov);
 
+/* The wide form: 65 <= m <= 256 summaries (ELFI's scratch-assay example has 145), variants 0 and 1 only -- the adjusted
+ * variants, and every other likelihood here, stop at 64.  Arguments, outputs, -inf rule and determinism as
+ * elfihip_syn_loglik without gamma_adj; a narrower m is ELFIHIP_ERR_ARG and belongs to elfihip_syn_loglik.  Two kernels
+ * (csrc/synlik_wide.hip): the moments in 64 x 64 blocks, then one workgroup per (group, prefix, penalty) that factors its
+ * matrix on a slab of the context's work space.  The host cuts the call into launches so that the work space stays under a
+ * cap (256 MiB; one group's rows and snapshots and one slab are the least); a result does not depend on the cut, on G, K
+ * or P.  elfihip_syn_wide_set_cap sets the cap of a context in bytes (0: the default) -- for tests of that statement. */
+int elfihip_syn_loglik_wide(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, int m, int64_t ldx, const double* y,
+                            const double* W, int variant, const int64_t* prefixes, int K, const double* penalties, int P,
+                            double* loglik, double* mean, double* cov);
+int elfihip_syn_loglik_wide_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx,
+                                const double* dy, const double* dW, int variant, const int64_t* prefixes, int K,
+                                const double* penalties, int P, double* dloglik, double* dmean, double* dcov);
+int elfihip_syn_wide_set_cap(elfihip_ctx* ctx, int64_t bytes);
+
 /* Graphical-lasso shrinkage (BSLasso, An et al. 2019; sklearn.covariance.graphical_lasso as pdf_methods.py:113-120 calls
  * it): B symmetric positive semi-definite matrices S (m x m, rows at pitch lds >= m, 1 <= m <= 64; S is taken as symmetric:
  * row j is read for column j) x P penalties alphas (host array, >= 0) in one launch, one wavefront per problem.  Problem
