@@ -1,4 +1,5 @@
-// What the two semiparametric likelihoods share (semibsl.hip: semiBSL; wsemibsl.hip: the whitened form): the arguments
+// What the semiparametric likelihoods share (semibsl.hip: semiBSL; wsemibsl.hip: the whitened form; semibsl_wide.hip:
+// semiBSL above 64 summaries, which takes the column kernel, the row bound and the device helpers): the arguments
 // and the launch of the column kernel, the entry points' first checks and the set-up before the launches, the workgroup
 // reductions, and the rank of a value within a column held in LDS.
 #pragma once
@@ -32,6 +33,19 @@ struct SemiArgs {
 
 // The column kernel of semibsl.hip over GK * m workgroups on the context's stream: Q, stats and, if asked for, u and scores.
 int semibsl_launch_column(elfihip_ctx* ctx, const SemiArgs& A, int64_t GK);
+
+// The wide layout of the column kernel (semibsl_wide.hip: 65 to 256 summaries).  A launch holds the (group, prefix) jobs
+// job0 .. job0 + jobs - 1 of the call, job = g K + k; Q and stats are the launch's own and counted from its first job.
+//   Q      (jobs, m, NP) column-major: the scores of one column are consecutive, NP = n rounded up to a multiple of 32
+//   stats  (jobs, SEMI_WIDE_STATS): eta at 0, logpdf at SEMI_WIDE_M, the denominator at 2 SEMI_WIDE_M
+// MP is not used.  u and scores stay (G, m) and (G, n, m) of the whole call.
+constexpr int SEMI_WIDE_M = 256;
+constexpr int SEMI_WIDE_STATS = 2 * SEMI_WIDE_M + 8;
+struct SemiWideArgs : SemiArgs {
+  int64_t job0;
+  int NP;
+};
+int semibsl_launch_column_wide(elfihip_ctx* ctx, const SemiWideArgs& A, int64_t jobs);
 
 // The checks both likelihoods' entry points begin with; `what` names the likelihood in the texts.  Each goes on with its own
 // bound on the number of workgroups and the check of the lists.

@@ -31,18 +31,26 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
 namespace elfihip {
 
-__global__ __launch_bounds__(256) void semibsl_column_kernel(SemiArgs A) {
+// Args picks the layout of what the kernel leaves for the next one: SemiArgs the row-major scores at pitch MP and
+// SEMI_STATS statistics of this file and wsemibsl.hip, SemiWideArgs (semi_rank.hpp) the column-major scores and the wider
+// statistics of semibsl_wide.hip, where a launch holds a part of the call's jobs.
+template <class Args>
+__global__ __launch_bounds__(256) void semibsl_column_kernel(Args A) {
+  constexpr bool WIDE = std::is_same<Args, SemiWideArgs>::value;
   extern __shared__ __align__(16) double lds[];
   double* red = lds;              // (SEMI_RED)
   double* col = lds + SEMI_RED;   // the column, NaN up to a multiple of 4 (a NaN counts in no comparison)
   const int tid = threadIdx.x, m = A.m;
   const int j = (int)(blockIdx.x % (unsigned)m);
-  const int64_t gk = blockIdx.x / (unsigned)m;
+  const int64_t lj = blockIdx.x / (unsigned)m;   // the job within the launch
+  int64_t gk = lj;
+  if constexpr (WIDE) gk += A.job0;
   const int k = (int)(gk % A.K);
   const int64_t g = gk / A.K;
   const int p = (int)A.prefixes[k];
@@ -82,23 +90,31 @@ __global__ __launch_bounds__(256) void semibsl_column_kernel(SemiArgs A) {
   }
   se = block_sum(se, red);
   sc = block_sum(sc, red);
-  double* st = A.stats + gk * SEMI_STATS;
+  double* st = A.stats + lj * (WIDE ? SEMI_WIDE_STATS : SEMI_STATS);
+  constexpr int LPV = WIDE ? SEMI_WIDE_M : SL_MAX_M;   // where logpdf begins; the denominator is at 2 LPV
   if (tid == 0) {
     double lp = mx + log(se) - log(dp) - log(h) - 0.91893853320467274178;
     if (!(h > 0.0 && h <= 1.7976931348623157e308)) lp = -INFINITY;   // no spread, or a value that is not finite
     const double u = fmin(1.0, sc / dp);
     st[j] = norm_ppf(u);
-    st[SL_MAX_M + j] = lp;
+    st[LPV + j] = lp;
     if (A.u && full) A.u[g * m + j] = u;
   }
 
   // ranks -> normal scores
   const double np1 = dp + 1.0;
-  double* Qg = A.Q + gk * A.n * A.MP + j;
+  double* Qg;
+  int64_t qp = 1;   // pitch of consecutive rows
+  if constexpr (WIDE) {
+    Qg = A.Q + (lj * m + j) * A.NP;
+  } else {
+    Qg = A.Q + gk * A.n * A.MP + j;
+    qp = A.MP;
+  }
   const double2* col2 = reinterpret_cast<const double2*>(col);
   for (int i = tid; i < p; i += 256) {
     const double q = rank_score(col2, pp, col[i], np1);
-    Qg[(int64_t)i * A.MP] = q;
+    Qg[(int64_t)i * qp] = q;
     if (A.scores && full) A.scores[(g * A.n + i) * m + j] = q;
   }
 
@@ -110,7 +126,7 @@ __global__ __launch_bounds__(256) void semibsl_column_kernel(SemiArgs A) {
       s += q * q;
     }
     s = block_sum(s, red);
-    if (tid == 0) st[2 * SL_MAX_M] = s;
+    if (tid == 0) st[2 * LPV] = s;
   }
 }
 
@@ -222,11 +238,20 @@ static int semibsl_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, 
   return ELFIHIP_OK;
 }
 
-int semibsl_launch_column(elfihip_ctx* ctx, const SemiArgs& A, int64_t GK) {
+template <class Args>
+static int launch_column(elfihip_ctx* ctx, const Args& A, int64_t jobs, const char* name) {
   const size_t bytes = (size_t)(SEMI_RED + ((A.n + 3) & ~(int64_t)3)) * sizeof(double);
-  ELFIHIP_TRY(set_lds(ctx, semibsl_column_kernel, bytes, 48 * 1024));
-  hipLaunchKernelGGL(semibsl_column_kernel, dim3((unsigned)(GK * A.m)), dim3(256), bytes, ctx->stream, A);
-  return launch_status(ctx, "semiparametric likelihood column kernel");
+  ELFIHIP_TRY(set_lds(ctx, semibsl_column_kernel<Args>, bytes, 48 * 1024));
+  hipLaunchKernelGGL(semibsl_column_kernel<Args>, dim3((unsigned)(jobs * A.m)), dim3(256), bytes, ctx->stream, A);
+  return launch_status(ctx, name);
+}
+
+int semibsl_launch_column(elfihip_ctx* ctx, const SemiArgs& A, int64_t GK) {
+  return launch_column(ctx, A, GK, "semiparametric likelihood column kernel");
+}
+
+int semibsl_launch_column_wide(elfihip_ctx* ctx, const SemiWideArgs& A, int64_t jobs) {
+  return launch_column(ctx, A, jobs, "wide semiparametric likelihood column kernel");
 }
 
 // Device rows, y and outputs; host prefixes and penalties (checked above).

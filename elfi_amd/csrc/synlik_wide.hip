@@ -13,7 +13,8 @@
 //             At a prefix boundary p the sums of the rows before p are written to the workspace; a boundary inside a
 //             4-row step goes through an extra, masked MFMA into a temporary, the running sums go on with the whole
 //             step, so prefix p of a long group has the bits of a group of p rows.
-//   finish    one workgroup of 256 threads per (group, prefix, penalty).  Left-looking blocked Cholesky factorisation on
+//   finish    one workgroup of 256 threads per (group, prefix, penalty).  Left-looking blocked Cholesky factorisation
+//             (wide_chol.hpp: wide_panel_chol, shared with semibsl_wide.hip) on
 //             the job's own slab of the workspace, the residual y - mean riding along as row m (its forward solve is the
 //             factorisation's update).  Per 32-column panel: the update sum_k L[i][k] L[j][k] over the panels already
 //             factored is accumulated by MFMA from the slab (each lane loads four consecutive k of one row, 32 bytes;
@@ -26,9 +27,8 @@
 //             log|S| and the quadratic form are summed by one thread in index order.
 // Whitening is the launch of syn_gauss.hpp in front.  No atomics, fixed order everywhere: one (group, prefix, penalty)
 // result depends neither on G, K, P nor on how the host cuts the launches into chunks to keep the workspace under its cap.
-#include "common.hpp"
-#include "mfma_f64.hpp"
 #include "syn_gauss.hpp"
+#include "wide_chol.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -37,21 +37,11 @@
 
 namespace elfihip {
 
-constexpr int SW_MIN_M = 65, SW_MAX_M = 256;
 constexpr int SW_RC = 32;              // rows per staged chunk (8 MFMA steps)
-constexpr int SW_BLK = 64;             // edge of a moments block
 constexpr int SW_SP = SW_BLK + 16;     // pitch of a staged slab
-constexpr int SW_PAN = 32;             // columns of a factorisation panel
-constexpr int SW_PP = SW_PAN + 1;      // pitch of the panel in LDS
-constexpr int SW_ROW_TILES = 5;        // 16-row tiles of a panel per wave: ceil(ceil(257 / 16) / 4)
-constexpr size_t SW_SCRATCH_CAP = (size_t)256 << 20;   // bytes of ctx->scratch one call may hold (half moments, half slabs)
 
-inline int wide_mpad(int m) { return (m + SW_BLK - 1) / SW_BLK * SW_BLK; }
-inline int wide_pitch(int m) { return (m + SW_PAN - 1) / SW_PAN * SW_PAN; }
 // doubles of one (group, prefix) snapshot: the padded S2 (lower blocks) and S1 behind it
 inline size_t wide_snap(int m) { return (size_t)wide_mpad(m) * wide_mpad(m) + wide_mpad(m); }
-// doubles of one job's slab: rows 0 .. m of the factor
-inline size_t wide_slab(int m) { return (size_t)(m + 1) * wide_pitch(m); }
 
 struct WideMomArgs {
   const double* X;          // (Gc n, m), pitch ldx: the groups of this launch
@@ -167,8 +157,7 @@ __global__ __launch_bounds__(256) void synlik_wide_finish_kernel(WideFinArgs A) 
   double* ws = rs + mpad;                  // Warton's diagonal scaling
   double* dg = ws + mpad;                  // diagonal of the factor
   double* z = dg + mpad;                   // the solved residual
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int lr = lane >> 4, lc = lane & 15;
+  const int tid = threadIdx.x;
   const int Pe = A.P > 0 ? A.P : 1;
   const int64_t job = A.job0 + blockIdx.x;
   const int pi = (int)(job % Pe);
@@ -216,74 +205,9 @@ __global__ __launch_bounds__(256) void synlik_wide_finish_kernel(WideFinArgs A) 
     return v;
   };
 
-  for (int c0 = 0; c0 < m; c0 += SW_PAN) {
-    const int nr = m + 1 - c0;                       // rows c0 .. m
-    const int nc = m - c0 < SW_PAN ? m - c0 : SW_PAN;
-    const int nrt = (nr + 15) / 16;
-    // update by the factored panels: acc[t][ct] = sum_{k < c0} L[c0 + 16 rt + .][k] L[c0 + 16 ct + .][k]; rows past m are
-    // read from row m and dropped.  A lane's four consecutive k feed four consecutive MFMAs (a permutation of k that both
-    // operands share).
-    v4d acc[SW_ROW_TILES][2];
-#pragma unroll
-    for (int t = 0; t < SW_ROW_TILES; ++t) acc[t][0] = acc[t][1] = (v4d){0.0, 0.0, 0.0, 0.0};
-    const int rb0 = c0 + lc < m ? c0 + lc : m, rb1 = c0 + 16 + lc < m ? c0 + 16 + lc : m;
-    for (int kk = 0; kk < c0; kk += 16) {
-      const double4 b0 = *reinterpret_cast<const double4*>(L + (size_t)rb0 * pw + kk + 4 * lr);
-      const double4 b1 = *reinterpret_cast<const double4*>(L + (size_t)rb1 * pw + kk + 4 * lr);
-#pragma unroll
-      for (int t = 0; t < SW_ROW_TILES; ++t) {
-        const int rt = wv + 4 * t;
-        if (rt < nrt) {
-          const int row = c0 + 16 * rt + lc < m ? c0 + 16 * rt + lc : m;
-          const double4 a = *reinterpret_cast<const double4*>(L + (size_t)row * pw + kk + 4 * lr);
-          acc[t][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b0.x, acc[t][0], 0, 0, 0);
-          acc[t][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b0.y, acc[t][0], 0, 0, 0);
-          acc[t][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.z, b0.z, acc[t][0], 0, 0, 0);
-          acc[t][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.w, b0.w, acc[t][0], 0, 0, 0);
-          acc[t][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b1.x, acc[t][1], 0, 0, 0);
-          acc[t][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b1.y, acc[t][1], 0, 0, 0);
-          acc[t][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.z, b1.z, acc[t][1], 0, 0, 0);
-          acc[t][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.w, b1.w, acc[t][1], 0, 0, 0);
-        }
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < SW_ROW_TILES; ++t) {
-      const int rt = wv + 4 * t;
-      if (rt < nrt) {
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int pr = 16 * rt + lr + 4 * r, c = 16 * ct + lc;
-            if (pr < nr) P[pr * SW_PP + c] = entry(c0 + pr, c0 + c) - acc[t][ct][r];
-          }
-      }
-    }
-    __syncthreads();
-    // the panel's own columns: right-looking inside the panel, in LDS
-    for (int j = 0; j < nc; ++j) {
-      const double piv = P[j * SW_PP + j];   // the same word for every thread: the branch is uniform
-      if (!(piv > 0.0)) {
-        if (tid == 0) *out = -INFINITY;
-        return;
-      }
-      const double d = sqrt(piv);            // (nobody writes P[j][j] from here on)
-      if (tid == 0) dg[c0 + j] = d;
-      for (int r = j + 1 + tid; r < nr; r += 256) P[r * SW_PP + j] = P[r * SW_PP + j] / d;
-      __syncthreads();
-      const int c = j + 1 + (tid & 31);
-      if (c < nc)
-        for (int r = c + (tid >> 5); r < nr; r += 8) P[r * SW_PP + c] -= P[r * SW_PP + j] * P[c * SW_PP + j];
-      __syncthreads();
-    }
-    for (int e = tid; e < nr * SW_PAN; e += 256) {
-      const int r = e / SW_PAN, c = e - r * SW_PAN;
-      const double v = P[r * SW_PP + c];
-      L[(size_t)(c0 + r) * pw + c0 + c] = v;
-      if (r == nr - 1 && c < nc) z[c0 + c] = v;
-    }
-    __syncthreads();   // the panel is in the slab (and P free) before the next update reads it
+  if (!wide_panel_chol(L, pw, m, P, dg, z, entry)) {
+    if (tid == 0) *out = -INFINITY;
+    return;
   }
 
   if (tid == 0) {

@@ -37,7 +37,9 @@ whitening= of the semiparametric calls above is not routed there and raises.
 MIN_WIDE_FEATURES = 65 to MAX_WIDE_FEATURES = 256 summaries (the scratch-assay example has 145), standard (Warton
 shrinkage or none, whitening) and unbiased, with the (G, K, P) call shape of `syn_loglik`;
 `wide_standard_likelihood(...)` / `wide_unbiased_likelihood()` are the `likelihood=` for BSL, select_penalty and
-log_SL_stdev.  Every other call here, the robust variants and slice_gamma included, takes at most MAX_FEATURES = 64.
+log_SL_stdev.  `wide_semi_loglik` mirrors `elfihip_semi_loglik_wide` (csrc/semibsl_wide.hip): semi_loglik for the same 65 to
+256 summaries, Warton shrinkage or none; `wide_semiparametric_likelihood(...)` is its `likelihood=`.  Every other call
+here -- the whitened semiparametric form, the robust variants and slice_gamma included -- takes at most MAX_FEATURES = 64.
 
 Not on the device: graphical-lasso shrinkage inside the semiparametric likelihoods, estimate_whitening_matrix
 (the reference's runs once before sampling, on the device models too; its W goes straight into the calls here).  They
@@ -54,7 +56,7 @@ from . import _lib
 from .priors import SLICE_GAMMA_STREAM_BASE
 
 MAX_FEATURES = 64
-MIN_WIDE_FEATURES, MAX_WIDE_FEATURES = 65, 256      # the wide Gaussian likelihood (csrc/synlik_wide.hip)
+MIN_WIDE_FEATURES, MAX_WIDE_FEATURES = 65, 256      # the wide likelihoods (csrc/synlik_wide.hip, csrc/semibsl_wide.hip)
 MAX_SEMI_ROWS = 16384       # rows per group of the semiparametric likelihood: one column is held in LDS
 _VARIANTS = {'standard': 0, 'unbiased': 1, 'mean': 2, 'variance': 3}
 _CLASSES = {}
@@ -248,6 +250,17 @@ def semi_loglik(ssx, ssy, n_groups=1, shrinkage=None, penalty=None, prefixes=Non
                        [(G, m), (G, m, m), (G, n, m)], return_parts, ctx)
 
 
+def wide_semi_loglik(ssx, ssy, n_groups=1, shrinkage=None, penalty=None, prefixes=None, penalties=None, return_parts=False,
+                     ctx=None):
+    """semi_loglik for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries (`elfihip_semi_loglik_wide`): layouts, shrinkage,
+    lists, the -inf cases, the shape of the result and return_parts as semi_loglik; narrower input belongs to semi_loglik."""
+    groups = _groups(ssx, ssy, n_groups, MAX_SEMI_ROWS, width=(MIN_WIDE_FEATURES, MAX_WIDE_FEATURES),
+                     kernel='wide semiparametric device')
+    G, n, m = groups[2:5]
+    return _group_call("elfihip_semi_loglik_wide", groups, shrinkage, penalty, penalties, prefixes, (),
+                       [(G, m), (G, m, m), (G, n, m)], return_parts, ctx)
+
+
 def wsemi_loglik(ssx, ssy, whitening, n_groups=1, shrinkage=None, penalty=None, prefixes=None, penalties=None,
                  return_parts=False, ctx=None):
     """Whitened semiparametric synthetic log-likelihoods (wsemiBSL: the normal scores of the rows are multiplied by
@@ -304,6 +317,11 @@ def semi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitening
     return np.array([semi_loglik(_one_group(ssx), ssy, shrinkage=shrinkage, penalty=penalty)])
 
 
+def wide_semi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None):
+    """semi_param_kernel_estimate for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries; np.array([ll])."""
+    return np.array([wide_semi_loglik(_one_group(ssx), ssy, shrinkage=shrinkage, penalty=penalty)])
+
+
 def wsemi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
     """Whitened semiparametric synthetic log-likelihood (semi_param_kernel_estimate with whitening=, pdf_methods.py:
     232-244) of one (n, m) summary matrix; np.array([ll])."""
@@ -338,6 +356,13 @@ def semiparametric_likelihood(shrinkage=None, penalty=None, whitening=None):
     return partial(semi_param_kernel_estimate, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
 
 
+def wide_semiparametric_likelihood(shrinkage=None, penalty=None):
+    """semiparametric_likelihood for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries: a `likelihood=` for elfi.BSL, HipBSL,
+    select_penalty and log_SL_stdev."""
+    _check_shrinkage(shrinkage)
+    return partial(wide_semi_param_kernel_estimate, shrinkage=shrinkage, penalty=penalty)
+
+
 def whitened_semiparametric_likelihood(whitening, shrinkage=None, penalty=None):
     """pdf_methods.semiparametric_likelihood(whitening=W) on the device (wsemiBSL; Warton shrinkage or none): a
     `likelihood=` for elfi.BSL, HipBSL, select_penalty and log_SL_stdev."""
@@ -361,7 +386,7 @@ def robust_likelihood(adjustment):
 
 def _likelihood_setup(likelihood, **override):
     """(batched call, its keywords) of one of the callables above (None: the standard one): syn_loglik, wide_syn_loglik,
-    semi_loglik or wsemi_loglik, which is called as batched(groups, observed, **keywords)."""
+    semi_loglik, wide_semi_loglik or wsemi_loglik, which is called as batched(groups, observed, **keywords)."""
     kw = {}
     fn = likelihood
     if isinstance(likelihood, partial):
@@ -374,6 +399,11 @@ def _likelihood_setup(likelihood, **override):
         if kw.get('whitening') is not None:
             raise NotImplementedError('the whitened semiparametric likelihood (wsemiBSL) is not on the device')
         return semi_loglik, dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'))
+    if fn is wide_semi_param_kernel_estimate:
+        kw.update({k: v for k, v in override.items() if not (k == 'whitening' and v is None)})
+        if 'whitening' in kw:
+            raise NotImplementedError('the whitened semiparametric likelihood stops at %d summaries' % MAX_FEATURES)
+        return wide_semi_loglik, dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'))
     if fn is wsemi_param_kernel_estimate:
         kw.update({k: v for k, v in override.items() if not (k == 'whitening' and v is None)})
         if kw.get('whitening') is None:

@@ -425,6 +425,21 @@ int elfihip_semi_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64
                             const int64_t* prefixes, int K, const double* penalties, int P, double* dloglik, double* du,
                             double* drho, double* dscores);
 
+/* The wide form: 65 <= m <= 256 summaries, 2 <= n <= 16384.  Arguments, formulas, outputs and determinism as
+ * elfihip_semi_loglik; a narrower m is ELFIHIP_ERR_ARG and belongs to elfihip_semi_loglik.  -inf with the status left at
+ * ELFIHIP_OK, as there: a u_j of 0 or 1, a column without spread, a non-positive Cholesky pivot, a non-finite value, two
+ * rows.  Three kernels (csrc/semibsl_wide.hip): the columns' density estimates and scores, the rank correlation in 64 x 64
+ * blocks, then one workgroup per (group, prefix, penalty) that factors its matrix on a slab of the context's work space.
+ * The host cuts the call into launches so that the work space stays under the cap of elfihip_syn_loglik_wide (256 MiB,
+ * elfihip_syn_wide_set_cap; one (group, prefix)'s scores and matrix and one slab are the least); a result does not depend
+ * on the cut, on G, K or P, and prefix p has the bits of a group of p rows. */
+int elfihip_semi_loglik_wide(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, int m, int64_t ldx, const double* y,
+                             const int64_t* prefixes, int K, const double* penalties, int P, double* loglik, double* u,
+                             double* rho, double* scores);
+int elfihip_semi_loglik_wide_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx,
+                                 const double* dy, const int64_t* prefixes, int K, const double* penalties, int P,
+                                 double* dloglik, double* du, double* drho, double* dscores);
+
 /* The whitened semiparametric synthetic log-likelihood (wsemiBSL, Priddle et al. 2021; the whitening branch of
  * elfi/methods/bsl/pdf_methods.py:213-264 and gaussian_copula_density.py:33-60) of G groups of n rows in one call.  The
  * arguments of elfihip_semi_loglik and W, the whitening matrix (m x m, row-major, pitch m).  Per column of the first p
