@@ -54,7 +54,8 @@ from .synlik import (HipBSL, glasso_likelihood, glasso_loglik, graphical_lasso, 
                      semiparametric_likelihood, slice_gamma, slice_gamma_mean, slice_gamma_variance, standard_likelihood,
                      syn_loglik, unbiased_likelihood, whitened_semiparametric_likelihood, wide_semi_loglik,
                      wide_semi_param_kernel_estimate, wide_semiparametric_likelihood, wide_standard_likelihood,
-                     wide_syn_loglik, wide_unbiased_likelihood, wsemi_loglik, wsemi_param_kernel_estimate)
+                     wide_syn_loglik, wide_unbiased_likelihood, wide_whitened_semiparametric_likelihood,
+                     wide_wsemi_loglik, wide_wsemi_param_kernel_estimate, wsemi_loglik, wsemi_param_kernel_estimate)
 from .logratio import HipLogisticRegression, hip_logistic_regression_class, log_ratio  # noqa: F401
 from .bolfire import HipBOLFIRE, HipBOLFIREPosterior, hip_bolfire_class  # noqa: F401
 from .twostage import (HipTwoStageSelection, hip_two_stage_selection_class, knn_entropy, mrsse,  # noqa: F401

@@ -22,33 +22,28 @@
 //   finish    one workgroup of 256 threads per (job, penalty): the left-looking panel Cholesky of wide_chol.hpp on the
 //             job's slab, entry (i, j) = (1 - l) rho_ij + l [i == j] (corr_warton: no eps) formed as it is needed and eta
 //             riding along as row m; then semibsl_finish_kernel's sums in index order in one thread and its formula.
+// The gram and finish kernels are templates on their argument struct (semi_wide.hpp): wsemibsl_wide.hip, the whitened form,
+// runs the gram kernel with a covariance epilogue as well and the finish kernel on the scaled matrix.
 // No atomics, every sum in a fixed order: one (group, prefix, penalty) result depends neither on G, K, P nor on how the
 // host cuts the jobs into launches to keep the workspace under the context's cap.  -inf with the status left at
 // ELFIHIP_OK: as semibsl.hip (a u_j of 0 or 1, a column without spread, a non-positive pivot, a non-finite value, p = 2).
-#include "semi_rank.hpp"
-#include "wide_chol.hpp"
+#include "semi_wide.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
 namespace elfihip {
 
-constexpr int SMW_RC = 32;             // rows per staged chunk (8 MFMA steps)
-constexpr int SMW_CP = SMW_RC + 2;     // pitch of a staged column
-
-struct SemiGramArgs {
-  const double* Q;          // (jobs, m, NP) of this launch
-  const double* stats;      // (jobs, SEMI_WIDE_STATS)
-  double* R;                // (jobs, mpad, mpad): rho, the lower blocks
-  double* rho;              // (G, m, m) or NULL
-  const int64_t* prefixes;  // (K)
-  int64_t n, job0;          // job0: the launch's first job in the call, job = g K + k
-  int m, mpad, NP, K, pairs;
-};
-
-__global__ __launch_bounds__(256) void semibsl_wide_gram_kernel(SemiGramArgs A) {
+// Args (semi_wide.hpp) picks the epilogue: SemiGramArgs rho of the scores at Q; SemiCovArgs their covariance for the whitened
+// form, C_ab = ((Q^T Q)_ab - s_a s_b / p) / (p - 1), every block of the job's padded matrix, one value at (a, b) and (b, a).
+// The column sums s of the staged columns are taken from the staged chunks in the two-level order (a thread per column: the
+// 32 staged rows in order, then the total), so every workgroup that holds column a has the same bits of s_a.
+template <class Args>
+__global__ __launch_bounds__(256) void semibsl_wide_gram_kernel(Args A) {
+  constexpr bool COV = std::is_same<Args, SemiCovArgs>::value;
   __shared__ __align__(16) double stage[2 * SW_BLK * SMW_CP];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, m = A.m;
   const int64_t lj = blockIdx.x / (unsigned)A.pairs;
@@ -68,6 +63,7 @@ __global__ __launch_bounds__(256) void semibsl_wide_gram_kernel(SemiGramArgs A) 
 #pragma unroll
   for (int i = 0; i < 4; ++i) tot[i] = (v4d){0.0, 0.0, 0.0, 0.0};
   const int lr = lane >> 4, lc = lane & 15;
+  [[maybe_unused]] double stot = 0.0;   // COV: the sum of staged column tid
   for (int r0 = 0; r0 < p; r0 += SMW_RC) {
     __syncthreads();  // the previous chunk is consumed
     for (int e = tid; e < slabs * SW_BLK * SMW_RC; e += 256) {
@@ -88,10 +84,39 @@ __global__ __launch_bounds__(256) void semibsl_wide_gram_kernel(SemiGramArgs A) 
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) tot[i] += chk[i];
+    if constexpr (COV) {
+      if (tid < slabs * SW_BLK) {
+        double sc = 0.0;
+        for (int rr = 0; rr < SMW_RC; ++rr) sc += stage[tid * SMW_CP + rr];   // rows beyond p are zeros
+        stot += sc;
+      }
+    }
   }
 
-  const double den = A.stats[lj * SEMI_WIDE_STATS + 2 * SEMI_WIDE_M];
   double* Rj = A.R + (size_t)lj * A.mpad * A.mpad;
+  if constexpr (COV) {
+    __shared__ double csum[2 * SW_BLK];   // the column sums of block bi, then of block bj
+    if (tid < slabs * SW_BLK) csum[tid] = stot;
+    __syncthreads();
+    const double dp = (double)p;
+    const int cl = 16 * wv + lc;
+    const int col = SW_BLK * bj + cl;
+    const double sb = csum[(diag ? 0 : SW_BLK) + cl];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rl = 16 * i + lr + 4 * r;
+        const int row = SW_BLK * bi + rl;
+        if (col <= row) {   // (above the diagonal of a diagonal block: its mirror writes)
+          const double v = (tot[i][r] - csum[rl] * sb / dp) / (dp - 1.0);
+          Rj[(size_t)row * A.mpad + col] = v;
+          Rj[(size_t)col * A.mpad + row] = v;
+        }
+      }
+    return;
+  }
+  const double den = A.stats[lj * SEMI_WIDE_STATS + 2 * SEMI_WIDE_M];
   double* rho = (A.rho && p == A.n) ? A.rho + (gk / A.K) * m * m : nullptr;
   const int col = SW_BLK * bj + 16 * wv + lc;
 #pragma unroll
@@ -108,19 +133,11 @@ __global__ __launch_bounds__(256) void semibsl_wide_gram_kernel(SemiGramArgs A) 
     }
 }
 
-struct SemiWideFinArgs {
-  const double* R;          // (jobs, mpad, mpad) of the gram launch
-  const double* stats;      // (jobs, SEMI_WIDE_STATS)
-  double* slabs;            // one per workgroup
-  double* loglik;           // (G, K, max(P, 1))
-  const int64_t* prefixes;  // (K)
-  const double* penalties;  // (P) or NULL
-  int64_t job0;             // the gram launch's first job in the call
-  int64_t fjob0;            // this launch's first (job, penalty), counted from the gram launch's first job
-  int m, mpad, pw, K, P;
-};
-
-__global__ __launch_bounds__(256) void semibsl_wide_finish_kernel(SemiWideFinArgs A) {
+// Args (semi_wide.hpp): SemiWideFinArgs the matrix and eta above; WsemiWideFinArgs the whitened form's scaled entry
+// d_i ((1 - l) rho_ij + l [i == j]) d_j with eta_w as row m, and -inf before the factorisation if a d is not positive and finite.
+template <class Args>
+__global__ __launch_bounds__(256) void semibsl_wide_finish_kernel(Args A) {
+  constexpr bool SCALED = std::is_same<Args, WsemiWideFinArgs>::value;
   extern __shared__ __align__(16) double lds[];
   const int m = A.m, mpad = A.mpad;
   double* P = lds;                            // (m + 1, SW_PP) the panel
@@ -143,18 +160,37 @@ __global__ __launch_bounds__(256) void semibsl_wide_finish_kernel(SemiWideFinArg
     if (tid == 0) *out = -INFINITY;
     return;
   }
-  if (tid < m) {
-    eta[tid] = st[tid];
-    lpv[tid] = st[SEMI_WIDE_M + tid];
+  [[maybe_unused]] double* dsc = lpv + mpad;   // SCALED: d
+  if constexpr (SCALED) {
+    const double* ws = A.wst + lj * WSEMI_WIDE_STATS;
+    double d = 1.0;
+    if (tid < m) {
+      eta[tid] = ws[SEMI_WIDE_M + tid];   // eta_w
+      lpv[tid] = st[SEMI_WIDE_M + tid];
+      dsc[tid] = d = ws[tid];
+    }
+    if (__syncthreads_or(!(d > 0.0 && d <= 1.7976931348623157e308))) {
+      if (tid == 0) *out = -INFINITY;
+      return;
+    }
+  } else {
+    if (tid < m) {
+      eta[tid] = st[tid];
+      lpv[tid] = st[SEMI_WIDE_M + tid];
+    }
+    __syncthreads();
   }
-  __syncthreads();
   const double lam = A.P > 0 ? A.penalties[pi] : 0.0;
   const double gam = 1.0 - lam;
   // entry (i, j <= i) of the matrix to factor, row m eta: its forward solve is the factorisation's own update
   const auto entry = [&](int i, int j) -> double {
     if (j >= m || j > i) return 0.0;
     if (i == m) return eta[j];
-    return i == j ? gam + lam : gam * Rj[(size_t)i * mpad + j];
+    const double v = i == j ? gam + lam : gam * Rj[(size_t)i * mpad + j];
+    if constexpr (SCALED)
+      return dsc[i] * (v * dsc[j]);
+    else
+      return v;
   };
   if (!wide_panel_chol(L, A.pw, m, P, dg, z, entry)) {
     if (tid == 0) *out = -INFINITY;
@@ -189,11 +225,41 @@ static int semi_wide_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n
   return ELFIHIP_OK;
 }
 
+template <class Args>
+static int launch_gram(elfihip_ctx* ctx, const Args& M, int64_t jobs, const char* name) {
+  hipLaunchKernelGGL(semibsl_wide_gram_kernel<Args>, dim3((unsigned)(jobs * M.pairs)), dim3(256), 0, ctx->stream, M);
+  return launch_status(ctx, name);
+}
+
+int semibsl_wide_launch_gram(elfihip_ctx* ctx, const SemiGramArgs& M, int64_t jobs) {
+  return launch_gram(ctx, M, jobs, "wide semiparametric likelihood gram kernel");
+}
+
+int semibsl_wide_launch_cov(elfihip_ctx* ctx, const SemiCovArgs& M, int64_t jobs) {
+  return launch_gram(ctx, M, jobs, "wide whitened semiparametric likelihood covariance kernel");
+}
+
+// extra: doubles of LDS behind the factorisation's and the two vectors
+template <class Args>
+static int launch_finish(elfihip_ctx* ctx, const Args& F, int64_t count, size_t extra, const char* name) {
+  const size_t lds = (wide_chol_lds(F.m) + 2 * (size_t)F.mpad + extra) * sizeof(double);
+  ELFIHIP_TRY(set_lds(ctx, semibsl_wide_finish_kernel<Args>, lds, 48 * 1024));
+  hipLaunchKernelGGL(semibsl_wide_finish_kernel<Args>, dim3((unsigned)count), dim3(256), lds, ctx->stream, F);
+  return launch_status(ctx, name);
+}
+
+int semibsl_wide_launch_finish(elfihip_ctx* ctx, const SemiWideFinArgs& F, int64_t count) {
+  return launch_finish(ctx, F, count, 0, "wide semiparametric likelihood finish kernel");
+}
+
+int semibsl_wide_launch_finish_scaled(elfihip_ctx* ctx, const WsemiWideFinArgs& F, int64_t count) {
+  return launch_finish(ctx, F, count, (size_t)F.mpad, "wide whitened semiparametric likelihood finish kernel");
+}
+
 // Device rows, y and outputs; host prefixes and penalties (checked above).
 static int semi_wide_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx, const double* dy,
                               const int64_t* prefixes, int K, const double* penalties, int P, double* dll, double* du,
                               double* drho, double* dscores) {
-  hipStream_t st = ctx->stream;
   const GroupParams B = group_params(prefixes, K, n, nullptr, penalties, P);
   double* dpar;
   ELFIHIP_TRY(upload_group_params(ctx, B, 0, &dpar));
@@ -255,19 +321,14 @@ static int semi_wide_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int
   F.pw = pw;
   F.K = Ke;
   F.P = P;
-  const size_t fin_lds = (wide_chol_lds(m) + 2 * (size_t)mpad) * sizeof(double);
-  ELFIHIP_TRY(set_lds(ctx, semibsl_wide_finish_kernel, fin_lds, 48 * 1024));
   for (int64_t j0 = 0; j0 < J; j0 += Jc) {
     const int64_t jc = std::min<int64_t>(Jc, J - j0);
     C.job0 = M.job0 = F.job0 = j0;
     ELFIHIP_TRY(semibsl_launch_column_wide(ctx, C, jc));
-    hipLaunchKernelGGL(semibsl_wide_gram_kernel, dim3((unsigned)(jc * pairs)), dim3(256), 0, st, M);
-    ELFIHIP_TRY(launch_status(ctx, "wide semiparametric likelihood gram kernel"));
+    ELFIHIP_TRY(semibsl_wide_launch_gram(ctx, M, jc));
     for (int64_t f0 = 0; f0 < jc * Pe; f0 += Fc) {
       F.fjob0 = f0;
-      const int64_t fc = std::min<int64_t>(Fc, jc * Pe - f0);
-      hipLaunchKernelGGL(semibsl_wide_finish_kernel, dim3((unsigned)fc), dim3(256), fin_lds, st, F);
-      ELFIHIP_TRY(launch_status(ctx, "wide semiparametric likelihood finish kernel"));
+      ELFIHIP_TRY(semibsl_wide_launch_finish(ctx, F, std::min<int64_t>(Fc, jc * Pe - f0)));
     }
   }
   return ELFIHIP_OK;

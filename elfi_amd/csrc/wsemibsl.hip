@@ -38,10 +38,11 @@
 // -inf, with the status left at ELFIHIP_OK: semibsl.hip's list (a u_j of 0 or 1, a column without spread, a non-positive
 // pivot, a non-finite value, two rows and m > 1) and a d_a that is not positive and finite.  A decided divergence: the
 // reference lets W eta turn an infinite eta_j (u_j of 0 or 1) into NaN where W has a zero, and returns NaN; here it is -inf.
-#include "semi_rank.hpp"
+#include "semi_wide.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -118,27 +119,57 @@ __global__ __launch_bounds__(256) void wsemi_transform_kernel(WsemiArgs A) {
   }
 }
 
-__global__ __launch_bounds__(256) void wsemi_rerank_kernel(WsemiArgs A) {
+// Args picks the layout: WsemiArgs T (G K, m, n) and Q2 row-major at pitch MP; WsemiWideArgs (semi_wide.hpp) the wide one
+// of wsemibsl_wide.hip, T and Q2 (jobs, m, NP) of a launch that holds a part of the call's jobs.  Q2 may be T there: a
+// workgroup has read its column before it writes it.
+template <class Args>
+__global__ __launch_bounds__(256) void wsemi_rerank_kernel(Args A) {
+  constexpr bool WIDE = std::is_same<Args, WsemiWideArgs>::value;
   extern __shared__ __align__(16) double lds[];
   double* col = lds;   // the column of T, NaN up to a multiple of 4
   const int tid = threadIdx.x, m = A.S.m;
   const int j = (int)(blockIdx.x % (unsigned)m);
-  const int64_t gk = blockIdx.x / (unsigned)m;
+  const int64_t lj = blockIdx.x / (unsigned)m;   // the job within the launch
+  int64_t gk = lj;
+  if constexpr (WIDE) gk += A.S.job0;
   const int64_t g = gk / A.S.K, n = A.S.n;
   const int p = (int)A.S.prefixes[gk % A.S.K];
   const int pp = (p + 3) & ~3;
   const bool full = p == n;
-  const double* Tc = A.T + (gk * m + j) * n;
+  const double* Tc;
+  if constexpr (WIDE)
+    Tc = A.T + (lj * m + j) * A.S.NP;
+  else
+    Tc = A.T + (gk * m + j) * n;
   for (int i = tid; i < pp; i += 256) col[i] = i < p ? Tc[i] : NAN;
   __syncthreads();
   const double np1 = (double)p + 1.0;
-  double* Qg = A.Q2 + gk * n * A.S.MP + j;
+  double* Qg;
+  int64_t qp = 1;   // pitch of consecutive rows
+  if constexpr (WIDE) {
+    Qg = A.Q2 + (lj * m + j) * A.S.NP;
+  } else {
+    Qg = A.Q2 + gk * n * A.S.MP + j;
+    qp = A.S.MP;
+  }
   const double2* col2 = reinterpret_cast<const double2*>(col);
   for (int i = tid; i < p; i += 256) {
     const double q = rank_score(col2, pp, col[i], np1);
-    Qg[(int64_t)i * A.S.MP] = q;
+    Qg[(int64_t)i * qp] = q;
     if (A.scores && full) A.scores[(g * n + i) * m + j] = q;
   }
+}
+
+template <class Args>
+static int launch_rerank(elfihip_ctx* ctx, const Args& A, int64_t jobs, const char* name) {
+  const size_t bytes = (size_t)((A.S.n + 3) & ~(int64_t)3) * sizeof(double);
+  ELFIHIP_TRY(set_lds(ctx, wsemi_rerank_kernel<Args>, bytes, 48 * 1024));
+  hipLaunchKernelGGL(wsemi_rerank_kernel<Args>, dim3((unsigned)(jobs * A.S.m)), dim3(256), bytes, ctx->stream, A);
+  return launch_status(ctx, name);
+}
+
+int wsemi_launch_rerank_wide(elfihip_ctx* ctx, const WsemiWideArgs& A, int64_t jobs) {
+  return launch_rerank(ctx, A, jobs, "wide whitened semiparametric likelihood re-rank kernel");
 }
 
 template <int T>
@@ -318,7 +349,6 @@ static int wsemi_check(elfihip_ctx* ctx, const void* X, int64_t G, int64_t n, in
 static int wsemi_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx, const double* dy,
                           const double* dW, const int64_t* prefixes, int K, const double* penalties, int P, double* dll,
                           double* du, double* drho, double* dscale, double* dscores) {
-  hipStream_t st = ctx->stream;
   const int64_t GK = G * (prefixes ? K : 1);
   // scratch: [Q][Q'][T][stats], Q' and T between semi_setup's two
   const size_t qd = (size_t)GK * (size_t)n * (16 * group_tiles(m)), td = (size_t)GK * (size_t)n * m;
@@ -336,10 +366,7 @@ static int wsemi_dev_impl(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t
       ctx, m, (unsigned)(GK * A.chunks), "whitened semiparametric likelihood transform kernel",
       [](auto T) { return wsemi_transform_kernel<decltype(T)::value>; },
       [](auto T) { return (size_t)TransformShape<decltype(T)::value>::DOUBLES * sizeof(double); }, A));
-  const size_t bytes = (size_t)((n + 3) & ~(int64_t)3) * sizeof(double);
-  ELFIHIP_TRY(set_lds(ctx, wsemi_rerank_kernel, bytes, 48 * 1024));
-  hipLaunchKernelGGL(wsemi_rerank_kernel, dim3((unsigned)(GK * m)), dim3(256), bytes, st, A);
-  ELFIHIP_TRY(launch_status(ctx, "whitened semiparametric likelihood re-rank kernel"));
+  ELFIHIP_TRY(launch_rerank(ctx, A, GK, "whitened semiparametric likelihood re-rank kernel"));
   return launch_by_tiles(
       ctx, m, (unsigned)GK, "whitened semiparametric likelihood finish kernel",
       [](auto T) { return wsemi_finish_kernel<decltype(T)::value>; },

@@ -38,8 +38,10 @@ MIN_WIDE_FEATURES = 65 to MAX_WIDE_FEATURES = 256 summaries (the scratch-assay e
 shrinkage or none, whitening) and unbiased, with the (G, K, P) call shape of `syn_loglik`;
 `wide_standard_likelihood(...)` / `wide_unbiased_likelihood()` are the `likelihood=` for BSL, select_penalty and
 log_SL_stdev.  `wide_semi_loglik` mirrors `elfihip_semi_loglik_wide` (csrc/semibsl_wide.hip): semi_loglik for the same 65 to
-256 summaries, Warton shrinkage or none; `wide_semiparametric_likelihood(...)` is its `likelihood=`.  Every other call
-here -- the whitened semiparametric form, the robust variants and slice_gamma included -- takes at most MAX_FEATURES = 64.
+256 summaries, Warton shrinkage or none; `wide_semiparametric_likelihood(...)` is its `likelihood=`.  `wide_wsemi_loglik`
+mirrors `elfihip_wsemi_loglik_wide` (csrc/wsemibsl_wide.hip): wsemi_loglik for the same widths;
+`wide_whitened_semiparametric_likelihood(W)` is its `likelihood=`.  Every other call here -- the robust variants and
+slice_gamma included -- takes at most MAX_FEATURES = 64.
 
 Not on the device: graphical-lasso shrinkage inside the semiparametric likelihoods, estimate_whitening_matrix
 (the reference's runs once before sampling, on the device models too; its W goes straight into the calls here).  They
@@ -282,6 +284,21 @@ def wsemi_loglik(ssx, ssy, whitening, n_groups=1, shrinkage=None, penalty=None, 
                        [(G, m), (G, m, m), (G, m), (G, n, m)], return_parts, ctx)
 
 
+def wide_wsemi_loglik(ssx, ssy, whitening, n_groups=1, shrinkage=None, penalty=None, prefixes=None, penalties=None,
+                      return_parts=False, ctx=None):
+    """wsemi_loglik for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries (`elfihip_wsemi_loglik_wide`): layouts, whitening,
+    shrinkage, lists, the -inf cases, the shape of the result and return_parts as wsemi_loglik; narrower input belongs to
+    wsemi_loglik."""
+    groups = _groups(ssx, ssy, n_groups, MAX_SEMI_ROWS, width=(MIN_WIDE_FEATURES, MAX_WIDE_FEATURES),
+                     kernel='wide whitened semiparametric device')
+    G, n, m = groups[2:5]
+    if whitening is None:
+        raise ValueError('the whitened semiparametric likelihood needs a whitening matrix')
+    W = _whitening_matrix(whitening, m, finite=True)
+    return _group_call("elfihip_wsemi_loglik_wide", groups, shrinkage, penalty, penalties, prefixes, (_lib.ptr(W),),
+                       [(G, m), (G, m, m), (G, m), (G, n, m)], return_parts, ctx)
+
+
 # ---- the reference's likelihood callables (pdf_methods.py:77-135, 138-176, 267-316) ----------------------------------
 
 def gaussian_syn_likelihood(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
@@ -330,6 +347,13 @@ def wsemi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitenin
     return np.array([wsemi_loglik(_one_group(ssx), ssy, whitening, shrinkage=shrinkage, penalty=penalty)])
 
 
+def wide_wsemi_param_kernel_estimate(ssx, ssy, shrinkage=None, penalty=None, whitening=None):
+    """wsemi_param_kernel_estimate for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries; np.array([ll])."""
+    if whitening is None:
+        raise ValueError('the whitened semiparametric likelihood needs whitening=')
+    return np.array([wide_wsemi_loglik(_one_group(ssx), ssy, whitening, shrinkage=shrinkage, penalty=penalty)])
+
+
 def standard_likelihood(shrinkage=None, penalty=None, whitening=None):
     """pdf_methods.standard_likelihood on the device (Warton shrinkage or none)."""
     _check_shrinkage(shrinkage)
@@ -372,6 +396,15 @@ def whitened_semiparametric_likelihood(whitening, shrinkage=None, penalty=None):
     return partial(wsemi_param_kernel_estimate, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
 
 
+def wide_whitened_semiparametric_likelihood(whitening, shrinkage=None, penalty=None):
+    """whitened_semiparametric_likelihood for MIN_WIDE_FEATURES to MAX_WIDE_FEATURES summaries: a `likelihood=` for
+    elfi.BSL, HipBSL, select_penalty and log_SL_stdev."""
+    _check_shrinkage(shrinkage)
+    if whitening is None:
+        raise ValueError('the whitened semiparametric likelihood needs a whitening matrix')
+    return partial(wide_wsemi_param_kernel_estimate, shrinkage=shrinkage, penalty=penalty, whitening=whitening)
+
+
 def unbiased_likelihood():
     """pdf_methods.unbiased_likelihood on the device."""
     return gaussian_syn_likelihood_ghurye_olkin
@@ -386,7 +419,7 @@ def robust_likelihood(adjustment):
 
 def _likelihood_setup(likelihood, **override):
     """(batched call, its keywords) of one of the callables above (None: the standard one): syn_loglik, wide_syn_loglik,
-    semi_loglik, wide_semi_loglik or wsemi_loglik, which is called as batched(groups, observed, **keywords)."""
+    semi_loglik, wide_semi_loglik, wsemi_loglik or wide_wsemi_loglik, which is called as batched(groups, observed, **keywords)."""
     kw = {}
     fn = likelihood
     if isinstance(likelihood, partial):
@@ -402,13 +435,15 @@ def _likelihood_setup(likelihood, **override):
     if fn is wide_semi_param_kernel_estimate:
         kw.update({k: v for k, v in override.items() if not (k == 'whitening' and v is None)})
         if 'whitening' in kw:
-            raise NotImplementedError('the whitened semiparametric likelihood stops at %d summaries' % MAX_FEATURES)
+            raise NotImplementedError('the whitened semiparametric likelihood stops at %d summaries here; above, '
+                                      'wide_whitened_semiparametric_likelihood(whitening, ...) is it' % MAX_FEATURES)
         return wide_semi_loglik, dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'))
-    if fn is wsemi_param_kernel_estimate:
+    if fn is wsemi_param_kernel_estimate or fn is wide_wsemi_param_kernel_estimate:
         kw.update({k: v for k, v in override.items() if not (k == 'whitening' and v is None)})
         if kw.get('whitening') is None:
             raise ValueError('the whitened semiparametric likelihood needs whitening=')
-        return wsemi_loglik, dict(shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw['whitening'])
+        return wide_wsemi_loglik if fn is wide_wsemi_param_kernel_estimate else wsemi_loglik, dict(
+            shrinkage=kw.get('shrinkage'), penalty=kw.get('penalty'), whitening=kw['whitening'])
     if fn is gaussian_syn_likelihood_ghurye_olkin and not override:
         return syn_loglik, dict(variant='unbiased')
     if fn is wide_gaussian_syn_likelihood_ghurye_olkin and not override:

@@ -463,6 +463,22 @@ int elfihip_wsemi_loglik_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int6
                              const double* dW, const int64_t* prefixes, int K, const double* penalties, int P,
                              double* dloglik, double* du, double* drho, double* dscale, double* dscores);
 
+/* The wide form: 65 <= m <= 256 summaries, 2 <= n <= 16384.  Arguments, formulas, outputs, the -inf cases and determinism
+ * as elfihip_wsemi_loglik; a narrower m is ELFIHIP_ERR_ARG and belongs to elfihip_wsemi_loglik, a NULL W is
+ * ELFIHIP_ERR_ARG.  Seven launches per cut (csrc/wsemibsl_wide.hip): the columns' density estimates and scores Q, T = Q W^T
+ * in slabs of W by MFMA, the ranks and scores of T's columns, rho of those and C = cov(Q) in 64 x 64 blocks,
+ * d^2 = diag(W C W^T) and eta_w = W eta per block of 64 rows of W, then one workgroup per (group, prefix, penalty) that
+ * factors diag(d) ((1 - l) rho + l I) diag(d) on a slab of the context's work space.  The host cuts the call into launches
+ * so that the work space stays under the cap of elfihip_syn_loglik_wide (256 MiB, elfihip_syn_wide_set_cap; one (group,
+ * prefix)'s two score matrices, rho and C, and one slab are the least); a result does not depend on the cut, on G, K or P,
+ * and prefix p has the bits of a group of p rows. */
+int elfihip_wsemi_loglik_wide(elfihip_ctx* ctx, const double* X, int64_t G, int64_t n, int m, int64_t ldx, const double* y,
+                              const double* W, const int64_t* prefixes, int K, const double* penalties, int P, double* loglik,
+                              double* u, double* rho, double* scale, double* scores);
+int elfihip_wsemi_loglik_wide_dev(elfihip_ctx* ctx, const double* dX, int64_t G, int64_t n, int m, int64_t ldx,
+                                  const double* dy, const double* dW, const int64_t* prefixes, int K, const double* penalties,
+                                  int P, double* dloglik, double* du, double* drho, double* dscale, double* dscores);
+
 /* KLIEP density-ratio estimation (elfi/methods/density_ratio_estimation.py: fit, _KLIEP :183-202, _KLIEP_lcv :157-181) of
  * numerator rows x (Nx, d), pitch ldx, against denominator rows y (Ny, d), pitch ldy, for S basis scales in one call; with
  * F > 0 folds also the S x F leave-fold-out fits of the likelihood cross-validation.
